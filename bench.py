@@ -74,6 +74,27 @@ def sources_hash(files):
     return h.hexdigest()[:12]
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # the .npy files of --dump-outputs, headers included
+
+
+def dump_outputs(path, out, seed=0):
+    """Write the per-ray outputs ``out`` of render_rays as <path>/<name>.npy, float32.  Above DUMP_LIMIT_BYTES in all, every
+    array keeps the same rays: a sorted sample drawn with a fixed seed, the same from run to run and from build to build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu() for k, v in sorted(out.items())}
+    n = next(iter(host.values())).shape[0]
+    total = sum(t.numel() * 4 for t in host.values())
+    rows = None
+    budget = DUMP_LIMIT_BYTES - 1024 * len(host)      # room for the .npy headers
+    if total > budget:
+        keep = budget // (total // n)
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+    for k, t in host.items():
+        np.save(os.path.join(path, k + ".npy"), (t if rows is None else t[rows]).numpy())
+    return {"dir": path, "arrays": sorted(host), "rays": n if rows is None else int(rows.numel()), "of_rays": n}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -96,6 +117,10 @@ def main():
     ap.add_argument("--no-face-safe", action="store_true", help="fast path without canonical cell selection near voxel faces (A/B)")
     ap.add_argument("--no-hotpath", action="store_true",
                     help="skip the whole-path stage timings (scripts/bench_hotpath_*.py) reported under \"hot_path\"")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0: depth, acc, max_depth, nears, fars "
+                         "[, rgb, sem] of every ray) as DIR/<name>.npy, float32; above 64 MB in all, the same seeded sample of "
+                         "rays from every array")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -184,6 +209,8 @@ def main():
         step(args.warmup + i)
     fence()
     elapsed = time.perf_counter() - t0
+    # the last timed step's outputs, copied on the device (the launches below overwrite `out`); written to disk at the end
+    last_out = {k: v.clone() for k, v in out.items()} if args.dump_outputs and rank == 0 else None
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -535,6 +562,8 @@ def main():
             "scaling": "strong" if split else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": cfg_out, "roofline": roof, "cpu_baseline": cpu_baseline, "ranks_seen": ranks_seen,
         }
+        if last_out is not None:
+            line["outputs_dumped"] = dump_outputs(args.dump_outputs, last_out)
         if world > 1:   # the all-reduced quantity itself: mean rendered depth over every rank's rays (same on all ranks)
             # (slots hold depth SUMS over all ranks; scaled here, after every timed section: a first-use kernel load between
             # the timed loop and the event-timed launches idles the GPU long enough to drop its clocks, measured +10 %)

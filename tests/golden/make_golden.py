@@ -1538,6 +1538,26 @@ def golden_encoder_full(REG):
     print('encoder_full: loss', float(loss), 'visible', {n: float(arrs[f'visible_frac.{n}']) for n in ('hw', 'zh', 'wz')})
 
 
+def golden_shipped_configs():
+    """shipped_configs_sha256.json: per experiment config the reference ships (config/{nuscenes,kitti,kitti_raw}/*.py, read
+    through selfocc_amd.config), its path and the digest of its hot-path part (tests/util.shipped_cfg_digest) — pins
+    scripts/shipped_cfg/*.json without carrying the configs themselves"""
+    import glob
+    import json
+    from selfocc_amd.config import Config
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from util import shipped_cfg_digest
+    out = {}
+    for path in sorted(f for d in ("nuscenes", "kitti", "kitti_raw") for f in glob.glob(os.path.join(REF, "config", d, "*.py"))):
+        out[os.path.basename(path)[:-3]] = dict(source=os.path.relpath(path, REF),
+                                                sha256=shipped_cfg_digest(Config.fromfile(path).to_dict()))
+    path = os.path.join(HERE, "shipped_configs_sha256.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"wrote {path}: {len(out)} configs")
+
+
 if __name__ == '__main__':
     assert os.path.isdir(REF), f"{REF} not found: golden vectors can only be regenerated where the reference is mounted"
     sys.path.insert(0, REF)
@@ -1552,7 +1572,7 @@ if __name__ == '__main__':
                 train_step=lambda: golden_train_step(REG, LOSS_REG),
                 train_step_variants=lambda: golden_train_step_variants(REG, LOSS_REG),
                 train_steps_k=lambda: golden_train_steps(REG, LOSS_REG),
-                encoder_full=lambda: golden_encoder_full(REG))
+                encoder_full=lambda: golden_encoder_full(REG), shipped_configs=golden_shipped_configs)
     for name, fn in todo.items():
         if not only or name in only:
             fn()

@@ -445,7 +445,8 @@ def test_msda_kernels_beside_a_bf16_mfma_kernel_on_another_stream(hip):
     with torch.no_grad():
         quiet = {k: f().clone() for k, f in victims.items()}
         torch.cuda.synchronize()
-        sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+        # different priorities: never one hardware queue (two streams of one priority may share it and never overlap)
+        sa, sb = torch.cuda.Stream(), torch.cuda.Stream(priority=torch.cuda.Stream.priority_range()[1])
         bad = {k: 0 for k in victims}
         for k, f in victims.items():
             for _ in range(40):

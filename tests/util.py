@@ -60,3 +60,16 @@ def grad_digest(t):
         return {'full': t}
     rows = t if t.dim() == 2 else t.reshape(-1, t.shape[-1])
     return {'rows8': rows[::8].contiguous(), 'rownorm': rows.norm(dim=1)}
+
+
+def shipped_cfg_digest(c):
+    """sha256 of the hot-path part of a shipped experiment config — the keys scripts/shipped_cfg/*.json carry (model cut to
+    type / lifter / encoder / head) — of a parsed config or of such a dump alike, through JSON with sorted keys (tuples hash
+    as lists).  tests/golden/shipped_configs_sha256.json holds the digests of the reference's configs."""
+    import hashlib
+    import json
+    want = {k: c[k] for k in ("loss", "loss_input_convertion", "img_size", "num_rays", "optimizer", "grad_max_norm",
+                              "crop_size") if k in c}
+    want["model"] = {k: c["model"][k] for k in ("type", "lifter", "encoder", "head")}
+    want["amp"] = c.get("amp", False)
+    return hashlib.sha256(json.dumps(json.loads(json.dumps(want)), sort_keys=True).encode()).hexdigest()
