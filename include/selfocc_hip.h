@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SELFOCC_ABI_VERSION 32
+#define SELFOCC_ABI_VERSION 33
 
 int selfocc_abi_version(void);
 const char *selfocc_last_error(void);
@@ -551,6 +551,41 @@ int selfocc_reproj_fwd(const so_reproj_args *args, void *stream);
 /* d loss / d weights given d loss / d l1 and d loss / d rgb_combine. */
 int selfocc_reproj_bwd(const so_reproj_args *args, const float *g_l1,
                        const float *g_rgb_combine, float *g_weights, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Depth-evaluation metric tail: DepthMetric._after_step (utils/metric_util.py:247-349) and
+ * compute_depth_errors_torch (:424-444) for one frame, in ONE launch (one workgroup per camera).
+ *   pred (N, h, w) f32 rendered depth; loc (N, n, 2) f32 normalised (u, v), 8-byte aligned;
+ *   gt (N, n) f32; mask (N, n) u8, nonzero = valid.  n < 2^24 (counts exact in f32).
+ * Gather: bit-identical to torch's GPU F.grid_sample(pred, loc * 2 - 1, bilinear, border,
+ * align_corners=True).  Median: lower median of the masked gt / sampled pred (torch.median).
+ * Outputs (each optional; at least one requested):
+ *   accumulators: abs_rel .. a3, scaling (n_types, N) f32 and count (1,) f32, added into (+=),
+ *     row raw_row for 'raw', median_row for 'median' (-1: type not evaluated); all or none;
+ *   errors (N, 7) f32 = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 of the raw prediction;
+ *   sampled (N, n) f32 = the gathered depth at every location;
+ *   medians (N, 2) f32 = (median gt, median sampled pred) of the masked points.
+ * A camera with no valid point gives NaN for its metric entries (its 'raw' scaling still
+ * counts 1).  ws: selfocc_depth_metric_ws_bytes(args) bytes of device memory (NULL if 0).
+ * ---------------------------------------------------------------------------------- */
+typedef struct so_depth_metric_args {
+    const float *pred;
+    const float *loc;
+    const float *gt;
+    const uint8_t *mask;
+    int32_t N, h, w, n;
+    int32_t n_types, raw_row, median_row, _pad;
+    float *abs_rel, *sq_rel, *rmse, *rmse_log, *a1, *a2, *a3, *scaling;
+    float *count;
+    float *errors;
+    float *sampled;
+    float *medians;
+    void *ws;
+    uint64_t ws_bytes;
+} so_depth_metric_args;
+
+size_t selfocc_depth_metric_ws_bytes(const so_depth_metric_args *args);
+int selfocc_depth_metric(const so_depth_metric_args *args, void *stream);
 
 #ifdef __cplusplus
 }

@@ -3,3 +3,14 @@
 reference's registry / config surface.  The arithmetic lives in csrc/*.hip behind the C ABI
 of include/selfocc_hip.h; there is no CPU fallback."""
 __version__ = "0.1.0"
+
+_LAZY = {'DepthMetric': 'depth_metric', 'depth_errors': 'depth_metric'}
+
+
+def __getattr__(name):
+    """``from selfocc_amd import DepthMetric`` (the depth-evaluation metric, depth_metric.py) without importing torch
+    at package import."""
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module(f".{_LAZY[name]}", __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -6,7 +6,7 @@ its exported symbols being callable with these layouts.
 """
 import ctypes as C
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 # enums ---------------------------------------------------------------------------
 RAYS_EXPLICIT, RAYS_PIXEL_GRID = 0, 1
@@ -100,6 +100,18 @@ class SoReprojArgs(C.Structure):
     ]
 
 
+class SoDepthMetricArgs(C.Structure):
+    _fields_ = [
+        ("pred", _p), ("loc", _p), ("gt", _p), ("mask", _p),
+        ("N", _i), ("h", _i), ("w", _i), ("n", _i),
+        ("n_types", _i), ("raw_row", _i), ("median_row", _i), ("_pad", _i),
+        ("abs_rel", _p), ("sq_rel", _p), ("rmse", _p), ("rmse_log", _p),
+        ("a1", _p), ("a2", _p), ("a3", _p), ("scaling", _p),
+        ("count", _p), ("errors", _p), ("sampled", _p), ("medians", _p),
+        ("ws", _p), ("ws_bytes", C.c_uint64),
+    ]
+
+
 # every symbol include/selfocc_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "selfocc_abi_version": (C.c_int, []),
@@ -148,4 +160,6 @@ SYMBOLS = {
     "selfocc_ssim_bwd": (C.c_int, [_p] * 4 + [_i] * 4 + [_p, _p, _p, _p]),
     "selfocc_reproj_fwd": (C.c_int, [C.POINTER(SoReprojArgs), _p]),
     "selfocc_reproj_bwd": (C.c_int, [C.POINTER(SoReprojArgs), _p, _p, _p, _p]),
+    "selfocc_depth_metric_ws_bytes": (C.c_size_t, [C.POINTER(SoDepthMetricArgs)]),
+    "selfocc_depth_metric": (C.c_int, [C.POINTER(SoDepthMetricArgs), _p]),
 }
