@@ -35,7 +35,10 @@ struct RayGeom {
 SO_DEVFN RayGeom so_pixel_ray(const so_render_args &a, int cam, int ix, int iy) {
     // RaySampler 'fixed' / 'cellular' lattice (ray_sampler.py:23-31, 58-68) and
     // Img2LiDAR.forward (img2lidar.py:58-69): origin = M[:3,3], dir = M[:3,:3] (u,v,1)
-    const float *M = a.img2lidar + cam * 16;
+    // the camera matrix is read-only for the launch and `cam` is block-uniform: constant address space, i.e. scalar loads
+    // into SGPRs, also where `a` was re-read through an opaque pointer (so_march_fast_ahead's canonical cell)
+    typedef const __attribute__((address_space(4))) float *so_const_fptr;
+    const so_const_fptr M = (so_const_fptr)(a.img2lidar + cam * 16);
     float u = (float)ix * a.sx + a.ox;
     float v = (float)iy * a.sy + a.oy;
     RayGeom g;
@@ -343,6 +346,27 @@ SO_DEVFN float so_alpha_fast(float xs, float hs) {
     return fminf(num * so_fast_rcp(den), 1.0f);
 }
 
+// Value and voxel-unit gradient of the trilinear SDF in the fast path's nested-lerp order (d, then w, then h; the
+// gradients reuse the differences), on packed FP32.  The corners travel as the pairs pk = (v[k], v[k + 4]), h = 0 in the low
+// and h = 1 in the high half — the order the brick records store them in (sdf_brickify_kernel) — so the d- and w-level lerps
+// and the e0 / e1 terms of the d gradient run two-wide with fd / fw broadcast from a low half; the h level combines the two
+// halves of one pair and stays scalar (a half-swapping form otherwise).  Each half of a packed op is exactly
+// the scalar op it replaces (a packed FMA rounds like fmaf): the results are bit-identical to the scalar sequence.
+SO_DEVFN void so_trilerp_fast_pk(so_f32x2 p0, so_f32x2 p1, so_f32x2 p2, so_f32x2 p3, float fh, float fw, float fd,
+                                 float &sdf, float &gvh, float &gvw, float &gvd) {
+    const so_f32x2 bd = {fd, fd}, bw = {fw, fw};
+    const so_f32x2 dda = p1 - p0, ddb = p3 - p2;                        // (dd0, dd2), (dd1, dd3)
+    const so_f32x2 ca = __builtin_elementwise_fma(bd, dda, p0);         // (c0, c2)
+    const so_f32x2 cb = __builtin_elementwise_fma(bd, ddb, p2);         // (c1, c3)
+    const so_f32x2 dw = cb - ca;                                        // (dw0, dw1)
+    const so_f32x2 b = __builtin_elementwise_fma(bw, dw, ca);           // (b0, b1)
+    const so_f32x2 e = __builtin_elementwise_fma(bw, ddb - dda, dda);   // (e0, e1)
+    gvh = b[1] - b[0];
+    sdf = fmaf(fh, gvh, b[0]);
+    gvw = fmaf(fh, dw[1] - dw[0], dw[0]);
+    gvd = fmaf(fh, e[1] - e[0], e[0]);
+}
+
 // ---- free-space skip codes --------------------------------------------------------------------
 // A sample whose two sigmoid arguments both exceed 17.5 has exp(-arg) < 2^-25, so 1 + exp(-arg) == 1.0f and
 // BOTH sigmoids are exactly 1.0f in float32, in the canonical order as well: alpha is the constant
@@ -635,8 +659,8 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
                 if constexpr (CAN_SKIP) {
                     if (use_skip) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 32u, 0);
                 }
-                st.v[0] = lo.x; st.v[1] = lo.y; st.v[2] = lo.z; st.v[3] = lo.w;
-                st.v[4] = hi.x; st.v[5] = hi.y; st.v[6] = hi.z; st.v[7] = hi.w;
+                st.v[0] = lo.x; st.v[4] = lo.y; st.v[1] = lo.z; st.v[5] = lo.w;   // record order: see sdf_brickify_kernel
+                st.v[2] = hi.x; st.v[6] = hi.y; st.v[3] = hi.z; st.v[7] = hi.w;
             } else {
                 const unsigned vo = st.cell * 4u;
                 const so_f2v p00 = so_bload2(rs, vo, 0u), p01 = so_bload2(rs, vo, sD);
@@ -853,8 +877,22 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
 // A skipped step moves 1 byte per lane through the L1 instead of 33.  Nothing is software-pipelined beyond
 // that: measurements showed the march insensitive to load/compute overlap inside a wave (8 waves / SIMD hide it).
 // ---------------------------------------------------------------------------------------
+// The launch arguments re-read from the kernarg segment through a pointer the optimiser cannot see through (the kernels
+// take so_render_args as their FIRST parameter): only the fields used are loaded (s_load), where they are used, and nothing
+// is shared with (or hoisted out of a loop as) the copy the kernel started with.
+SO_DEVFN so_render_args so_reload_args() {
+    typedef const __attribute__((address_space(4))) uint32_t *so_kernarg_ptr;
+    so_kernarg_ptr ka = (so_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    so_render_args ac;
+    static_assert(sizeof(ac) % 4 == 0, "so_render_args is dword-sized");
+#pragma unroll
+    for (unsigned k = 0; k < sizeof(ac) / 4; ++k) ((uint32_t *)&ac)[k] = ka[k];
+    return ac;
+}
+
 struct AheadStep {
-    float fh, fw, fd, fi;
+    float gh, gw, gd, fi;         // grid coordinates (the fractions are taken only by the steps that interpolate)
     int h0, w0, d0;
     unsigned cell, code;
     bool all_interior;            // wave-uniform
@@ -896,7 +934,7 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom,
         st.fi = (float)i;
         const float step = st.fi * dt;
         const float gh = fmaf(Gdh, step, G0h), gw = fmaf(Gdw, step, G0w), gd = fmaf(Gdd, step, G0d);
-        st.fh = __builtin_amdgcn_fractf(gh); st.fw = __builtin_amdgcn_fractf(gw); st.fd = __builtin_amdgcn_fractf(gd);
+        st.gh = gh; st.gw = gw; st.gd = gd;
         const int h0 = so_floor_i(gh), w0 = so_floor_i(gw), d0 = so_floor_i(gd);
         st.h0 = h0; st.w0 = w0; st.d0 = d0;
         const bool interior = ((unsigned)h0 < (unsigned)(H - 1)) & ((unsigned)w0 < (unsigned)(W - 1)) &
@@ -909,18 +947,37 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom,
     auto near_face = [&](float fh, float fw, float fd) __attribute__((always_inline)) {
         return fmaxf(fmaxf(fabsf(fh - 0.5f), fabsf(fw - 0.5f)), fabsf(fd - 0.5f)) > 0.5f - face_m;
     };
-    auto canon_cell = [&](const int i) __attribute__((always_inline)) {   // see so_march_fast
-        const float b0 = so_bin(i, S);
-        const float t_start = b0 * tfar + (1.0f - b0) * tnear;
+    // The sample's cell in the canonical order (see so_march_fast).  Only tnear / tfar stay live across the loop: the ray
+    // and the mapping are re-derived inside this rare branch from launch arguments re-read from the kernarg segment
+    // (so_reload_args) — otherwise the direction stays in VGPRs and every mapping / camera constant in SGPRs across the
+    // march loop (71 VGPRs / 104 SGPRs: 7 waves / SIMD).  The phases are fenced off from one another so that only one
+    // phase's constants are in SGPRs at a time.  geom() is the code that made the ray up front, and the phases are
+    // so_locate's: the same values, bit for bit.
+    auto canon_cell = [&](const int i) __attribute__((always_inline)) {
+        const RayGeom gc = geom(so_reload_args());
+        __builtin_amdgcn_sched_barrier(0);
         float px, py, pz;
-        if (a.sample_pos == SO_SAMPLE_AT_START) {
-            px = g.ox + g.dx * t_start; py = g.oy + g.dy * t_start; pz = g.oz + g.dz * t_start;
-        } else {
-            const float b1 = so_bin(i + 1, S);
-            const float tt = t_start + (b1 * tfar + (1.0f - b1) * tnear);
-            px = g.ox + (g.dx * tt) / 2.0f; py = g.oy + (g.dy * tt) / 2.0f; pz = g.oz + (g.dz * tt) / 2.0f;
+        {
+            const so_render_args ac = so_reload_args();
+            const int n = ac.n_samples;
+            const float b0 = so_bin(i, n);
+            const float t_start = b0 * tfar + (1.0f - b0) * tnear;
+            if (ac.sample_pos == SO_SAMPLE_AT_START) {
+                px = gc.ox + gc.dx * t_start; py = gc.oy + gc.dy * t_start; pz = gc.oz + gc.dz * t_start;
+            } else {
+                const float b1 = so_bin(i + 1, n);
+                const float tt = t_start + (b1 * tfar + (1.0f - b1) * tnear);
+                px = gc.ox + (gc.dx * tt) / 2.0f; py = gc.oy + (gc.dy * tt) / 2.0f; pz = gc.oz + (gc.dz * tt) / 2.0f;
+            }
         }
-        return so_locate(a.map, px, py, pz);
+        __builtin_amdgcn_sched_barrier(0);
+        float slope;
+        const float gh = so_grid_coord(so_axis_m2g(so_reload_args().map.h, py, slope), so_reload_args().map.h.tot_len);
+        __builtin_amdgcn_sched_barrier(0);
+        const float gw = so_grid_coord(so_axis_m2g(so_reload_args().map.w, px, slope), so_reload_args().map.w.tot_len);
+        __builtin_amdgcn_sched_barrier(0);
+        const float gd = so_grid_coord(so_axis_m2g(so_reload_args().map.d, pz, slope), so_reload_args().map.d.tot_len);
+        return so_cell_of(gh, gw, gd);
     };
 
     auto step = [&](const int i, AheadStep &cur, AheadStep &nxt) __attribute__((always_inline)) {
@@ -931,54 +988,61 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom,
             w = kAlphaFree * T;
             T = T * ((1.0f - kAlphaFree) + 1e-7f);
         } else {
-            // (issuing these loads before locate() above, to run it under them, measured 9 % SLOWER)
-            float v[8];
-            float fh = cur.fh, fw = cur.fw, fd = cur.fd;
-            if (cur.all_interior) {
-#ifdef SO_AHEAD_LDS
-                int hmin, wmin, dmin;
-                const bool boxed = lds != nullptr && so_stage_box(cur.h0, cur.w0, cur.d0, H, W, D, hmin, wmin, dmin) &&
-                                   hmin + 3 < H && wmin + 3 < W && dmin + 3 < D;
-                if (boxed) {      // lane <-> corner (lane >> 4, (lane >> 2) & 3, lane & 3) of the block: ONE dword load per lane
-                    const unsigned vo = ((unsigned)((hmin * W + wmin) * D + dmin) + lane_vox) * 4u;
-                    lds[lane] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, 0u, 0));
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    const float *p0 = lds + (((cur.h0 - hmin) * 4 + (cur.w0 - wmin)) * 4 + (cur.d0 - dmin));
-                    v[0] = p0[0]; v[1] = p0[1]; v[2] = p0[4]; v[3] = p0[5]; v[4] = p0[16]; v[5] = p0[17]; v[6] = p0[20]; v[7] = p0[21];
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                } else
-#endif
-                {
-                const so_f4v lo = so_bload4(rb, cur.cell * 32u, 0u), hi = so_bload4(rb, cur.cell * 32u + 16u, 0u);
-                v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
-                }
-            } else {
-                so_gather_sdf_buf(rs, H, W, D, cur.h0, cur.w0, cur.d0, v);
-            }
+            float fh = __builtin_amdgcn_fractf(cur.gh), fw = __builtin_amdgcn_fractf(cur.gw), fd = __builtin_amdgcn_fractf(cur.gd);
+            so_f32x2 p0, p1, p2, p3;
+            auto gather = [&](int h0, int w0, int d0) __attribute__((always_inline)) {
+                float v[8];
+                so_gather_sdf_buf(rs, H, W, D, h0, w0, d0, v);
+                p0 = so_f32x2{v[0], v[4]}; p1 = so_f32x2{v[1], v[5]}; p2 = so_f32x2{v[2], v[6]}; p3 = so_f32x2{v[3], v[7]};
+            };
+            bool loaded = false;                 // wave-uniform
             if constexpr (FACE_SAFE) {
+                // decided before the corners are loaded, so that no corner is live across the canonical recomputation
                 if (__any(near_face(fh, fw, fd))) {
+                    int h0 = cur.h0, w0 = cur.w0, d0 = cur.d0;
+                    bool moved = false;
                     if (near_face(fh, fw, fd)) {
                         const so_cell c = canon_cell(i);
-                        if (c.h0 != cur.h0 || c.w0 != cur.w0 || c.d0 != cur.d0) {   // the canonical order lands next door
-                            so_gather_sdf_buf(rs, H, W, D, c.h0, c.w0, c.d0, v);
+                        if (c.h0 != h0 || c.w0 != w0 || c.d0 != d0) {   // the canonical order lands next door
+                            h0 = c.h0; w0 = c.w0; d0 = c.d0;
                             fh = c.fh1; fw = c.fw1; fd = c.fd1;
+                            moved = true;
                         }
                     }
+                    // a moved lane reads its new cell from the volume, the wave's other lanes the same corner values
+                    // there as in their brick records
+                    if (__any(moved)) { gather(h0, w0, d0); loaded = true; }
                 }
             }
-            const float dd0 = v[1] - v[0], dd1 = v[3] - v[2], dd2 = v[5] - v[4], dd3 = v[7] - v[6];
-            const float c0 = fmaf(fd, dd0, v[0]), c1 = fmaf(fd, dd1, v[2]);
-            const float c2 = fmaf(fd, dd2, v[4]), c3 = fmaf(fd, dd3, v[6]);
-            const float dw0 = c1 - c0, dw1 = c3 - c2;
-            const float b0 = fmaf(fw, dw0, c0), b1 = fmaf(fw, dw1, c2);
-            const float dh0 = b1 - b0;
-            const float sdf = fmaf(fh, dh0, b0);
-            const float gvw = fmaf(fh, dw1 - dw0, dw0);
-            const float e0 = fmaf(fw, dd1 - dd0, dd0), e1 = fmaf(fw, dd3 - dd2, dd2);
-            const float gvd = fmaf(fh, e1 - e0, e0);
+            if (!loaded) {
+                if (cur.all_interior) {
+#ifdef SO_AHEAD_LDS
+                    int hmin, wmin, dmin;
+                    const bool boxed = lds != nullptr && so_stage_box(cur.h0, cur.w0, cur.d0, H, W, D, hmin, wmin, dmin) &&
+                                       hmin + 3 < H && wmin + 3 < W && dmin + 3 < D;
+                    if (boxed) {      // lane <-> corner (lane >> 4, (lane >> 2) & 3, lane & 3) of the block: ONE dword load per lane
+                        const unsigned vo = ((unsigned)((hmin * W + wmin) * D + dmin) + lane_vox) * 4u;
+                        lds[lane] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, 0u, 0));
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        const float *q = lds + (((cur.h0 - hmin) * 4 + (cur.w0 - wmin)) * 4 + (cur.d0 - dmin));
+                        p0 = so_f32x2{q[0], q[16]}; p1 = so_f32x2{q[1], q[17]}; p2 = so_f32x2{q[4], q[20]}; p3 = so_f32x2{q[5], q[21]};
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                    } else
+#endif
+                    {   // one 32-B record = the four corner pairs, in the register order so_trilerp_fast_pk takes them
+                        // (issuing these loads before locate() above, to run it under them, measured 9 % SLOWER)
+                        const so_f4v lo = so_bload4(rb, cur.cell * 32u, 0u), hi = so_bload4(rb, cur.cell * 32u + 16u, 0u);
+                        p0 = lo.xy; p1 = lo.zw; p2 = hi.xy; p3 = hi.zw;
+                    }
+                } else {
+                    gather(cur.h0, cur.w0, cur.d0);
+                }
+            }
+            float sdf, dh0, gvw, gvd;
+            so_trilerp_fast_pk(p0, p1, p2, p3, fh, fw, fd, sdf, dh0, gvw, gvd);
             const float cosv = fmaf(gvd, Gdd, fmaf(gvw, Gdw, dh0 * Gdh));
             const float alpha = so_alpha_fast(sdf * s2, fminf(cosv, 0.0f) * hdt_s2);
             w = alpha * T;
@@ -1030,8 +1094,8 @@ SO_DEVFN void so_march(const so_render_args &a, int ray, GeomFn geom, float *lds
 }
 
 
-// re-pack of the SDF volume for the fast path: brick[cell] = the 8 corners of cell (h, w, d),
-// d fastest, clamped at the upper faces (only interior cells are ever read); codes[cell] = the
+// re-pack of the SDF volume for the fast path: brick[cell] = the 8 corners of cell (h, w, d) as the four pairs
+// (v[k], v[k + 4]), k = 0..3 (k = 2 w + d, so_gather_sdf's numbering), clamped at the upper faces (only interior cells are ever read); codes[cell] = the
 // free-space skip code of the cell (see so_skip_unit), 0 when skipping is off
 __global__ __launch_bounds__(256) void sdf_brickify_kernel(const float *__restrict__ vol, float *__restrict__ brick,
                                                            int H, int W, int D, so_render_args a, int with_codes) {
@@ -1044,8 +1108,8 @@ __global__ __launch_bounds__(256) void sdf_brickify_kernel(const float *__restri
     const float v0 = r00[d], v1 = r00[d1], v2 = r01[d], v3 = r01[d1];
     const float v4 = r10[d], v5 = r10[d1], v6 = r11[d], v7 = r11[d1];
     float4 *o = (float4 *)(brick + (size_t)cell * 8);
-    o[0] = make_float4(v0, v1, v2, v3);
-    o[1] = make_float4(v4, v5, v6, v7);
+    o[0] = make_float4(v0, v4, v1, v5);   // the (h = 0, h = 1) corner pairs of so_trilerp_fast_pk, d then w fastest
+    o[1] = make_float4(v2, v6, v3, v7);
     uint8_t *codes = (uint8_t *)(brick + (size_t)H * W * D * 8);
     unsigned code = 0u;
     if (with_codes) {
@@ -1090,8 +1154,7 @@ __global__ __launch_bounds__(256, (NF >= 8 ? SO_WAVES_FEAT : 1)) void render_fwd
 
 // pixel-grid rays: block = 16x16 pixel tile of one camera, each wave an 8x8 sub-tile
 template <int NF, bool BF16, bool PER_SAMPLE, int MODE>
-__global__ __launch_bounds__(256, (NF >= 8 ? SO_WAVES_FEAT : 1)) void render_fwd_pixgrid(so_render_args a, int tiles_x,
-                                                           int tiles_y) {
+SO_DEVFN void pixgrid_body(const so_render_args &a, int tiles_x, int tiles_y) {
     int b = blockIdx.x;
     int cam = b / (tiles_x * tiles_y);
     int tb = b - cam * tiles_x * tiles_y;
@@ -1130,6 +1193,25 @@ __global__ __launch_bounds__(256, (NF >= 8 ? SO_WAVES_FEAT : 1)) void render_fwd
         auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_pixel_ray(a, cam, ix, iy); };
         so_march<NF, BF16, PER_SAMPLE, MODE>(a, ray, geom);
     }
+}
+
+template <int NF, bool BF16, bool PER_SAMPLE, int MODE>
+__global__ __launch_bounds__(256, (NF >= 8 ? SO_WAVES_FEAT : 1)) void render_fwd_pixgrid(so_render_args a, int tiles_x,
+                                                                                         int tiles_y) {
+    pixgrid_body<NF, BF16, PER_SAMPLE, MODE>(a, tiles_x, tiles_y);
+}
+// The skip marchers (bench.py's kernel) at 8 waves / SIMD need <= 64 VGPRs AND <= 80 SGPRs: a CU admits
+// floor(800 / (ceil(sgpr / 16) * 16 + 16)) blocks of 256 threads, 7 at 82 - 96 SGPRs although the compiler's occupancy says 8.
+// Left alone the allocator spends 84 (constants the rare canonical branch needs, hoisted); capped it fits in 80 without spilling.
+template <>
+__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<0, false, false, 3>(
+    so_render_args a, int tiles_x, int tiles_y) {
+    pixgrid_body<0, false, false, 3>(a, tiles_x, tiles_y);
+}
+template <>
+__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<0, false, false, 4>(
+    so_render_args a, int tiles_x, int tiles_y) {
+    pixgrid_body<0, false, false, 4>(a, tiles_x, tiles_y);
 }
 
 template <int NF, bool BF16, bool PER_SAMPLE, int MODE>

@@ -93,16 +93,24 @@ struct so_cell {
     float sh, sw, sd;        // d grid / d metre along each axis
 };
 
-SO_DEVFN so_cell so_locate(const so_mapping &M, float x, float y, float z) {
+// cell and weights of grid coordinates (gh, gw, gd); slopes left unset
+SO_DEVFN so_cell so_cell_of(float gh, float gw, float gd) {
     so_cell c;
-    float gh = so_grid_coord(so_axis_m2g(M.h, y, c.sh), M.h.tot_len);
-    float gw = so_grid_coord(so_axis_m2g(M.w, x, c.sw), M.w.tot_len);
-    float gd = so_grid_coord(so_axis_m2g(M.d, z, c.sd), M.d.tot_len);
     float fh = floorf(gh), fw = floorf(gw), fd = floorf(gd);
     c.h0 = (int)fh; c.w0 = (int)fw; c.d0 = (int)fd;
     c.fh1 = gh - fh; c.fh0 = (fh + 1.0f) - gh;
     c.fw1 = gw - fw; c.fw0 = (fw + 1.0f) - gw;
     c.fd1 = gd - fd; c.fd0 = (fd + 1.0f) - gd;
+    return c;
+}
+
+SO_DEVFN so_cell so_locate(const so_mapping &M, float x, float y, float z) {
+    float sh, sw, sd;
+    float gh = so_grid_coord(so_axis_m2g(M.h, y, sh), M.h.tot_len);
+    float gw = so_grid_coord(so_axis_m2g(M.w, x, sw), M.w.tot_len);
+    float gd = so_grid_coord(so_axis_m2g(M.d, z, sd), M.d.tot_len);
+    so_cell c = so_cell_of(gh, gw, gd);
+    c.sh = sh; c.sw = sw; c.sd = sd;
     return c;
 }
 
