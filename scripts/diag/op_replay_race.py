@@ -67,7 +67,7 @@ def rec(name, fn):
 KEEP_REF = set()
 for mod in (bricks, attention, tpvformer):
     for name in ("linear_fwd", "linear_fwd_heads", "msda_fused_inference", "msda_cross_inference", "fused_linear",
-                 "value_proj_head_major", "value_proj_head_major_multi", "point_sampling"):
+                 "value_proj_head_major", "point_sampling"):
         if hasattr(mod, name):
             setattr(mod, name, rec(f"{mod.__name__.split('.')[-1]}.{name}", getattr(mod, name)))
 

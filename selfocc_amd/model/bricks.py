@@ -131,26 +131,34 @@ HEAD_MAJOR_PROJ = os.environ.get('SELFOCC_HEAD_MAJOR_PROJ', '1') == '1'
 HEAD_MAJOR_PROJ_TRAIN = os.environ.get('SELFOCC_HEAD_MAJOR_PROJ_TRAIN', '1') == '1'
 
 
-def value_proj_head_major(lin_weight, lin_bias, value2d, nv, num_heads):
-    """(G, B, 6, nv, 16) head-major projection of (B * nv, K) rows through the stacked weight (G * 96, K), or None when
-    the shape / mode does not qualify (the caller then projects pixel-major as the reference does).  Under autograd
-    the result carries the projection's backward (_TallLinearHeads)."""
-    if not (HEAD_MAJOR_PROJ and FUSED_LINEAR_FWD and not torch.is_autocast_enabled()
-            and value2d.is_cuda and value2d.dtype == torch.float32 and lin_weight.dtype == torch.float32 and num_heads == 6):
+def value_proj_head_major(lins, value2d, nv, num_heads):
+    """The head-major (B, 6, nv, 16) projections of (B * nv, K) rows through the G nn.Linear(K, 96) ``lins``, ONE
+    selfocc_linear_fwd_heads launch with their weights stacked, or None when the shape / mode does not qualify (the caller
+    then projects pixel-major as the reference does).  Under autograd: the tuple of the G outputs of one _TallLinearHeads
+    node, each tagged ``_so_grad_sink = (ValueGradSink, g)`` for the g-th attention's MSDA Function; else the
+    (G, B, 6, nv, 16) tensor.  Either way ``[g]`` is group g's value — under autograd the Function's own output, not a
+    select (select's backward is a zero fill + a copy)."""
+    K = value2d.shape[1]
+    if not (HEAD_MAJOR_PROJ and FUSED_LINEAR_FWD and not torch.is_autocast_enabled() and value2d.is_cuda
+            and value2d.dtype == torch.float32 and num_heads == 6):
         return None
-    rows, n_out = value2d.shape[0], lin_weight.shape[0]
-    if rows < LINEAR_FWD_MIN_ROWS or not linear_fwd_heads_supported(rows, n_out, value2d.shape[1], nv):
+    if any(tuple(l.weight.shape) != (96, K) or l.weight.dtype != torch.float32 or (l.bias is None and len(lins) > 1)
+           for l in lins):
         return None
-    if torch.is_grad_enabled() and (value2d.requires_grad or lin_weight.requires_grad):
+    rows = value2d.shape[0]
+    if rows < LINEAR_FWD_MIN_ROWS or not linear_fwd_heads_supported(rows, 96 * len(lins), K, nv):
+        return None
+    wb = [t for l in lins for t in (l.weight, l.bias)]
+    if torch.is_grad_enabled() and (value2d.requires_grad or any(l.weight.requires_grad for l in lins)):
         if not HEAD_MAJOR_PROJ_TRAIN:
             return None
-        G = n_out // 96
-        sink = ValueGradSink(G) if VALUE_GRAD_SINK else None
-        out = _TallLinearHeads.apply(value2d, lin_weight, lin_bias, nv, sink)
+        sink = ValueGradSink(len(lins)) if VALUE_GRAD_SINK else None
+        outs = _TallLinearHeads.apply(value2d, nv, sink, *wb)
         if sink is not None:
-            out._so_grad_sink = sink           # read by the caller, which hands (sink, g) to the g-th attention's MSDA Function
-        return out
-    return linear_fwd_heads(value2d, lin_weight, lin_bias, nv)
+            for g, o in enumerate(outs):
+                o._so_grad_sink = (sink, g)
+        return outs
+    return linear_fwd_heads(value2d, stack_rows(wb[0::2]), stack_rows(wb[1::2]), nv)
 
 
 # training: the MSDA backward writes grad_value pixel-major straight into the row-major gradient of the (stacked) value
@@ -159,38 +167,22 @@ VALUE_GRAD_SINK = os.environ.get('SELFOCC_VALUE_GRAD_SINK', '1') == '1'
 
 
 # training: the three TPV planes' value projections of the same image features as ONE projection / ONE backward
-# (_TallLinearHeadsMulti): the 59 MB input is read once per layer instead of three times in each direction, one input
+# (_TallLinearHeads with G = 3): the 59 MB input is read once per layer instead of three times in each direction, one input
 # gradient instead of three + two accumulations (env SELFOCC_MERGED_VALUE_PROJ_TRAIN=0: per plane, as round 2)
 MERGED_VALUE_PROJ_TRAIN = os.environ.get('SELFOCC_MERGED_VALUE_PROJ_TRAIN', '1') == '1'
-
-
-def value_proj_head_major_multi(lins, value2d, nv, num_heads):
-    """[(B, 6, nv, 16)] * G: the head-major projections of (B * nv, K) rows through G nn.Linear(K, 96) in one launch
-    under autograd, or None when the shape / mode does not qualify (the caller then projects per plane)."""
-    if not (HEAD_MAJOR_PROJ and HEAD_MAJOR_PROJ_TRAIN and MERGED_VALUE_PROJ_TRAIN and FUSED_LINEAR_FWD
-            and not torch.is_autocast_enabled() and torch.is_grad_enabled() and value2d.is_cuda
-            and value2d.dtype == torch.float32 and num_heads == 6):
-        return None
-    K = value2d.shape[1]
-    if any(l.bias is None or tuple(l.weight.shape) != (96, K) or l.weight.dtype != torch.float32 for l in lins):
-        return None
-    rows = value2d.shape[0]
-    if rows < LINEAR_FWD_MIN_ROWS or not linear_fwd_heads_supported(rows, 96 * len(lins), K, nv):
-        return None
-    if not (value2d.requires_grad or any(l.weight.requires_grad for l in lins)):
-        return None
-    wb = [t for l in lins for t in (l.weight, l.bias)]
-    sink = ValueGradSink(len(lins)) if VALUE_GRAD_SINK else None
-    outs = list(_TallLinearHeadsMulti.apply(value2d, nv, sink, *wb))
-    if sink is not None:
-        for g, o in enumerate(outs):
-            o._so_grad_sink = (sink, g)        # read by BEVCrossAttention._forward_camera_loop
-    return outs
 
 
 def _linear_fwd_ok(x2d, weight):
     return (x2d.is_cuda and x2d.dtype == torch.float32 and weight.dtype == torch.float32
             and x2d.shape[0] >= LINEAR_FWD_MIN_ROWS and linear_fwd_supported(x2d.shape[0], weight.shape[0], x2d.shape[1]))
+
+
+def _tall_fwd(x, w, b, relu=False):
+    """relu?(x W^T + b) for (T, K) rows: one selfocc_linear_fwd launch when the shape qualifies, else torch.addmm"""
+    if FUSED_LINEAR_FWD and _linear_fwd_ok(x, w):
+        return linear_fwd(x, w, b, relu=relu)
+    y = torch.addmm(b, x, w.t()) if b is not None else x @ w.t()
+    return torch.relu(y) if relu else y
 
 
 def fused_linear(lin, x, relu=False, residual=None, norm=None, out=None):
@@ -233,29 +225,6 @@ def fused_linear(lin, x, relu=False, residual=None, norm=None, out=None):
     return y
 
 
-class _TallLinear(torch.autograd.Function):
-    """y = x W^T + b for x with millions of rows and a handful of output features.  The vendor
-    GEMM picked for the weight gradient dW = dy^T x of such a shape (25 x 1.65 M x 96 at the shipped
-    nuscenes_occ sizes) runs on 2 workgroups — 23 ms per call, 4 calls per iteration in the
-    round-1 profile; here the reduction over rows is split into 256 batched GEMMs + a sum."""
-
-    # under torch.autocast (the reference's env amp=true) the op runs in float32 like the HIP ops around it
-    @staticmethod
-    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
-    def forward(ctx, x, weight, bias):
-        ctx.save_for_backward(x, weight)
-        ctx.has_bias = bias is not None
-        if FUSED_LINEAR_FWD and _linear_fwd_ok(x, weight):
-            return linear_fwd(x, weight, bias)
-        return torch.addmm(bias, x, weight.t()) if bias is not None else x @ weight.t()
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type='cuda')
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        return _tall_linear_backward(x, weight, dy, ctx.has_bias, ctx.needs_input_grad[0])
-
-
 def _dgrad(dy, weight):
     if (FUSED_DGRAD and dy.is_cuda and dy.dtype == torch.float32 and dy.shape[0] >= DGRAD_MIN_ROWS
             and dgrad_supported(dy.shape[0], weight.shape[0], weight.shape[1])):
@@ -294,76 +263,110 @@ def _tall_linear_backward(x, weight, dy, has_bias, need_dx=True):
         return (_dgrad(dy, weight) if need_dx else None), dw, (db if has_bias else None)
 
 
-class _TallLinearReLU(torch.autograd.Function):
-    """relu(x W^T + b) as one node (the FFN's first layer): the forward is one selfocc_linear_fwd launch with the ReLU in
-    its epilogue; the backward masks dy with the saved output and continues as _TallLinear.  (nn.ReLU(inplace=True) on
-    the view _TallLinear returns costs autograd a CopySlices: four extra 60 MB copies and a fill per layer.)"""
+def stacked_view(params):
+    """ONE contiguous tensor that IS the row-concatenation of the leaf parameters ``params`` — their storages are made to
+    alias consecutive row blocks of it — so that a stacked projection costs no ``torch.cat`` per call (the round-6 training
+    iteration launched ~40 five-microsecond cats for the merged sampling_offsets | attention_weights and value projections).
+    The parameters stay separate ``nn.Parameter`` objects with their own names, gradients, version counters and optimiser
+    state; in-place updates (optimisers, ``load_state_dict``) keep the aliasing, a ``module.to(...)`` / ``.data =``
+    assignment breaks it and the next call re-establishes it.  Each parameter belongs to ONE stack, always in the same order:
+    two different groupings would re-alias (one cat each) on every call.  None when a tensor is not a leaf parameter
+    (``functional_call`` views under row sharding, autocast casts, ...) or is an inference tensor: the caller then cats."""
+    p0 = params[0]
+    if any((not isinstance(p, nn.Parameter)) or (not p.is_leaf) or p.is_inference() or p.dtype != p0.dtype
+           or p.device != p0.device or p.shape[1:] != p0.shape[1:] for p in params):
+        return None
+    rows = sum(p.shape[0] for p in params)
+    st, off, aliased = p0.untyped_storage(), p0.storage_offset(), True
+    for p in params:
+        if p.untyped_storage().data_ptr() != st.data_ptr() or p.storage_offset() != off or not p.is_contiguous():
+            aliased = False
+            break
+        off += p.numel()
+    if aliased:
+        return torch.as_strided(p0.data, (rows, *p0.shape[1:]), p0.data.stride(), p0.storage_offset())
+    # never an inference tensor, even when the first call comes under torch.inference_mode(): the parameters re-pointed at
+    # it would be inference tensors too, and unusable for training from then on
+    with torch.inference_mode(False), torch.no_grad():
+        buf = torch.cat([p.data for p in params], 0)
+        o = 0
+        for p in params:
+            p.data = buf[o:o + p.shape[0]]
+            o += p.shape[0]
+    return buf
 
+
+def stack_rows(ts):
+    """The row-concatenation of ``ts``: the tensor itself (or None) for one, else the parameters' shared buffer
+    (stacked_view) or a torch.cat."""
+    if len(ts) == 1:
+        return ts[0]
+    st = stacked_view(ts)
+    return st if st is not None else torch.cat(ts, 0)
+
+
+def _split_rows(dw, db, sizes):
+    """(dW_1, db_1, dW_2, db_2, ...): the per-Linear row blocks of a stacked projection's weight / bias gradients"""
+    if len(sizes) == 1:
+        return dw, db
+    return [t for g in zip(dw.split(sizes), db.split(sizes)) for t in g]
+
+
+class _TallLinear(torch.autograd.Function):
+    """y = relu?(x [W_1; ...; W_G]^T + [b_1; ...; b_G]): G >= 1 Linears of the SAME rows (T, K) as ONE projection with
+    their weights stacked, output row-major (T, N_1 + ... + N_G); the bias is optional when G = 1.
+
+    For x with millions of rows and a handful of output features: the vendor GEMM picked for the weight gradient
+    dW = dy^T x of such a shape (25 x 1.65 M x 96 at the shipped nuscenes_occ sizes) runs on 2 workgroups — 23 ms per
+    call, 4 calls per iteration in the round-1 profile; _tall_linear_backward splits the reduction over rows instead.
+    G = 2 is the `sampling_offsets` | `attention_weights` pair of every deformable attention (image_cross_attention.py:296-312
+    and cross_view_hybrid_attention.py:78-90 read the same `query` twice): one read of x and one launch forward, and —
+    because the MSDA backward writes the gradient of the merged row (ABI 32 ``ol_stride``) — ONE input-gradient pass, ONE
+    weight-gradient pass and no gradient add in backward.  ``relu`` is the FFN's first layer: the ReLU runs in the
+    projection's epilogue and backward masks dy with the saved output (nn.ReLU(inplace=True) on the view returned here
+    costs autograd a CopySlices: four extra 60 MB copies and a fill per layer)."""
+
+    # under torch.autocast (the reference's env amp=true) the op runs in float32 like the HIP ops around it
     @staticmethod
     @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
-    def forward(ctx, x, weight, bias):
-        if FUSED_LINEAR_FWD and _linear_fwd_ok(x, weight):
-            y = linear_fwd(x, weight, bias, relu=True)
-        else:
-            y = torch.relu(torch.addmm(bias, x, weight.t()) if bias is not None else x @ weight.t())
-        ctx.save_for_backward(x, weight, y)
-        ctx.has_bias = bias is not None
+    def forward(ctx, x, relu, *wb):
+        w, b = stack_rows(wb[0::2]), stack_rows(wb[1::2])
+        y = _tall_fwd(x, w, b, relu)
+        # the parameters themselves, not the stacked view: autograd's version check catches in-place updates before backward
+        ctx.save_for_backward(x, y if relu else None, *wb[0::2])
+        ctx.has_bias = b is not None
         return y
 
     @staticmethod
     @torch.amp.custom_bwd(device_type='cuda')
     def backward(ctx, dy):
-        x, weight, y = ctx.saved_tensors
-        dy = torch.ops.aten.threshold_backward(dy.contiguous().to(y.dtype), y, 0)
-        return _tall_linear_backward(x, weight, dy, ctx.has_bias, ctx.needs_input_grad[0])
+        x, y, *ws = ctx.saved_tensors
+        if y is not None:
+            dy = torch.ops.aten.threshold_backward(dy.contiguous().to(y.dtype), y, 0)
+        dx, dw, db = _tall_linear_backward(x, stack_rows(ws), dy, ctx.has_bias, ctx.needs_input_grad[0])
+        return (dx, None, *_split_rows(dw, db, [w.shape[0] for w in ws]))
 
 
 class _TallLinearHeads(torch.autograd.Function):
-    """value_proj with a HEAD-MAJOR result under autograd: forward = selfocc_linear_fwd_heads (the projection writes the
-    (G, B, 6, nv, 16) layout the MSDA kernels gather fastest from, forward and backward point kernels alike); backward
-    brings the head-major gradient back to rows with one transposing copy and continues as _TallLinear."""
-
-    @staticmethod
-    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
-    def forward(ctx, x, weight, bias, nv, sink=None):
-        ctx.save_for_backward(x, weight)
-        ctx.has_bias = bias is not None
-        ctx.sink = sink
-        return linear_fwd_heads(x, weight, bias, nv)
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type='cuda')
-    def backward(ctx, dy_hm):
-        x, weight = ctx.saved_tensors
-        G, B, H, nv, d = dy_hm.shape
-        # the MSDA backward wrote its grad_value pixel-major into the sink (msda.ValueGradSink): dy_hm is a view of it
-        dy = ctx.sink.rows([dy_hm[g] for g in range(G)]) if ctx.sink is not None else None
-        if dy is None:
-            dy = dy_hm.permute(1, 3, 0, 2, 4).reshape(B * nv, G * H * d)    # (b, pix, g, h, c): one transposing copy
-        return (*_tall_linear_backward(x, weight, dy, ctx.has_bias, ctx.needs_input_grad[0]), None, None)
-
-
-class _TallLinearHeadsMulti(torch.autograd.Function):
-    """G value projections of the SAME rows (the TPV planes' value_proj of one layer): one selfocc_linear_fwd_heads launch
-    with the stacked (G * 96, K) weight, one head-major tensor per group; backward = one weight-gradient and one
-    input-gradient pass over the row-major (rows, G * 96) gradient assembled from the G head-major ones."""
+    """G >= 1 value projections nn.Linear(K, 96) of the SAME rows (one attention's value_proj, or the TPV planes' of one
+    layer) with HEAD-MAJOR results: forward = one selfocc_linear_fwd_heads launch with the stacked (G * 96, K) weight, one
+    (B, 6, nv, 16) tensor per group — the layout the MSDA kernels gather fastest from, forward and backward point kernels
+    alike; backward = one weight-gradient and one input-gradient pass over the row-major (rows, G * 96) gradient, which the
+    MSDA backward wrote in place (msda.ValueGradSink) or which is assembled with one transposing copy per group."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
     def forward(ctx, x, nv, sink, *wb):
-        w, b = stacked_view(list(wb[0::2])), stacked_view(list(wb[1::2]))
-        if w is None or b is None:
-            w, b = torch.cat(wb[0::2], 0), torch.cat(wb[1::2], 0)
-        ctx.save_for_backward(x, w)
-        ctx.G = len(wb) // 2
-        ctx.sink = sink
+        w, b = stack_rows(wb[0::2]), stack_rows(wb[1::2])
+        ctx.save_for_backward(x, *wb[0::2])
+        ctx.has_bias, ctx.sink = b is not None, sink
         return tuple(linear_fwd_heads(x, w, b, nv).unbind(0))
 
     @staticmethod
     @torch.amp.custom_bwd(device_type='cuda')
     def backward(ctx, *gys):
-        x, w = ctx.saved_tensors
-        G = ctx.G
+        x, *ws = ctx.saved_tensors
+        G = len(ws)
         B, H, nv, d = next(g for g in gys if g is not None).shape
         # the G attentions' MSDA backward wrote their grad_value pixel-major into ONE row-major buffer (msda.ValueGradSink):
         # the gys are views of it — no transposing copies
@@ -376,78 +379,8 @@ class _TallLinearHeadsMulti(torch.autograd.Function):
                 else:
                     dy[:, :, g].copy_(gy.permute(0, 2, 1, 3))      # one transposing copy per group
             dy2 = dy.view(B * nv, G * H * d)
-        dx, dw, db = _tall_linear_backward(x, w, dy2, True, ctx.needs_input_grad[0])
-        n = H * d
-        grads = [t for g in range(G) for t in (dw[g * n:(g + 1) * n], db[g * n:(g + 1) * n])]
-        return (dx, None, None, *grads)
-
-
-STACKED_VIEW = os.environ.get('SELFOCC_STACKED_VIEW', '1') == '1'      # A/B: 0 = torch.cat per call
-
-
-def stacked_view(params):
-    """ONE contiguous tensor that IS the row-concatenation of the leaf parameters ``params`` — their storages are made to
-    alias consecutive row blocks of it — so that a stacked projection costs no ``torch.cat`` per call (the round-6 training
-    iteration launched ~40 five-microsecond cats for the merged sampling_offsets | attention_weights and value projections).
-    The parameters stay separate ``nn.Parameter`` objects with their own names, gradients and optimiser state; in-place
-    updates (optimisers, ``load_state_dict``) keep the aliasing, a ``module.to(...)`` / ``.data =`` assignment breaks it and the
-    next call re-establishes it.  None when a tensor is not a leaf parameter (``functional_call`` views under row sharding, ...)."""
-    p0 = params[0]
-    if not STACKED_VIEW:
-        return None
-    if any((not isinstance(p, nn.Parameter)) or (not p.is_leaf) or p.dtype != p0.dtype or p.device != p0.device
-           or p.shape[1:] != p0.shape[1:] for p in params):
-        return None
-    rows = sum(p.shape[0] for p in params)
-    inner = 1
-    for n in p0.shape[1:]:
-        inner *= n
-    st, off, aliased = p0.untyped_storage(), p0.storage_offset(), True
-    for p in params:
-        if p.untyped_storage().data_ptr() != st.data_ptr() or p.storage_offset() != off or not p.is_contiguous():
-            aliased = False
-            break
-        off += p.numel()
-    if aliased:
-        return torch.as_strided(p0.data, (rows, *p0.shape[1:]), p0.data.stride(), p0.storage_offset())
-    with torch.no_grad():
-        buf = torch.cat([p.data for p in params], 0).contiguous()
-        o = 0
-        for p in params:
-            p.data = buf[o:o + p.shape[0]]
-            o += p.shape[0]
-    return buf
-
-
-class _TallLinearMerged(torch.autograd.Function):
-    """G Linears of the SAME rows as ONE projection with the weights stacked: y (T, N_1 + ... + N_G).  Used for the
-    `sampling_offsets` | `attention_weights` pair of every deformable attention (image_cross_attention.py:296-312 and
-    cross_view_hybrid_attention.py:78-90 read the same `query` twice): one read of x and one launch forward, and — because
-    the MSDA backward writes the gradient of the merged row (ABI 32 ``ol_stride``) — ONE input-gradient pass, ONE
-    weight-gradient pass and no gradient add in backward, instead of two each and an add."""
-
-    @staticmethod
-    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
-    def forward(ctx, x, *wb):
-        w, b = stacked_view(list(wb[0::2])), stacked_view(list(wb[1::2]))      # the parameters themselves, aliased: no copy
-        if w is None or b is None:
-            w, b = torch.cat(wb[0::2], 0), torch.cat(wb[1::2], 0)
-        ctx.save_for_backward(x, w)
-        ctx.sizes = [t.shape[0] for t in wb[0::2]]
-        if FUSED_LINEAR_FWD and _linear_fwd_ok(x, w):
-            return linear_fwd(x, w, b)
-        return torch.addmm(b, x, w.t())
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type='cuda')
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        dx, dw, db = _tall_linear_backward(x, w, dy, True, ctx.needs_input_grad[0])
-        grads, o = [], 0
-        for n in ctx.sizes:
-            grads += [dw[o:o + n], db[o:o + n]]
-            o += n
-        return (dx, *grads)
+        dx, dw, db = _tall_linear_backward(x, stack_rows(ws), dy2, ctx.has_bias, ctx.needs_input_grad[0])
+        return (dx, None, None, *_split_rows(dw, db, [w.shape[0] for w in ws]))
 
 
 # sampling_offsets | attention_weights as one projection (env SELFOCC_MERGED_OFF_LOGITS=0: two Linears, as until round 5)
@@ -459,21 +392,19 @@ def merged_off_logits(module, x2d):
     """(T, 3 * heads * L * P) rows [heads*L*P*2 raw offsets | heads*L*P logits] = the module's `sampling_offsets` and
     `attention_weights` Linears of the rows ``x2d`` (T, K) in ONE projection, or None when the module / input does not qualify
     (the caller then runs the two Linears).  Same parameters, same state-dict keys; under autograd the result carries one
-    backward for both (``_TallLinearMerged``)."""
+    backward for both (``_TallLinear`` with G = 2).  The kernels read the offsets as float2 and want an even row stride: an
+    odd heads * L * P does not qualify."""
     so, aw = module.sampling_offsets, module.attention_weights
     if not (MERGED_OFF_LOGITS and x2d.is_cuda and x2d.dtype == torch.float32 and not torch.is_autocast_enabled()
             and so.bias is not None and aw.bias is not None and so.weight.dtype == torch.float32
-            and so.weight.shape[0] == 2 * aw.weight.shape[0] and x2d.shape[0] >= LINEAR_FWD_MIN_ROWS):
+            and so.weight.shape[0] == 2 * aw.weight.shape[0] and aw.weight.shape[0] % 2 == 0
+            and x2d.shape[0] >= LINEAR_FWD_MIN_ROWS):
         return None
     MERGED_OFF_LOGITS_CALLS[0] += 1
+    wb = (so.weight, so.bias, aw.weight, aw.bias)      # the only stack these parameters are in (stacked_view)
     if torch.is_grad_enabled() and (x2d.requires_grad or so.weight.requires_grad or aw.weight.requires_grad):
-        return _TallLinearMerged.apply(x2d, so.weight, so.bias, aw.weight, aw.bias)
-    w, b = stacked_view([so.weight, aw.weight]), stacked_view([so.bias, aw.bias])
-    if w is None or b is None:
-        w, b = torch.cat([so.weight, aw.weight], 0).detach(), torch.cat([so.bias, aw.bias], 0).detach()
-    if FUSED_LINEAR_FWD and _linear_fwd_ok(x2d, w):
-        return linear_fwd(x2d, w, b)
-    return torch.addmm(b, x2d, w.t())
+        return _TallLinear.apply(x2d, False, *wb)
+    return _tall_fwd(x2d, stack_rows(wb[0::2]), stack_rows(wb[1::2]))
 
 
 class TallLinear(nn.Linear):
@@ -486,7 +417,7 @@ class TallLinear(nn.Linear):
     def forward(self, x):
         rows = x.numel() // max(x.shape[-1], 1)
         if torch.is_grad_enabled() and rows >= self.min_rows and (x.requires_grad or self.weight.requires_grad):
-            y = _TallLinear.apply(x.reshape(rows, x.shape[-1]), self.weight, self.bias)
+            y = _TallLinear.apply(x.reshape(rows, x.shape[-1]), False, self.weight, self.bias)
             return y.view(*x.shape[:-1], self.weight.shape[0])
         if not torch.is_grad_enabled() and FUSED_LINEAR_FWD and x.is_cuda and not torch.is_autocast_enabled():
             x2 = x.reshape(rows, x.shape[-1])
@@ -534,7 +465,7 @@ class FFN(BaseModule):
         if (FUSED_FFN_RELU and self.num_fcs == 2 and torch.is_grad_enabled() and x.is_cuda and isinstance(lin0, TallLinear)
                 and isinstance(self.layers[0][1], nn.ReLU) and rows >= lin0.min_rows
                 and (x.requires_grad or lin0.weight.requires_grad)):
-            h = _TallLinearReLU.apply(x.reshape(rows, x.shape[-1]), lin0.weight, lin0.bias)
+            h = _TallLinear.apply(x.reshape(rows, x.shape[-1]), True, lin0.weight, lin0.bias)
             h = self.layers[0][2](h.view(*x.shape[:-1], lin0.weight.shape[0]))
             out = self.layers[1](h)
             if FUSED_DROPOUT_ADD and self.add_identity and isinstance(self.dropout_layer, nn.Identity):
@@ -551,7 +482,7 @@ class FFN(BaseModule):
         return identity + self.dropout_layer(out)
 
 
-# training: the FFN's Linear + ReLU as one autograd node (_TallLinearReLU); env SELFOCC_FUSED_FFN_RELU=0: nn.Sequential
+# training: the FFN's Linear + ReLU as one autograd node (_TallLinear with relu); env SELFOCC_FUSED_FFN_RELU=0: nn.Sequential
 FUSED_FFN_RELU = os.environ.get('SELFOCC_FUSED_FFN_RELU', '1') == '1'
 # training: `identity + dropout(x)` at the end of every attention / FFN block as one HIP pass per direction with a
 # counter-based mask (selfocc_amd/dropout.py); env SELFOCC_FUSED_DROPOUT=0: torch's dropout + add
@@ -589,8 +520,8 @@ def deformable_sampling(module, query, value, reference_points, spatial_shapes, 
     if (key_padding_mask is None and LP0 <= 256 and not HEAD_MAJOR_VALUE and module.value_proj.weight.shape[0] == 96
             and (not torch.is_grad_enabled() or FUSED_TRAINING)):
         # the projection itself writes (bs, heads, nv, d)
-        v_hm = value_proj_head_major(module.value_proj.weight, module.value_proj.bias, value.reshape(bs * num_value, -1),
-                                     num_value, module.num_heads)
+        v_hm = value_proj_head_major([module.value_proj], value.reshape(bs * num_value, -1), num_value, module.num_heads)
+        v_hm = v_hm[0] if v_hm is not None else None
     if v_hm is None:
         value = module.value_proj(value)
         if key_padding_mask is not None:
@@ -624,7 +555,7 @@ def deformable_sampling(module, query, value, reference_points, spatial_shapes, 
             logits = module.attention_weights(query).view(bs, num_query, module.num_heads, LP)
         hm = HEAD_MAJOR_VALUE
         if v_hm is not None:
-            value, hm = v_hm.view(v_hm.shape[1:]), True      # G = 1: a view (select's backward is a zero fill + a copy)
+            value, hm = v_hm, True
         elif HEAD_MAJOR_VALUE:
             value = to_head_major(value)
         if use_bf16:
@@ -637,15 +568,14 @@ def deformable_sampling(module, query, value, reference_points, spatial_shapes, 
             logits = module.attention_weights(query).view(bs, num_query, module.num_heads, LP)
         hm = HEAD_MAJOR_VALUE
         if v_hm is not None:
-            value, hm = v_hm.view(v_hm.shape[1:]), True      # G = 1: a view (select's backward is a zero fill + a copy)
+            value, hm = v_hm, True
         elif HEAD_MAJOR_VALUE:
             value = to_head_major(value)
-        sink = getattr(v_hm, '_so_grad_sink', None) if v_hm is not None else None
         return MSDAFusedFunction.apply(value, spatial_shapes, level_start_index, reference_points, kind,
                                        ol if ol is not None else off, logits, host, hm, use_bf16, mlp,
-                                       (sink, 0) if sink is not None else None)
+                                       getattr(v_hm, '_so_grad_sink', None))
     if v_hm is not None:      # (the unfused fallback below wants the mmcv layout)
-        value = v_hm.view(v_hm.shape[1:]).permute(0, 2, 1, 3).contiguous()
+        value = v_hm.permute(0, 2, 1, 3).contiguous()
     aw = module.attention_weights(query).view(bs, num_query, module.num_heads,
                                               module.num_levels * module.num_points).softmax(-1)
     aw = aw.view(bs, num_query, module.num_heads, module.num_levels, module.num_points)

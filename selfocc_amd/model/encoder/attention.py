@@ -10,8 +10,6 @@ The sampling itself is the HIP kernel behind MultiScaleDeformableAttnFunction (m
 """
 import math
 
-import os
-
 import torch
 import torch.nn as nn
 
@@ -173,7 +171,7 @@ class BEVCrossAttention(BaseModule):
         num_cams, heads, L, P = self.num_cams, da.num_heads, da.num_levels, da.num_points
         _, l, _, _ = value.shape                                            # (cams, nv, bs, C)
         hm = bricks.HEAD_MAJOR_VALUE
-        sink = None    # (ValueGradSink, g): where the backward puts grad_value (set by bricks.value_proj_head_major[_multi])
+        sink = None    # (ValueGradSink, g): where the backward puts grad_value (set by bricks.value_proj_head_major)
         if value_pre is not None and value_pre.dim() == 4:
             v, hm = value_pre, True    # TPVCrossAttention already laid this plane's values out head-major
             sink = getattr(value_pre, '_so_grad_sink', None)
@@ -184,11 +182,10 @@ class BEVCrossAttention(BaseModule):
             v_hm = None
             if not hm and da.value_proj.weight.shape[0] == 96:
                 # the projection itself writes (cams, heads, l, d) (selfocc_linear_fwd_heads; under autograd _TallLinearHeads)
-                v_hm = bricks.value_proj_head_major(da.value_proj.weight, da.value_proj.bias, vin, l, heads)
+                v_hm = bricks.value_proj_head_major([da.value_proj], vin, l, heads)
             if v_hm is not None:
-                v, hm = v_hm.view(v_hm.shape[1:]), True      # G = 1: a view, not a select
-                s1 = getattr(v_hm, '_so_grad_sink', None)
-                sink = (s1, 0) if s1 is not None else None
+                v, hm = v_hm[0], True      # under autograd the Function's own output: no select
+                sink = getattr(v, '_so_grad_sink', None)
             else:
                 v = da.value_proj(vin.view(num_cams, l, self.embed_dims)).view(num_cams, l, heads, -1)
                 if hm:
@@ -225,21 +222,6 @@ class BEVCrossAttention(BaseModule):
         return post_norm(slots) if post_norm is not None else slots
 
 
-# dev A/B (round 6): SELFOCC_PLANE_STREAMS=1 runs the three planes' inference branches on three streams.  Measured and left OFF:
-# the eval encoder gets SLOWER (5.45 -> 5.69 ms at nuscenes_occ, 5.95 -> 6.19 at nuscenes_depth, same box, twice; results unchanged,
-# scripts/diag/plane_streams_ab.sh) — the gather kernels already keep the texture path 70 - 77 % busy on their own and lose more
-# to each other than the short launches gain by hiding under them.
-PLANE_STREAMS = os.environ.get('SELFOCC_PLANE_STREAMS', '0') == '1'
-_PLANE_STREAMS = {}
-
-
-def _plane_streams(device):
-    key = str(device)
-    if key not in _PLANE_STREAMS:
-        _PLANE_STREAMS[key] = [torch.cuda.Stream(device=device) for _ in range(3)]
-    return _PLANE_STREAMS[key]
-
-
 @MODELS.register_module()
 class TPVCrossAttention(BaseModule):
     """One BEVCrossAttention per TPV plane (hw, zh, wz) with num_points = [wz, zh, hw] pillar
@@ -266,6 +248,9 @@ class TPVCrossAttention(BaseModule):
                 tpv_masks=None, level_start_index=None, **kwargs):
         plans = kwargs.get('rebatch_plans') or [None] * 3
         outs, vpre = [None] * 3, [None] * 3
+        # the three planes' value_proj, stacked in this order by both branches below: the only stack these parameters are in
+        # (bricks.stacked_view)
+        vps = [a.deformable_attention.value_proj for a in self.attns]
         if not torch.is_grad_enabled() and not self.training and query[0].shape[0] == 1:
             # inference: the three planes' results land in consecutive slices of ONE buffer, so that the layer's next
             # norm / ffn step sees the concatenated tensor without a copy (tpvformer.cat_planes)
@@ -277,76 +262,39 @@ class TPVCrossAttention(BaseModule):
                 # (the 68 MB input is read once instead of three times); each plane's kernel reads its column block
                 # in place (selfocc_msda_cross_fwd value_stride)
                 C = self.embed_dims
-                w, b = self._merged_value_proj()
                 cams, l = value.shape[0], value.shape[1]
                 vin = value.permute(2, 0, 1, 3).reshape(cams * l, C)
                 heads0 = self.attns[0].deformable_attention.num_heads
-                v_hm = bricks.value_proj_head_major(w, b, vin, l, heads0) if C == 96 else None
+                bf16 = bricks.VALUE_BF16 and C // heads0 == 16
+                v_hm = bricks.value_proj_head_major(vps, vin, l, heads0) if C == 96 else None
                 if v_hm is not None:
                     # (3, cams, heads, l, d): each plane's head-major value, written by the projection kernel itself
-                    if bricks.VALUE_BF16 and C // heads0 == 16:
-                        v_hm = v_hm.to(torch.bfloat16)
-                    vpre = list(v_hm)
-
-                    def plane(i):
-                        return self.attns[i](query[i], key, value, residual[i] if residual is not None else None,
-                                             spatial_shapes=spatial_shapes, level_start_index=level_start_index,
-                                             reference_points_cams=reference_points_cams[i], bev_masks=tpv_masks[i],
-                                             rebatch_plan=plans[i], out=outs[i], value_pre=vpre[i],
-                                             post_norm=kwargs.get('post_norm'))
-                    if not PLANE_STREAMS:
-                        return [plane(i) for i in range(3)]
-                    # the three planes are independent until the layer's next step: each runs on its own stream (its
-                    # temporaries live and die in that stream's pool; inputs and the `outs` slices belong to the caller's
-                    # stream, which waits for all three before it goes on)
-                    main = torch.cuda.current_stream()
-                    side = _plane_streams(value.device)
-                    start = torch.cuda.Event()
-                    start.record(main)
-                    res = []
-                    for i in range(3):
-                        side[i].wait_event(start)
-                        with torch.cuda.stream(side[i]):
-                            res.append(plane(i))
-                    for st in side:
-                        main.wait_stream(st)
-                    return res
-                if bricks.FUSED_LINEAR_FWD and bricks._linear_fwd_ok(vin, w):
-                    v_all = bricks.linear_fwd(vin, w, b).view(cams, l, 3 * C)
+                    vpre = list(v_hm.to(torch.bfloat16) if bf16 else v_hm)
                 else:
-                    v_all = torch.addmm(b, vin, w.t()).view(cams, l, 3 * C)
-                if bricks.VALUE_BF16 and C // heads0 == 16:
-                    v_all = v_all.to(torch.bfloat16)       # one cast for the three planes
-                if bricks.HEAD_MAJOR_VALUE:
-                    # one transposing copy for the three planes: (plane, cams, heads, l, d), each plane dense
-                    heads = self.attns[0].deformable_attention.num_heads
-                    vpre = list(v_all.view(cams, l, 3, heads, C // heads).permute(2, 0, 3, 1, 4).contiguous())
-                else:
-                    vpre = [v_all[..., i * C:(i + 1) * C] for i in range(3)]
-        elif (torch.is_grad_enabled() and value.is_cuda and query[0].shape[0] == 1 and value.shape[2] == 1
-              and all(a.camera_loop for a in self.attns)):
+                    w, b = bricks.stack_rows([p.weight for p in vps]), bricks.stack_rows([p.bias for p in vps])
+                    v_all = bricks._tall_fwd(vin, w, b).view(cams, l, 3 * C)
+                    if bf16:
+                        v_all = v_all.to(torch.bfloat16)       # one cast for the three planes
+                    if bricks.HEAD_MAJOR_VALUE:
+                        # one transposing copy for the three planes: (plane, cams, heads, l, d), each plane dense
+                        vpre = list(v_all.view(cams, l, 3, heads0, C // heads0).permute(2, 0, 3, 1, 4).contiguous())
+                    else:
+                        vpre = [v_all[..., i * C:(i + 1) * C] for i in range(3)]
+        elif (torch.is_grad_enabled() and bricks.MERGED_VALUE_PROJ_TRAIN and value.is_cuda and query[0].shape[0] == 1
+              and value.shape[2] == 1 and all(a.camera_loop for a in self.attns)
+              and len({a.deformable_attention.num_heads for a in self.attns}) == 1):
             # training: the three planes' value projections of the same image features are one autograd node
-            # (bricks._TallLinearHeadsMulti): one projection, one weight / input gradient pass per layer
+            # (bricks._TallLinearHeads): one projection, one weight / input gradient pass per layer
             cams, l = value.shape[0], value.shape[1]
-            das = [a.deformable_attention for a in self.attns]
-            v3 = bricks.value_proj_head_major_multi([da.value_proj for da in das],
-                                                    value.permute(2, 0, 1, 3).reshape(cams * l, self.embed_dims), l,
-                                                    das[0].num_heads) if len({da.num_heads for da in das}) == 1 else None
+            v3 = bricks.value_proj_head_major(vps, value.permute(2, 0, 1, 3).reshape(cams * l, self.embed_dims), l,
+                                              self.attns[0].deformable_attention.num_heads)
             if v3 is not None:
-                vpre = v3          # (cams, heads, l, d) each: `_forward_camera_loop` takes a 4-d value_pre as head-major
+                vpre = list(v3)    # (cams, heads, l, d) each: `_forward_camera_loop` takes a 4-d value_pre as head-major
         return [self.attns[i](query[i], key, value, residual[i] if residual is not None else None,
                               spatial_shapes=spatial_shapes, level_start_index=level_start_index,
                               reference_points_cams=reference_points_cams[i], bev_masks=tpv_masks[i],
                               rebatch_plan=plans[i], out=outs[i], value_pre=vpre[i], post_norm=kwargs.get('post_norm'))
                 for i in range(3)]
-
-    def _merged_value_proj(self):
-        """(3 C, C) weight and (3 C) bias of the three planes' value_proj stacked; cached until a parameter changes."""
-        ps = [a.deformable_attention.value_proj for a in self.attns]
-        key = tuple((p.weight._version, p.weight.data_ptr(), p.bias._version, p.bias.data_ptr()) for p in ps)
-        if getattr(self, '_vp_cache', (None,))[0] != key:
-            self._vp_cache = (key, torch.cat([p.weight for p in ps], 0).detach(), torch.cat([p.bias for p in ps], 0).detach())
-        return self._vp_cache[1], self._vp_cache[2]
 
 
 @MODELS.register_module()

@@ -203,7 +203,7 @@ class SDFField(BaseModule):
     def _mlp(self, x):
         """density_net applied to (rows, C); Linear layers through _TallLinear (same parameters)."""
         for m in self.density_net:
-            x = _TallLinear.apply(x, m.weight, m.bias) if isinstance(m, nn.Linear) else m(x)
+            x = _TallLinear.apply(x, False, m.weight, m.bias) if isinstance(m, nn.Linear) else m(x)
         return x
 
     def pre_compute_density_color(self, representation):

@@ -237,7 +237,7 @@ class ValueGradSink:
     row-major buffer (B, nv, G, heads, d) — the dy of that projection's weight- / input-gradient passes — written PIXEL-major by
     the band kernels themselves (ABI 32 ``g_value_stride``).  Until round 6 every attention returned a head-major grad_value
     and the projection's backward re-assembled the rows with one transposing copy per attention (12 x 59 MB copies per
-    nuscenes_occ iteration).  Created by bricks.value_proj_head_major[_multi], handed to the attention's MSDA Function as
+    nuscenes_occ iteration).  Created by bricks.value_proj_head_major, handed to the attention's MSDA Function as
     ``grad_sink=(sink, g)``; the Function returns a (B, heads, nv, d) VIEW of the buffer as the gradient of its head-major
     input, and the projection's backward recognises the views (``rows()``) and uses the buffer as it is."""
 

@@ -2,8 +2,8 @@
 
   * selfocc_flatten_feats == 2 broadcast adds per level + cat + permute (tpvformer_encoder.py:261-277), bit for bit;
     _FlattenFeats' hand-written backward == autograd through those ops;
-  * _TallLinearHeadsMulti (one merged value projection per layer) == three nn.Linear + head-major transposes;
-  * _TallLinearReLU == nn.Linear -> nn.ReLU(inplace=True) (mmcv FFN's first layer).
+  * _TallLinearHeads (one merged value projection per layer) == three nn.Linear + head-major transposes;
+  * _TallLinear with the ReLU epilogue == nn.Linear -> nn.ReLU(inplace=True) (mmcv FFN's first layer).
 """
 import pytest
 import torch
@@ -56,13 +56,13 @@ def test_flatten_feats_backward_vs_autograd(hip):
     assert torch.all(ga[1][3] == 0)
 
 
-def test_merged_value_projection_vs_three_linears(hip):
+def test_value_proj_head_major_three_groups_vs_three_linears(hip):
     from selfocc_amd.model import bricks
     torch.manual_seed(0)
     cams, nv, K = 6, 2600, 96
     lins = [nn.Linear(K, 96).to(D0) for _ in range(3)]
     x = torch.randn(cams * nv, K, device=D0, requires_grad=True)
-    vs = bricks.value_proj_head_major_multi(lins, x, nv, 6)
+    vs = bricks.value_proj_head_major(lins, x, nv, 6)
     assert vs is not None and len(vs) == 3 and vs[0].shape == (cams, 6, nv, 16)
     gs = [torch.randn_like(v) for v in vs]
     gs[1] = None                                                   # a plane whose result nobody used
@@ -78,6 +78,23 @@ def test_merged_value_projection_vs_three_linears(hip):
     want = [x.grad] + [p.grad if p.grad is not None else torch.zeros_like(p) for l in lins for p in (l.weight, l.bias)]
     for a, b in zip(got, want):
         assert torch.allclose(a, b, rtol=1e-4, atol=1e-4 * max(b.abs().max().item(), 1e-3))
+
+
+def test_merged_value_projection_refuses_in_place_change_before_backward(hip):
+    """_TallLinearHeads saves the parameters themselves, not their stacked view: an in-place change of one of them between
+    forward and backward raises as it does for nn.Linear, instead of a backward with the new weights"""
+    from selfocc_amd.model import bricks
+    torch.manual_seed(0)
+    cams, nv, K = 2, 1300, 96
+    lins = [nn.Linear(K, 96).to(D0) for _ in range(3)]
+    x = torch.randn(cams * nv, K, device=D0, requires_grad=True)
+    vs = bricks.value_proj_head_major(lins, x, nv, 6)
+    assert vs is not None and len(vs) == 3
+    assert lins[1].weight.data_ptr() == lins[0].weight.data_ptr() + 96 * K * 4        # aliased into one stacked buffer
+    with torch.no_grad():
+        lins[1].weight.mul_(0.5)
+    with pytest.raises(RuntimeError, match="modified by an inplace operation"):
+        torch.autograd.backward(list(vs), [torch.ones_like(v) for v in vs])
 
 
 def test_ffn_fused_relu_vs_sequential(hip, monkeypatch):

@@ -561,6 +561,66 @@ def test_merged_offset_logit_projection_module_equals_two_linears(hip, monkeypat
     assert not bad, (bad, errs)
 
 
+@pytest.mark.parametrize("route", ["fused", "camera_loop"])
+def test_odd_offset_logit_row_stride_trains_through_the_two_linears(hip, monkeypatch, route):
+    """heads * L * P odd (3 * 1 * 3, d = 32): the merged [offsets | logits] row would have an odd stride, which the kernels
+    refuse (they read the offsets as float2), so merged_off_logits leaves such a module to its two Linears.  Training
+    through the fused and the camera-loop ops runs and equals the two-Linear route (SELFOCC_MERGED_OFF_LOGITS off)."""
+    from selfocc_amd.model import bricks
+    from selfocc_amd.model.encoder import attention as A
+    from selfocc_amd.registry import MODELS
+    import selfocc_amd.model  # noqa: F401
+    d0 = torch.device("cuda:0")
+    torch.manual_seed(3)
+    heads, L, P, C = 3, 1, 3, 96
+    shapes = torch.tensor([[40, 50]], device=d0)
+    shapes._so_host = [40, 50]
+    starts = torch.tensor([0], device=d0)
+    if route == "fused":
+        att = MODELS.build(dict(type='CrossViewHybridAttention', embed_dims=C, num_heads=heads, num_levels=L, num_points=P,
+                                dropout=0.0, batch_first=True)).to(d0)
+        nq = 40 * 50
+        ref = torch.rand(1, nq, L, P, 2, device=d0)
+        fn, mod = 'MSDAFusedFunction', bricks
+        run = lambda q: att(q, reference_points=ref, spatial_shapes=shapes, level_start_index=starts)
+    else:
+        cams, nq = 2, 1500
+        att = MODELS.build(dict(type='BEVCrossAttention', embed_dims=C, num_cams=cams, dropout=0.0, batch_first=True,
+                                deformable_attention=dict(type='BEVDeformableAttention', embed_dims=C, num_heads=heads,
+                                                          num_levels=L, num_points=P, dropout=0.0, batch_first=True))).to(d0)
+        value = torch.randn(cams, 40 * 50, 1, C, device=d0)
+        ref = torch.rand(cams, 1, nq, P, 2, device=d0)
+        masks = torch.rand(cams, 1, nq, P, device=d0) > 0.3
+        fn, mod = 'MSDACrossFunction', A
+        run = lambda q: att(q, value, value, spatial_shapes=shapes, reference_points_cams=ref, bev_masks=masks,
+                            level_start_index=starts)
+    with torch.no_grad():
+        for n, p in att.named_parameters():
+            if 'sampling_offsets.weight' in n or 'attention_weights.weight' in n:
+                p.normal_(std=0.05)
+    calls, real = [], getattr(mod, fn)
+    monkeypatch.setattr(mod, fn, type(fn, (), {'apply': staticmethod(lambda *a: (calls.append(1), real.apply(*a))[1])}))
+    monkeypatch.setattr(bricks, 'LINEAR_FWD_MIN_ROWS', 64)
+    q = torch.randn(1, nq, C, device=d0)
+    gy = torch.randn(1, nq, C, device=d0)
+    res = {}
+    for merged in (True, False):
+        monkeypatch.setattr(bricks, 'MERGED_OFF_LOGITS', merged)
+        att.zero_grad(set_to_none=True)
+        qq = q.clone().requires_grad_(True)
+        att.train()
+        n0, m0 = len(calls), bricks.MERGED_OFF_LOGITS_CALLS[0]
+        y = run(qq)
+        y.backward(gy)
+        assert len(calls) > n0 and bricks.MERGED_OFF_LOGITS_CALLS[0] == m0      # the HIP op ran, without the merged row
+        res[merged] = (y.detach(), qq.grad, {n: p.grad.clone() for n, p in att.named_parameters()})
+    (ym, gqm, gpm), (yd, gqd, gpd) = res[True], res[False]
+    err = lambda a, b: float((a - b).abs().max()) / max(float(b.abs().max()), 1e-30)      # of the tensor's scale
+    errs = dict(y=err(ym, yd), g_query=err(gqm, gqd), **{n: err(gpm[n], gpd[n]) for n in gpd})
+    bad = {k: v for k, v in errs.items() if v > 1e-5}
+    assert not bad, (bad, errs)
+
+
 def test_abi32_stride_arguments_are_validated_at_the_c_boundary(hip):
     """ol_stride / g_value_stride of the fused entry points (include/selfocc_hip.h, ABI 32): a bad value is an error string,
     never a wild write."""
