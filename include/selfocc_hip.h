@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SELFOCC_ABI_VERSION 33
+#define SELFOCC_ABI_VERSION 34
 
 int selfocc_abi_version(void);
 const char *selfocc_last_error(void);
@@ -586,6 +586,73 @@ typedef struct so_depth_metric_args {
 
 size_t selfocc_depth_metric_ws_bytes(const so_depth_metric_args *args);
 int selfocc_depth_metric(const so_depth_metric_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Occupancy metric tail of eval_iou_kitti.py (:166-190): the counters of IoU (utils/metric_util.py:168-233),
+ * SSCMetrics (utils/scenerf_metric.py:43-188) and, optionally, MeanIoU (selfocc_iou_counts layout) in ONE
+ * streaming pass over an (H, W, D) volume, n = H * W * D < 2^31.  Every counter is exact int64, added (+=).
+ *   prediction p: pred (integer, pred_dtype SO_LBL_U8 / I32 / I64; bool = u8) OR sdf f32 with
+ *     p = (sdf <= thresh) (NaN -> 0) and crop {lo_h, hi_h, lo_w, hi_w, lo_d, hi_d}: index i_k outside
+ *     [lo_k, n_k - hi_k) -> 0 (as so_occ_args.crop).  occ (n) int32 receives that p (sdf form only).
+ *   label t: gt of gt_dtype (SO_LBL_F32 / U8 / I32 / I64), read at (h, W - 1 - w, d) when flip_gt.  A float
+ *     label that is not an integer equals no class; it is > 0 / == 0 / == 255 as the float compares.
+ *   iou (3) seen, correct, positive: over voxels inside iou_mask (NULL: all), seen = #(t != iou_empty and
+ *     t != iou_ignore; iou_ignore < 0: no ignore label), correct = sum of p over the seen voxels, positive =
+ *     sum of p.  Kitti form: iou_empty = 0, iou_ignore = 255; Occ3D form: 17, -1.
+ *   completion (3) tp, fp, fn of (t > 0, p > 0); semantic (3, n_classes) tp, fp, fn per class j < n_classes
+ *     (1 <= n_classes <= 256): t == p in range -> tp[t]; else fp[p], fn[t] for those in range.  Both over the
+ *     voxels with nonempty (NULL: all) and t != 255; completion also needs nonsurface.  ssc_keep255 = 1 counts a
+ *     t == 255 voxel as (t, p) = (0, 0) instead (SSCMetrics.get_score_* called directly).
+ *   miou (3, n_miou + 1), the MeanIoU counts of p_m = p * lut[sem] against t over t != 255: miou_map (256)
+ *     maps a label value to its column (-1: none; injective), column n_miou is t / p_m != miou_empty.  sem
+ *     (n) int64 indexes lut (n_lut entries, negative from the end); an index out of range gives p_m = 0 and
+ *     counts into bad (if given).
+ *   d_range (2) int32: (min, max) of the d index over t not in {0, 255}, (-1, -1) if none; needs ws.
+ *   ws (4) uint32 device scratch, zero before the first call; every call leaves it zero again.  Calls that
+ *     share a ws must be ordered (one stream).
+ * At least one of iou / completion / semantic / miou / d_range / occ.  No host synchronisation. */
+enum { SO_LBL_F32 = 0, SO_LBL_U8 = 1, SO_LBL_I32 = 2, SO_LBL_I64 = 3 };
+
+typedef struct so_ssc_metric_args {
+    int32_t H, W, D;
+    int32_t pred_dtype;
+    const void *pred;
+    const float *sdf;
+    float thresh;
+    int32_t crop[6];
+    int32_t gt_dtype;
+    const void *gt;
+    int32_t flip_gt;
+    int32_t iou_empty, iou_ignore;
+    int32_t n_classes;
+    int32_t ssc_keep255;
+    int32_t n_lut;
+    const uint8_t *nonempty;
+    const uint8_t *nonsurface;
+    const uint8_t *iou_mask;
+    const int64_t *sem;
+    const int32_t *lut;
+    const int32_t *miou_map;
+    int32_t n_miou, miou_empty;
+    const int64_t *coords; /* (n_coords, 3): selfocc_iou_coords only */
+    int64_t n_coords;
+    unsigned long long *iou;
+    unsigned long long *completion;
+    unsigned long long *semantic;
+    unsigned long long *miou;
+    unsigned long long *bad;
+    int32_t *d_range;
+    int32_t *occ;
+    uint32_t *ws;
+} so_ssc_metric_args;
+
+int selfocc_ssc_metric(const so_ssc_metric_args *args, void *stream);
+
+/* IoU._after_step(outputs, coords) (metric_util.py:189-199): iou[0] += n_coords, iou[1] += sum of pred at the
+ * (n_coords, 3) int64 rows of coords (each in [-size, size) along (H, W, D), negative from the end, duplicates
+ * counted as often as they occur), iou[2] += sum of pred.  A row out of range is skipped and counted into bad
+ * (required).  Uses H, W, D, pred, pred_dtype, coords, n_coords, iou, bad. */
+int selfocc_iou_coords(const so_ssc_metric_args *args, void *stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,7 @@ its exported symbols being callable with these layouts.
 """
 import ctypes as C
 
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 # enums ---------------------------------------------------------------------------
 RAYS_EXPLICIT, RAYS_PIXEL_GRID = 0, 1
@@ -17,6 +17,7 @@ FLAG_DEPTH_DIV_NORM, FLAG_CLAMP_RGB, FLAG_EXACT, FLAG_NO_SKIP, FLAG_NO_FACE_SAFE
 VALUE_PIXEL_MAJOR, VALUE_HEAD_MAJOR = 0, 1
 DTYPE_F32, DTYPE_BF16 = 0, 1
 LINEAR_RELU = 1
+LBL_F32, LBL_U8, LBL_I32, LBL_I64 = 0, 1, 2, 3
 
 _f, _i, _p = C.c_float, C.c_int32, C.c_void_p
 
@@ -112,6 +113,22 @@ class SoDepthMetricArgs(C.Structure):
     ]
 
 
+class SoSscMetricArgs(C.Structure):
+    _fields_ = [
+        ("H", _i), ("W", _i), ("D", _i), ("pred_dtype", _i),
+        ("pred", _p), ("sdf", _p),
+        ("thresh", _f), ("crop", _i * 6),
+        ("gt_dtype", _i), ("gt", _p),
+        ("flip_gt", _i), ("iou_empty", _i), ("iou_ignore", _i), ("n_classes", _i), ("ssc_keep255", _i), ("n_lut", _i),
+        ("nonempty", _p), ("nonsurface", _p), ("iou_mask", _p),
+        ("sem", _p), ("lut", _p), ("miou_map", _p),
+        ("n_miou", _i), ("miou_empty", _i),
+        ("coords", _p), ("n_coords", C.c_int64),
+        ("iou", _p), ("completion", _p), ("semantic", _p), ("miou", _p), ("bad", _p),
+        ("d_range", _p), ("occ", _p), ("ws", _p),
+    ]
+
+
 # every symbol include/selfocc_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "selfocc_abi_version": (C.c_int, []),
@@ -162,4 +179,6 @@ SYMBOLS = {
     "selfocc_reproj_bwd": (C.c_int, [C.POINTER(SoReprojArgs), _p, _p, _p, _p]),
     "selfocc_depth_metric_ws_bytes": (C.c_size_t, [C.POINTER(SoDepthMetricArgs)]),
     "selfocc_depth_metric": (C.c_int, [C.POINTER(SoDepthMetricArgs), _p]),
+    "selfocc_ssc_metric": (C.c_int, [C.POINTER(SoSscMetricArgs), _p]),
+    "selfocc_iou_coords": (C.c_int, [C.POINTER(SoSscMetricArgs), _p]),
 }
