@@ -321,10 +321,19 @@ SO_DEVFN float so_fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 SO_DEVFN float so_fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 // wave-wide AND of a per-lane predicate: one v_cmp + one scalar compare (HIP's __all() goes through a select)
 SO_DEVFN bool so_all(bool p) { return __builtin_amdgcn_ballot_w64(p) == __builtin_amdgcn_ballot_w64(true); }
+// wave-wide AND of p && q && r: one ballot per compare, combined in SGPRs.  so_all(p & q & r) materialises the combined lane
+// mask through a VGPR (v_cndmask + v_cmp) before the ballot: two VALU instructions per use.
+SO_DEVFN bool so_all3(bool p, bool q, bool r) {
+    return (__builtin_amdgcn_ballot_w64(p) & __builtin_amdgcn_ballot_w64(q) & __builtin_amdgcn_ballot_w64(r)) ==
+           __builtin_amdgcn_ballot_w64(true);
+}
 // (h * W + w) * D + d for in-range cells with full-rate 24-bit multiplies (v_mad_u32_u24); the 32-bit / 64-bit
 // integer multiplies the compiler picks for plain ints are quarter rate.  Needs H * W < 2^24, D < 2^24.
+// The first multiply-add is written out: from __umul24(h0, W) + w0 the compiler forms the quarter-rate v_mad_u64_u32.
+// The value differs from the plain expression only where h0 or W leave 24 bits, i.e. for cells that are never addressed.
 SO_DEVFN unsigned so_cell_index(int h0, int w0, int d0, int W, int D) {
-    const unsigned hw = __umul24((unsigned)h0, (unsigned)W) + (unsigned)w0;
+    unsigned hw;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(hw) : "v"(h0), "s"(W), "v"(w0));
     return __umul24(hw, (unsigned)D) + (unsigned)d0;
 }
 SO_DEVFN int so_floor_i(float x) {   // (int)floorf(x) in one instruction
@@ -937,9 +946,8 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom,
         st.gh = gh; st.gw = gw; st.gd = gd;
         const int h0 = so_floor_i(gh), w0 = so_floor_i(gw), d0 = so_floor_i(gd);
         st.h0 = h0; st.w0 = w0; st.d0 = d0;
-        const bool interior = ((unsigned)h0 < (unsigned)(H - 1)) & ((unsigned)w0 < (unsigned)(W - 1)) &
-                              ((unsigned)d0 < (unsigned)(D - 1));
-        st.all_interior = so_all(interior);
+        st.all_interior = so_all3((unsigned)h0 < (unsigned)(H - 1), (unsigned)w0 < (unsigned)(W - 1),
+                                  (unsigned)d0 < (unsigned)(D - 1));
         st.cell = so_cell_index(h0, w0, d0, W, D);
         st.code = 0u;
         if (st.all_interior) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 32u, 0);
