@@ -46,9 +46,46 @@ typedef struct so_axis {
     int32_t tot_len;      /* number of grid points along the axis                      */
 } so_axis;
 
+/* Mapping kinds.  The zero-initialised kind is the piece-wise linear form above, so a
+ * caller that fills only h / w / d keeps its meaning.
+ *
+ * SO_MAP_UPSCALE is NonLinearMapping ('linear_upscale', mappings.py:199-288): uniform inner
+ * cells, outer cells that grow by `inc` metres each.  Per axis, in float32, in this order:
+ *   h / w (metre y / x, symmetric):  a = |m|
+ *   d     (metre z, one-sided):      a = m - start
+ *     base  = min(a / unit, size0)                     (size0 = inner cells)
+ *     o     = relu(a - range0)                         (range0 = metres of the inner part)
+ *     k     = floor(sqrt(c2 + (2 * o) / inc) - c)
+ *     resi  = (o - k * unit) - ((inc * k) * (k + 1)) / 2
+ *     g_abs = (base + k) + resi / (unit + (k + 1) * inc)
+ *   h / w: g = (sign(m) * g_abs + off0) + off1        (off0 / off1 = inner / outer cells)
+ *   d:     g = g_abs
+ * The axis fields read: size0 / size1 = inner / outer cells, range0 = metres of the inner part
+ * (range_inner, or z1 - z0), range1 = metres of the outer part, start = z0 on d (0 on h / w).
+ * d grid / d metre is 1 / unit inside and 1 / (unit + (k + 1) * inc) in outer cell k. */
+#define SO_MAP_LINEAR 0
+#define SO_MAP_UPSCALE 1
+
+/* constants of one 'linear_upscale' axis, computed in double on the host, stored as float32 */
+typedef struct so_upscale_axis {
+    float unit; /* metres per inner cell (hw_unit / z_unit)                   */
+    float inc;  /* growth of the cell size per outer cell (increase_unit)     */
+    float c;    /* 0.5 + unit / inc                                           */
+    float c2;   /* (0.5 + unit / inc) ** 2                                    */
+} so_upscale_axis;
+
 typedef struct so_mapping {
     so_axis h, w, d;
+    int32_t kind;                /* SO_MAP_LINEAR or SO_MAP_UPSCALE                  */
+    int32_t _pad[3];             /* the kind fields take 64 bytes: the fields after
+                                    so_mapping keep their offsets mod 64              */
+    so_upscale_axis uh, uw, ud;  /* kind == SO_MAP_UPSCALE only                      */
 } so_mapping;
+
+/* Device form of meter2grid(xyz, normalize) for either mapping kind: xyz (n, 3) metres
+ * (x, y, z) -> hwd (n, 3) grid coordinates (h, w, d), divided by tot_len - 1 when
+ * `normalize` is non-zero.  Both pointers are device memory. */
+int selfocc_meter2grid(const so_mapping *map, const float *xyz, int n, int normalize, float *hwd, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * SDF volume rendering.  Replaces the sdfstudio-fork NeuSCustomModel.__call__ that

@@ -95,6 +95,31 @@ NUM_RAYS['kitti_raw'] = [176, 608]
 KITTI_OCC_AABB = [-25.6, 0, -2.0, 25.6, 51.2, 4.4]            # eval_iou_kitti.py:161
 
 
+# NeuSHead's default mapping_args (model/head/neus_head/neus_head.py): 'linear_upscale', a 321 x 321 x 31 lattice over
+# +-80 m (51.2 m of 0.4 m cells, then 32 cells growing to 28.8 m) x [-4, 12] m (20 cells to 4 m, 10 growing cells to 12 m)
+UPSCALE_MAPPING = dict(nonlinear_mode='linear_upscale', h_size=[128, 32], h_range=[51.2, 28.8], h_half=False,
+                       w_size=[128, 32], w_range=[51.2, 28.8], w_half=False, d_size=[20, 10], d_range=[-4.0, 4.0, 12.0])
+
+
+def upscale_variant(cfg, mapping_args=UPSCALE_MAPPING):
+    """a shipped config switched to the 'linear_upscale' mapping, with every size that follows from the mapping made to
+    match it: encoder / head mapping_args, lifter tpv_h / w / z, positional-encoding tot_range, head roi_aabb"""
+    from selfocc_amd.mapping import GridMeterMapping
+    cfg = copy.deepcopy(cfg)
+    m = cfg['model']
+    for part in (m['encoder'], m['head']):
+        part['mapping_args'] = dict(mapping_args)
+    mp = GridMeterMapping(**mapping_args)
+    m['lifter'].update(tpv_h=mp.size_h, tpv_w=mp.size_w, tpv_z=mp.size_d)
+    r = mapping_args['h_range'][0] + mapping_args['h_range'][1]
+    box = [-r, -r, mapping_args['d_range'][0], r, r, mapping_args['d_range'][2]]
+    m['head']['roi_aabb'] = list(box)
+    pe = m['encoder'].get('positional_encoding')
+    if isinstance(pe, dict) and 'tot_range' in pe:
+        pe['tot_range'] = list(box)
+    return cfg
+
+
 def shipped_for_eval(name):
     info = SHIPPED[name]
     cfg = modify_for_eval(shipped(name), info['dataset'], novel_depth=info['eval'] == 'render_novel')

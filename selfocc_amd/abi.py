@@ -18,6 +18,7 @@ VALUE_PIXEL_MAJOR, VALUE_HEAD_MAJOR = 0, 1
 DTYPE_F32, DTYPE_BF16 = 0, 1
 LINEAR_RELU = 1
 LBL_F32, LBL_U8, LBL_I32, LBL_I64 = 0, 1, 2, 3
+MAP_LINEAR, MAP_UPSCALE = 0, 1
 
 _f, _i, _p = C.c_float, C.c_int32, C.c_void_p
 
@@ -27,8 +28,13 @@ class SoAxis(C.Structure):
                 ("off0", _f), ("off1", _f), ("start", _f), ("tot_len", _i)]
 
 
+class SoUpscaleAxis(C.Structure):
+    _fields_ = [("unit", _f), ("inc", _f), ("c", _f), ("c2", _f)]
+
+
 class SoMapping(C.Structure):
-    _fields_ = [("h", SoAxis), ("w", SoAxis), ("d", SoAxis)]
+    _fields_ = [("h", SoAxis), ("w", SoAxis), ("d", SoAxis),
+                ("kind", _i), ("_pad", _i * 3), ("uh", SoUpscaleAxis), ("uw", SoUpscaleAxis), ("ud", SoUpscaleAxis)]
 
 
 class SoRenderArgs(C.Structure):
@@ -133,6 +139,7 @@ class SoSscMetricArgs(C.Structure):
 SYMBOLS = {
     "selfocc_abi_version": (C.c_int, []),
     "selfocc_last_error": (C.c_char_p, []),
+    "selfocc_meter2grid": (C.c_int, [C.POINTER(SoMapping), _p, _i, _i, _p, _p]),
     "selfocc_render_fwd": (C.c_int, [C.POINTER(SoRenderArgs), _p]),
     "selfocc_render_bwd": (C.c_int, [C.POINTER(SoRenderBwdArgs), _p]),
     "selfocc_render_bwd_ws_bytes": (C.c_size_t, [C.POINTER(SoRenderBwdArgs)]),

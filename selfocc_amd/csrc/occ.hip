@@ -99,6 +99,8 @@ SO_DEVFN void so_team_lookup(const void *__restrict__ vol, int stride, int ch0, 
     if (!(b > -INFINITY)) arg = 0;
 }
 
+// MK: mapping kind (so_locate_k)
+template <int MK = SO_MAP_LINEAR>
 __global__ __launch_bounds__(256) void field_query_kernel(so_query_args a) {
     const long long gt = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long pt = gt / kTeam;
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(256) void field_query_kernel(so_query_args a) {
     const bool live = pt < a.n;
     const int i = live ? (int)pt : a.n - 1;      // dead teams shadow the last point (the shuffles need every lane)
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
-    const so_cell c = so_locate(a.map, a.xyz[3 * (size_t)i], a.xyz[3 * (size_t)i + 1], a.xyz[3 * (size_t)i + 2]);
+    const so_cell c = so_locate_k<MK>(a.map, a.xyz[3 * (size_t)i], a.xyz[3 * (size_t)i + 1], a.xyz[3 * (size_t)i + 2]);
     if (a.sdf && j == 0 && live) {
         float v[8], wk[8];
         so_gather_sdf(a.sdf_vol, H, W, D, c, v);
@@ -130,13 +132,14 @@ __global__ __launch_bounds__(256) void field_query_kernel(so_query_args a) {
 // Backward of field_query_kernel with respect to the volume(s): the transpose of the trilinear gather.
 // One lane per query point, 8 (x n_sem) float atomics; the lattice is small (640 k points at the shipped
 // sizes) and neighbouring points hit neighbouring voxels, so the adds of a wave land in a few cache lines.
+template <int MK = SO_MAP_LINEAR>
 __global__ __launch_bounds__(256) void field_query_bwd_kernel(so_query_args a, const float *__restrict__ g_sdf,
                                                               const float *__restrict__ g_logits,
                                                               float *__restrict__ g_sdf_vol, float *__restrict__ g_feat_vol) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
-    const so_cell c = so_locate(a.map, a.xyz[3 * (size_t)i], a.xyz[3 * (size_t)i + 1], a.xyz[3 * (size_t)i + 2]);
+    const so_cell c = so_locate_k<MK>(a.map, a.xyz[3 * (size_t)i], a.xyz[3 * (size_t)i + 1], a.xyz[3 * (size_t)i + 2]);
     const float fd[2] = {c.fd0, c.fd1}, fw[2] = {c.fw0, c.fw1}, fh[2] = {c.fh0, c.fh1};
     const float gs = (g_sdf && g_sdf_vol) ? g_sdf[i] : 0.0f;
 #pragma unroll
@@ -243,7 +246,8 @@ extern "C" int selfocc_field_query(const so_query_args *args, void *stream) {
                kTeam * kTeamRounds);
     const long long nthreads = (long long)a.n * kTeam;
     SO_REQUIRE(nthreads < (1LL << 31) * 256, "field_query: too many points");
-    hipLaunchKernelGGL(field_query_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((a.map.kind == SO_MAP_UPSCALE ? field_query_kernel<SO_MAP_UPSCALE> : field_query_kernel<SO_MAP_LINEAR>),
+                       dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     return so_launch_status();
 }
 
@@ -261,8 +265,8 @@ extern "C" int selfocc_field_query_bwd(const so_query_args *args, const float *g
         SO_REQUIRE(a.n_sem > 0 && a.feat_stride >= a.n_rgb + a.n_sem, "semantic gradient needs n_sem > 0 and a valid feat_stride");
     }
     if (!g_sdf && !g_logits) return 0;
-    hipLaunchKernelGGL(field_query_bwd_kernel, dim3((a.n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, g_sdf,
-                       g_logits, g_sdf_vol, g_feat_vol);
+    hipLaunchKernelGGL((a.map.kind == SO_MAP_UPSCALE ? field_query_bwd_kernel<SO_MAP_UPSCALE> : field_query_bwd_kernel<SO_MAP_LINEAR>), dim3((a.n + 255) / 256),
+                       dim3(256), 0, (hipStream_t)stream, a, g_sdf, g_logits, g_sdf_vol, g_feat_vol);
     return so_launch_status();
 }
 

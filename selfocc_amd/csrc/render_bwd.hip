@@ -156,6 +156,7 @@ SO_DEVFN void ray_bounds(const so_render_args &a, const RayGeomB &g, float &tn, 
     tf = fmaxf(tf, tn + 1e-6f);
 }
 
+template <int MK = SO_MAP_LINEAR>
 SO_DEVFN so_cell sample_cell(const so_render_args &a, const RayGeomB &g, float t0, float t1) {
     float px, py, pz;
     if (a.sample_pos == SO_SAMPLE_AT_START) {
@@ -164,7 +165,7 @@ SO_DEVFN so_cell sample_cell(const so_render_args &a, const RayGeomB &g, float t
         const float tt = t0 + t1;
         px = g.ox + (g.dx * tt) / 2.0f; py = g.oy + (g.dy * tt) / 2.0f; pz = g.oz + (g.dz * tt) / 2.0f;
     }
-    return so_locate(a.map, px, py, pz);
+    return so_locate_k<MK>(a.map, px, py, pz);
 }
 
 // run of consecutive lanes with one key: returns the run's length at its head lane (0 elsewhere) and the head's lane
@@ -185,7 +186,8 @@ SO_DEVFN int rb_run(int key, int lane, int &head_lane) {
 // per SIMD, latency-bound); scan carries and per-ray sums cross the waves through a few floats of LDS.
 // (Measured and dropped, round 4: forcing the 24-channel BIN instantiation to 3 / 4 waves per SIMD with
 // amdgpu_waves_per_eu — 168 / 128 VGPRs, 296 / 484 B of scratch — 0.98 -> 1.67 / 1.96 ms: the spills land in the corner loops.)
-template <int NF, bool BF16, int M, int WPR, bool BIN>
+// MK = mapping kind (so_locate_k): the 'linear_upscale' instances differ only in sample_cell
+template <int NF, bool BF16, int M, int WPR, bool BIN, int MK = SO_MAP_LINEAR>
 __global__ __launch_bounds__(256) void render_bwd_kernel(so_render_bwd_args ba, RbBin bin) {
     static_assert(WPR == 1 || WPR == 4, "waves per ray");
     constexpr int RECF = RbRec<NF>::RECF, NCH = RbRec<NF>::NCH;
@@ -233,7 +235,7 @@ __global__ __launch_bounds__(256) void render_bwd_kernel(so_render_bwd_args ba, 
         const float t0 = edge_t(a, ray, ic, tn, tf), t1 = edge_t(a, ray, ic + 1, tn, tf);
         delta[j] = t1 - t0;
         tmid[j] = (t0 + t1) / 2.0f;
-        cell[j] = sample_cell(a, g, t0, t1);
+        cell[j] = sample_cell<MK>(a, g, t0, t1);
         float v[8], wk[8];
         so_gather_sdf(a.sdf_vol, H, W, D, cell[j], v);
         sdfv[j] = so_trilerp_sdf(cell[j], v, wk);
@@ -642,7 +644,8 @@ __global__ __launch_bounds__(256) void render_bwd_kernel(so_render_bwd_args ba, 
 // with or without the table: what is left is the ~30 IEEE divisions per sample of the canonical cell, which the pass must
 // repeat exactly.)
 constexpr int kCountWaves = 16, kCountSlots = 1024;
-__global__ __launch_bounds__(kCountWaves * 64) void rb_count_kernel(so_render_args a, RbBin b) {
+template <int MK>
+SO_DEVFN void rb_count_body(const so_render_args &a, const RbBin &b) {
     __shared__ int tkey[kCountSlots], tcnt[kCountSlots];
     for (int k = threadIdx.x; k < kCountSlots; k += kCountWaves * 64) { tkey[k] = -1; tcnt[k] = 0; }
     __syncthreads();
@@ -657,7 +660,7 @@ __global__ __launch_bounds__(kCountWaves * 64) void rb_count_kernel(so_render_ar
             const int smp = s0 + lane;
             int key = -1;
             if (smp < S) {
-                const so_cell c = sample_cell(a, g, edge_t(a, ray, smp, tn, tf), edge_t(a, ray, smp + 1, tn, tf));
+                const so_cell c = sample_cell<MK>(a, g, edge_t(a, ray, smp, tn, tf), edge_t(a, ray, smp + 1, tn, tf));
                 key = rb_key(b, c, H, W, D) * kShards + rb_shard((long long)ray * S + smp);
             }
             int hl;
@@ -674,6 +677,8 @@ __global__ __launch_bounds__(kCountWaves * 64) void rb_count_kernel(so_render_ar
     for (int k = threadIdx.x; k < kCountSlots; k += kCountWaves * 64)
         if (tkey[k] >= 0 && tcnt[k] > 0) atomicAdd(b.counts + tkey[k], tcnt[k]);
 }
+__global__ __launch_bounds__(kCountWaves * 64) void rb_count_kernel(so_render_args a, RbBin b) { rb_count_body<SO_MAP_LINEAR>(a, b); }
+__global__ __launch_bounds__(kCountWaves * 64) void rb_count_up_kernel(so_render_args a, RbBin b) { rb_count_body<SO_MAP_UPSCALE>(a, b); }
 
 // counts -> cursors + items, in two launches of ceil(n_bricks / 1024) blocks: per-block totals, then the scan proper
 __global__ __launch_bounds__(1024) void rb_scan1_kernel(RbBin b) {
@@ -927,19 +932,19 @@ inline bool rb_in_range(const so_render_args &a) {
            (size_t)a.n_rays * a.n_samples < ((size_t)1 << 31);
 }
 
-template <int NF, bool BF16, bool BIN>
+template <int NF, bool BF16, bool BIN, int MK>
 int launch_ray(const so_render_bwd_args &ba, const RbBin &bin, hipStream_t st) {
     const int S = ba.fwd.n_samples;
     const int m = (S + 63) / 64;
     if (m >= 3) {   // four waves per ray: M = ceil(m / 4) steps per wave
         const int blocks = ba.fwd.n_rays;
-#define SO_L(MM) hipLaunchKernelGGL((render_bwd_kernel<NF, BF16, MM, 4, BIN>), dim3(blocks), dim3(256), 0, st, ba, bin)
+#define SO_L(MM) hipLaunchKernelGGL((render_bwd_kernel<NF, BF16, MM, 4, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin)
         if (m <= 4) SO_L(1);
         else SO_L(2);
 #undef SO_L
     } else {
         const int blocks = (ba.fwd.n_rays + 3) / 4;
-#define SO_L(MM) hipLaunchKernelGGL((render_bwd_kernel<NF, BF16, MM, 1, BIN>), dim3(blocks), dim3(256), 0, st, ba, bin)
+#define SO_L(MM) hipLaunchKernelGGL((render_bwd_kernel<NF, BF16, MM, 1, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin)
         if (m <= 1) SO_L(1);
         else SO_L(2);
 #undef SO_L
@@ -947,11 +952,11 @@ int launch_ray(const so_render_bwd_args &ba, const RbBin &bin, hipStream_t st) {
     return so_launch_status();
 }
 
-template <int NF, bool BF16>
-int launch_m(const so_render_bwd_args &ba, hipStream_t st) {
+template <int NF, bool BF16, int MK>
+int launch_mk(const so_render_bwd_args &ba, hipStream_t st) {
     const so_render_args &a = ba.fwd;
     const bool binned = ba.scatter_ws != nullptr && rb_in_range(a) && (ba.g_sdf_vol || ba.g_feat_vol);
-    if (!binned) return launch_ray<NF, BF16, false>(ba, RbBin{}, st);
+    if (!binned) return launch_ray<NF, BF16, false, MK>(ba, RbBin{}, st);
     RbBin bin;
     int max_items = 0;
     const size_t need = rb_layout<NF>(a, rb_chunk(), (char *)ba.scatter_ws, &bin, &max_items);
@@ -962,10 +967,11 @@ int launch_m(const so_render_bwd_args &ba, hipStream_t st) {
     hipError_t e = hipMemsetAsync(ba.scatter_ws, 0, rb_zeroed_bytes(a), st);
     SO_REQUIRE(e == hipSuccess, "render_bwd: hipMemsetAsync failed: %s", hipGetErrorString(e));
     const unsigned sblocks = (unsigned)((rb_bricks(a, nullptr) + 1023) / 1024);
-    hipLaunchKernelGGL(rb_count_kernel, dim3((unsigned)((a.n_rays + kCountWaves - 1) / kCountWaves)), dim3(kCountWaves * 64), 0, st, a, bin);
+    hipLaunchKernelGGL((MK == SO_MAP_UPSCALE ? rb_count_up_kernel : rb_count_kernel), dim3((unsigned)((a.n_rays + kCountWaves - 1) / kCountWaves)),
+                       dim3(kCountWaves * 64), 0, st, a, bin);
     hipLaunchKernelGGL(rb_scan1_kernel, dim3(sblocks), dim3(1024), 0, st, bin);
     hipLaunchKernelGGL(rb_scan2_kernel, dim3(sblocks), dim3(1024), 0, st, bin);
-    if (int rc = launch_ray<NF, BF16, true>(ba, bin, st)) return rc;
+    if (int rc = launch_ray<NF, BF16, true, MK>(ba, bin, st)) return rc;
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
     const size_t lds = (size_t)kTileVox * RbRec<NF>::RW * 8;
     // 512 threads per item (SELFOCC_RB_THREADS chose among 256 / 512 / 1024 while the kernel was tuned: 512 won at every shape)
@@ -975,6 +981,19 @@ int launch_m(const so_render_bwd_args &ba, hipStream_t st) {
     hipLaunchKernelGGL((rb_brick_kernel<NF, 512>), dim3(max_items), dim3(512), lds, st, bin, ba.g_sdf_vol, ba.g_feat_vol,
                        ba.g_inv_s, H, W, D);
     return so_launch_status();
+}
+
+// the mapping kind picks the instances ('linear_upscale' is built for the widths of the forward's upscale route)
+template <int NF, bool BF16>
+int launch_m(const so_render_bwd_args &ba, hipStream_t st) {
+    if (ba.fwd.map.kind == SO_MAP_UPSCALE) {
+        if constexpr (NF == 24 && BF16) {
+            SO_REQUIRE(false, "the 'linear_upscale' mapping is built for n_rgb + n_sem = 0, 3, 8 and float32 24 (got bfloat16 24)");
+        } else {
+            return launch_mk<NF, BF16, SO_MAP_UPSCALE>(ba, st);
+        }
+    }
+    return launch_mk<NF, BF16, SO_MAP_LINEAR>(ba, st);
 }
 
 }  // namespace

@@ -182,7 +182,8 @@ SO_DEVFN void so_gather_feat_interior(__amdgpu_buffer_rsrc_t rf, int W, int D, u
     }
 }
 
-template <int NF, bool BF16, bool PER_SAMPLE>
+// MK: the mapping kind (SO_MAP_LINEAR / SO_MAP_UPSCALE), a compile-time choice of so_locate_k
+template <int NF, bool BF16, bool PER_SAMPLE, int MK = SO_MAP_LINEAR>
 SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g) {
     constexpr int NSEM = NF > 4 ? NF - 3 : 0;  // NF = 3 rgb (+1 pad) or 3 rgb + n_sem
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
@@ -212,7 +213,7 @@ SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g)
             px = g.ox + (g.dx * tt) / 2.0f; py = g.oy + (g.dy * tt) / 2.0f;
             pz = g.oz + (g.dz * tt) / 2.0f;
         }
-        so_cell c = so_locate(a.map, px, py, pz);
+        so_cell c = so_locate_k<MK>(a.map, px, py, pz);
         float v[8], wk[8];
         so_gather_sdf(a.sdf_vol, H, W, D, c, v);
         float sdf = so_trilerp_sdf(c, v, wk);
@@ -1088,10 +1089,13 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom,
 }
 
 // MODE: 0 = canonical (EXACT), 1 = fast, 2 = fast with canonical cell selection near voxel faces,
-//       3 / 4 = the code-ahead skip marcher (SDF-only per-ray launches with brick + skip) without / with it
+//       3 / 4 = the code-ahead skip marcher (SDF-only per-ray launches with brick + skip) without / with it,
+//       5 = canonical under the 'linear_upscale' mapping (g(t) is not affine: no fast path, no brick, no skip)
 template <int NF, bool BF16, bool PER_SAMPLE, int MODE, class GeomFn>
 SO_DEVFN void so_march(const so_render_args &a, int ray, GeomFn geom, float *lds = nullptr, int lane = 0, bool store = true) {
-    if constexpr (MODE >= 3) {
+    if constexpr (MODE == 5) {
+        so_march_exact<NF, BF16, PER_SAMPLE, SO_MAP_UPSCALE>(a, ray, geom(a));
+    } else if constexpr (MODE >= 3) {
         static_assert(NF == 0 && !PER_SAMPLE, "skip marcher: SDF-only per-ray launches");
         so_march_fast_ahead<MODE == 4>(a, ray, geom, lds, lane, store);
     } else if constexpr (MODE != 0) {
@@ -1185,7 +1189,7 @@ SO_DEVFN void pixgrid_body(const so_render_args &a, int tiles_x, int tiles_y) {
                                                              s_sem + threadIdx.x);
     } else {
 #ifdef SO_AHEAD_LDS
-        if constexpr (MODE >= 3) {
+        if constexpr (MODE == 3 || MODE == 4) {
             // whole-wave LDS staging: lanes beyond the lattice edge shadow the nearest real pixel and skip the stores
             __shared__ float s_box[4 * 64];
             const bool real = (ix < a.nx) && (iy < a.ny);
@@ -1244,8 +1248,16 @@ int dispatch_ps(const so_render_args &a, hipStream_t st) {
     // (SO_FLAG_RAY_PER_LANE, the A/B route of rounds 2 - 4 through ray-per-lane per-sample kernels, is accepted and ignored
     // since ABI v30: 48 instantiations nobody shipped)
     if (per_sample) return so_render_fwd_samples<NF, BF16>(a, st);
-    // the fast path needs g(t) affine in t: no jitter, single-segment axes
-    bool fast = !(a.flags & SO_FLAG_EXACT) && a.jitter_mode == SO_JITTER_NONE &&
+    // 'linear_upscale': the canonical march with the upscale mapping (no brick re-pack, no skip codes)
+    if (a.map.kind == SO_MAP_UPSCALE) {
+        if constexpr (NF == 24 && BF16) {
+            SO_REQUIRE(false, "the 'linear_upscale' mapping is built for n_rgb + n_sem = 0, 3, 8 and float32 24 (got bfloat16 24)");
+        } else {
+            return launch_fwd<NF, BF16, false, 5>(a, st);
+        }
+    }
+    // the fast path needs g(t) affine in t: no jitter, single-segment axes, the linear mapping kind
+    bool fast = !(a.flags & SO_FLAG_EXACT) && a.jitter_mode == SO_JITTER_NONE && a.map.kind == SO_MAP_LINEAR &&
                 a.map.h.size1 == 0.0f && a.map.w.size1 == 0.0f && a.map.d.size1 == 0.0f &&
                 (long long)a.map.h.tot_len * a.map.w.tot_len < (1 << 24) && a.map.d.tot_len < (1 << 24);   // so_cell_index
     if (fast) {
@@ -1268,13 +1280,56 @@ int dispatch_ps(const so_render_args &a, hipStream_t st) {
 }  // namespace
 
 int so_validate_mapping(const so_mapping &m) {
+    SO_REQUIRE(m.kind == SO_MAP_LINEAR || m.kind == SO_MAP_UPSCALE, "mapping: unknown kind %d (0 = linear, 1 = linear_upscale)",
+               (int)m.kind);
     const so_axis *ax[3] = {&m.h, &m.w, &m.d};
+    const so_upscale_axis *ux[3] = {&m.uh, &m.uw, &m.ud};
     for (int i = 0; i < 3; ++i) {
         SO_REQUIRE(ax[i]->tot_len >= 2, "mapping axis %d: tot_len must be >= 2", i);
         SO_REQUIRE(ax[i]->size0 > 0 && ax[i]->range0 > 0, "mapping axis %d: size0/range0 must be > 0", i);
-        SO_REQUIRE(ax[i]->size1 == 0 || ax[i]->range1 > 0, "mapping axis %d: range1 must be > 0", i);
+        if (m.kind == SO_MAP_LINEAR) {
+            SO_REQUIRE(ax[i]->size1 == 0 || ax[i]->range1 > 0, "mapping axis %d: range1 must be > 0", i);
+        } else {
+            // the reference divides by increase_unit and takes sqrt(c^2 + 2 o / increase_unit): both need it > 0,
+            // and increase_unit = (range_outer - outer * unit) * 2 / outer / (outer + 1) needs outer >= 1
+            SO_REQUIRE(ax[i]->size1 >= 1, "linear_upscale axis %d: outer cells must be >= 1 (got %g)", i, (double)ax[i]->size1);
+            SO_REQUIRE(ux[i]->unit > 0 && __builtin_isfinite(ux[i]->unit), "linear_upscale axis %d: unit must be > 0 (got %g)", i,
+                       (double)ux[i]->unit);
+            SO_REQUIRE(ux[i]->inc > 0 && __builtin_isfinite(ux[i]->inc),
+                       "linear_upscale axis %d: increase unit must be > 0 (got %g): the outer range must exceed outer * unit",
+                       i, (double)ux[i]->inc);
+        }
     }
     return 0;
+}
+
+namespace {
+template <int MK>
+__global__ __launch_bounds__(256) void meter2grid_kernel(so_mapping m, const float *__restrict__ xyz, int n, int normalize,
+                                                         float *__restrict__ hwd) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float gh, gw, gd, sh, sw, sd;
+    so_m2g<MK>(m, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], gh, gw, gd, sh, sw, sd);
+    if (normalize) {
+        gh = gh / (float)(m.h.tot_len - 1); gw = gw / (float)(m.w.tot_len - 1); gd = gd / (float)(m.d.tot_len - 1);
+    }
+    hwd[3 * (size_t)i] = gh; hwd[3 * (size_t)i + 1] = gw; hwd[3 * (size_t)i + 2] = gd;
+}
+}  // namespace
+
+extern "C" int selfocc_meter2grid(const so_mapping *map, const float *xyz, int n, int normalize, float *hwd, void *stream) {
+    SO_REQUIRE(map != nullptr, "map is NULL");
+    if (so_validate_mapping(*map)) return -1;
+    SO_REQUIRE(n >= 0, "n must be >= 0");
+    if (n == 0) return 0;
+    SO_REQUIRE(xyz != nullptr && hwd != nullptr, "xyz / hwd is NULL");
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (map->kind == SO_MAP_UPSCALE)
+        hipLaunchKernelGGL(meter2grid_kernel<SO_MAP_UPSCALE>, grid, dim3(256), 0, (hipStream_t)stream, *map, xyz, n, normalize, hwd);
+    else
+        hipLaunchKernelGGL(meter2grid_kernel<SO_MAP_LINEAR>, grid, dim3(256), 0, (hipStream_t)stream, *map, xyz, n, normalize, hwd);
+    return so_launch_status();
 }
 
 int so_validate_render(const so_render_args &a) {

@@ -122,8 +122,8 @@ SO_DEVFN float so_wave_sum(float v) {
     return v;
 }
 
-// WPR = waves per ray (1, 2 or 4); a 256-thread block serves 4 / WPR rays.
-template <int NF, bool BF16, int WPR>
+// WPR = waves per ray (1, 2 or 4); a 256-thread block serves 4 / WPR rays.  MK = mapping kind (so_locate_k).
+template <int NF, bool BF16, int WPR, int MK = SO_MAP_LINEAR>
 __global__ __launch_bounds__(256) void render_fwd_samples_kernel(so_render_args a) {
     constexpr int NSEM = NF > 4 ? NF - 3 : 0;
     constexpr int RPB = 4 / WPR;                  // rays per block
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void render_fwd_samples_kernel(so_render_args 
                 const float tt = t_start + t_end;
                 px = g.ox + (g.dx * tt) / 2.0f; py = g.oy + (g.dy * tt) / 2.0f; pz = g.oz + (g.dz * tt) / 2.0f;
             }
-            const so_cell c = so_locate(a.map, px, py, pz);
+            const so_cell c = so_locate_k<MK>(a.map, px, py, pz);
             float v[8], wk[8];
             so_gather_sdf(a.sdf_vol, H, W, D, c, v);
             sdf = so_trilerp_sdf(c, v, wk);
@@ -322,10 +322,10 @@ __global__ __launch_bounds__(256) void render_fwd_samples_kernel(so_render_args 
     }
 }
 
-template <int NF, bool BF16, int WPR>
+template <int NF, bool BF16, int WPR, int MK = SO_MAP_LINEAR>
 int launch_samples_w(const so_render_args &a, hipStream_t st) {
     constexpr int RPB = 4 / WPR;
-    hipLaunchKernelGGL((render_fwd_samples_kernel<NF, BF16, WPR>), dim3((a.n_rays + RPB - 1) / RPB), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((render_fwd_samples_kernel<NF, BF16, WPR, MK>), dim3((a.n_rays + RPB - 1) / RPB), dim3(256), 0, st, a);
     return so_launch_status();
 }
 
@@ -334,6 +334,15 @@ int launch_samples_w(const so_render_args &a, hipStream_t st) {
 // called by selfocc_render_fwd (render_fwd.hip) for launches that request per-sample outputs
 template <int NF, bool BF16>
 int so_render_fwd_samples(const so_render_args &a, hipStream_t st) {
+    if (a.map.kind == SO_MAP_UPSCALE) {
+        if constexpr (NF == 24 && BF16) {
+            SO_REQUIRE(false, "the 'linear_upscale' mapping is built for n_rgb + n_sem = 0, 3, 8 and float32 24 (got bfloat16 24)");
+        } else {
+            if (a.n_samples <= 64) return launch_samples_w<NF, BF16, 1, SO_MAP_UPSCALE>(a, st);
+            if (a.n_samples <= 128) return launch_samples_w<NF, BF16, 2, SO_MAP_UPSCALE>(a, st);
+            return launch_samples_w<NF, BF16, 4, SO_MAP_UPSCALE>(a, st);
+        }
+    }
     if (a.n_samples <= 64) return launch_samples_w<NF, BF16, 1>(a, st);
     if (a.n_samples <= 128) return launch_samples_w<NF, BF16, 2>(a, st);
     return launch_samples_w<NF, BF16, 4>(a, st);

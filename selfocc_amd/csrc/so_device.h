@@ -76,6 +76,44 @@ SO_DEVFN float so_axis_m2g(const so_axis &A, float m, float &slope) {
     return (t + A.off0) + A.off1;
 }
 
+// NonLinearMapping.meter2grid ('linear_upscale'), one axis (mappings.py:254-288), in the reference's float32 order.
+// SYM: h / w (a = |m|, signed result + off0 + off1); otherwise d (a = m - start, no sign, no offset).
+// slope = d grid / d metre as the reference's autograd takes it: 1 / unit inside, 1 / (unit + (k + 1) inc) in outer cell k.
+template <bool SYM>
+SO_DEVFN float so_axis_m2g_up(const so_axis &A, const so_upscale_axis &U, float m, float &slope) {
+    const float a = SYM ? fabsf(m) : m - A.start;
+    float base = a / U.unit;
+    base = base > A.size0 ? A.size0 : base;                     // clamp(max=inner)
+    const float od = a - A.range0;
+    const float o = od < 0.0f ? 0.0f : od;                      // relu
+    const float k = floorf(sqrtf(U.c2 + (2.0f * o) / U.inc) - U.c);
+    const float resi = (o - k * U.unit) - ((U.inc * k) * (k + 1.0f)) / 2.0f;
+    const float den = U.unit + (k + 1.0f) * U.inc;
+    const float g = (base + k) + resi / den;
+    slope = o > 0.0f ? 1.0f / den : 1.0f / U.unit;
+    if constexpr (SYM) {
+        const float s = m > 0.0f ? 1.0f : (m < 0.0f ? -1.0f : 0.0f);
+        return (s * g + A.off0) + A.off1;
+    } else {
+        return g;
+    }
+}
+
+// meter2grid of one point, un-normalised, for a compile-time mapping kind (h <-> y, w <-> x, d <-> z)
+template <int MK>
+SO_DEVFN void so_m2g(const so_mapping &M, float x, float y, float z, float &gh, float &gw, float &gd, float &sh, float &sw,
+                     float &sd) {
+    if constexpr (MK == SO_MAP_UPSCALE) {
+        gh = so_axis_m2g_up<true>(M.h, M.uh, y, sh);
+        gw = so_axis_m2g_up<true>(M.w, M.uw, x, sw);
+        gd = so_axis_m2g_up<false>(M.d, M.ud, z, sd);
+    } else {
+        gh = so_axis_m2g(M.h, y, sh);
+        gw = so_axis_m2g(M.w, x, sw);
+        gd = so_axis_m2g(M.d, z, sd);
+    }
+}
+
 // grid index -> the coordinate F.grid_sample(align_corners=True) computes after the
 // reference's normalize (/(tot_len-1)), 2g-1 and un-normalise steps
 // (mappings.py:145-148, nerfacc_head/bev_nerf.py:103-113).
@@ -112,6 +150,20 @@ SO_DEVFN so_cell so_locate(const so_mapping &M, float x, float y, float z) {
     so_cell c = so_cell_of(gh, gw, gd);
     c.sh = sh; c.sw = sw; c.sd = sd;
     return c;
+}
+
+// so_locate for a compile-time mapping kind: SO_MAP_LINEAR is so_locate itself
+template <int MK>
+SO_DEVFN so_cell so_locate_k(const so_mapping &M, float x, float y, float z) {
+    if constexpr (MK == SO_MAP_LINEAR) {
+        return so_locate(M, x, y, z);
+    } else {
+        float gh, gw, gd, sh, sw, sd;
+        so_m2g<MK>(M, x, y, z, gh, gw, gd, sh, sw, sd);
+        so_cell c = so_cell_of(so_grid_coord(gh, M.h.tot_len), so_grid_coord(gw, M.w.tot_len), so_grid_coord(gd, M.d.tot_len));
+        c.sh = sh; c.sw = sw; c.sd = sd;
+        return c;
+    }
 }
 
 struct __attribute__((packed, aligned(4))) so_f2u { float x, y; };

@@ -4,8 +4,9 @@ Mirrors the interface of the reference's ``GridMeterMapping`` / ``LinearMapping`
 ``NonLinearMapping`` (model/encoder/bevformer/mappings.py:4-288): same constructor
 arguments, ``size_h/size_w/size_d``, ``grid2meter(grid)`` and
 ``meter2grid(meter, normalize=False)``.  ``to_abi()`` produces the ``so_mapping`` the
-HIP kernels consume (piece-wise linear only — every shipped config uses
-``nonlinear_mode='linear'``).
+HIP kernels consume: kind ``MAP_LINEAR`` for the piece-wise linear form (every shipped
+config), ``MAP_UPSCALE`` for ``'linear_upscale'`` (NeuSHead's default ``mapping_args``).
+``meter2grid_device`` is the kernels' own meter2grid (``selfocc_meter2grid``).
 """
 import torch
 
@@ -82,12 +83,26 @@ class LinearMapping:
         return m
 
 
+# the messages of so_validate_mapping (csrc/render_fwd.hip), word for word
+def _outer_msg(axis, outer):
+    return f"linear_upscale axis {axis}: outer cells must be >= 1 (got {outer:g})"
+
+
+def _inc_msg(axis, inc):
+    return f"linear_upscale axis {axis}: increase unit must be > 0 (got {inc:g}): the outer range must exceed outer * unit"
+
+
 class NonLinearMapping:
     """'linear_upscale': uniform inner cells, arithmetically growing outer cells
-    (mappings.py:199-288).  Host-side only (reference points of the encoder)."""
+    (mappings.py:199-288).  The encoders build their reference points from it; the render,
+    training and query kernels take it through ``to_abi()`` (kind ``MAP_UPSCALE``)."""
 
     def __init__(self, bev_inner=128, bev_outer=32, range_inner=51.2, range_outer=51.2,
                  z_inner=20, z_outer=10, z_ranges=[-5.0, 3.0, 11.0]):
+        # the reference divides by the outer cell counts (a ZeroDivisionError at 0) and by the increase units
+        for i, outer in ((0, bev_outer), (2, z_outer)):
+            if not outer >= 1:
+                raise ValueError(_outer_msg(i, outer))
         self.bev_inner, self.bev_outer = bev_inner, bev_outer
         self.range_inner, self.range_outer = range_inner, range_outer
         self.z_inner, self.z_outer, self.z_ranges = z_inner, z_outer, z_ranges
@@ -136,9 +151,34 @@ class NonLinearMapping:
         return torch.cat([wh[..., 1:2], wh[..., 0:1], d], dim=-1)
 
     def to_abi(self):
-        raise NotImplementedError(
-            "the HIP kernels implement nonlinear_mode='linear' only (every shipped SelfOcc config); "
-            "'linear_upscale' is host-side only")
+        """so_mapping of kind MAP_UPSCALE.  The constants are the reference's Python (double) expressions,
+        rounded once to float32 — what torch does with them when it meets a float32 tensor."""
+        def axis(inner, outer, rng_in, rng_out, off, start, tot):
+            a = abi.SoAxis()
+            a.size0, a.size1 = float(inner), float(outer)
+            a.range0, a.range1 = float(rng_in), float(rng_out)
+            a.off0, a.off1 = (float(inner), float(outer)) if off else (0.0, 0.0)
+            a.start, a.tot_len = float(start), int(tot)
+            return a
+
+        def up(unit, inc):
+            u = abi.SoUpscaleAxis()
+            c = 1. / 2 + unit / inc
+            u.unit, u.inc, u.c, u.c2 = unit, inc, c, c ** 2
+            return u
+        # sqrt(c^2 + 2 o / inc) and the divisions by inc need inc > 0 (the reference silently yields NaN / inf)
+        for i, inc in ((0, self.increase_unit), (1, self.increase_unit), (2, self.z_increase_unit)):
+            if not inc > 0:
+                raise ValueError(_inc_msg(i, inc))
+        z0, z1, z2 = self.z_ranges
+        m = abi.SoMapping()
+        m.kind = abi.MAP_UPSCALE
+        m.h = axis(self.bev_inner, self.bev_outer, self.range_inner, self.range_outer, True, 0.0, self.bev_size)
+        m.w = axis(self.bev_inner, self.bev_outer, self.range_inner, self.range_outer, True, 0.0, self.bev_size)
+        m.d = axis(self.z_inner, self.z_outer, z1 - z0, z2 - z1, False, z0, self.z_size)
+        m.uh = m.uw = up(self.hw_unit, self.increase_unit)
+        m.ud = up(self.z_unit, self.z_increase_unit)
+        return m
 
 
 class GridMeterMapping:
@@ -164,3 +204,22 @@ class GridMeterMapping:
 
     def to_abi(self):
         return self.mapping.to_abi()
+
+    def meter2grid_device(self, xyz, normalize=False):
+        """meter2grid on the GPU through the kernels' own mapping code (selfocc_meter2grid)."""
+        return meter2grid_device(self, xyz, normalize)
+
+
+def meter2grid_device(mapping, xyz, normalize=False):
+    """(..., 3) float32 metres (x, y, z) on a HIP device -> (..., 3) grid coordinates (h, w, d), computed by the same
+    device code the render / query kernels locate their samples with; bit-exact to the reference's meter2grid."""
+    from ._lib import lib, check, ptr, current_stream
+    if not xyz.is_cuda:
+        raise RuntimeError("meter2grid_device needs a CUDA(HIP) tensor: there is no CPU fallback")
+    assert xyz.shape[-1] == 3 and xyz.dtype == torch.float32, "xyz: (..., 3) float32"
+    x = xyz.contiguous()
+    out = torch.empty_like(x)
+    m = mapping.to_abi()
+    check(lib().selfocc_meter2grid(m, ptr(x), x.numel() // 3, 1 if normalize else 0, ptr(out), current_stream(x.device)),
+          "selfocc_meter2grid")
+    return out

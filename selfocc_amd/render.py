@@ -25,7 +25,7 @@ class SDFVolume:
     The reference materialises (1, 1 + color_dims, H, W, D) instead
     (nerfacc_head/bev_nerf.py:74-95); ``from_reference_layout`` converts.
     """
-    mapping: object            # GridMeterMapping / LinearMapping (has to_abi())
+    mapping: object            # GridMeterMapping / LinearMapping / NonLinearMapping (has to_abi())
     sdf: torch.Tensor
     feat: Optional[torch.Tensor] = None
     n_rgb: int = 0
@@ -218,8 +218,9 @@ def render_rays(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, per_sample=F
     a, out, _keep = marshal_render_args(vol, rays, cfg, per_sample=per_sample,
                                         want_grad_samples=want_grad_samples, t_rand=t_rand,
                                         bkgd_rays=bkgd_rays, outputs=outputs)
-    if cfg.brick and not cfg.exact and rays.n_rays * cfg.n_samples >= 16 * vol.sdf.numel():
-        a.sdf_brick = ptr(_brick_workspace(vol.sdf))   # the re-pack only pays off for large ray batches
+    # the re-pack only pays off for large ray batches; the 'linear_upscale' mapping takes the canonical route, which reads no brick
+    if cfg.brick and not cfg.exact and a.map.kind == abi.MAP_LINEAR and rays.n_rays * cfg.n_samples >= 16 * vol.sdf.numel():
+        a.sdf_brick = ptr(_brick_workspace(vol.sdf))
     check(lib().selfocc_render_fwd(a, current_stream(vol.sdf.device)), "selfocc_render_fwd")
     return out
 
