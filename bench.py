@@ -14,11 +14,14 @@ frames, every rank marches one frame's worth of rays (rays are independent units
 collective) and the ranks all-reduce the scalar rendered-depth loss over RCCL each step, as
 north_star describes => weak scaling.  `--shard rays`: ONE frame is split into
 row blocks over the ranks (selfocc_amd.dist.shard_rays, the mode NeuSHead(ray_shard=True) runs) =>
-strong scaling; at N > 1 the default run also reports it under "strong_scaling".
+strong scaling; at N > 1 a `--full` run also reports it under "strong_scaling".
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the render
-kernel is the only kernel in a step); `cpu_baseline` times the torch-op port of the
-reference's CPU render path (oracle/torch_port.py) on a bounded sample, rank 0, N=1.
+Prints ONE JSON line (rank 0).  A plain run sets up, pre-heats, warms up, times the K steps, writes --dump-outputs and
+prints the headline.  Everything else moves behind `--full`, after the timed steps: `roofline` is for the dominant
+kernel (the render kernel is the only kernel in a step); `cpu_baseline` times the torch-op port of the
+reference's CPU render path (oracle/torch_port.py) on a bounded sample, rank 0, N=1; parity with the C oracle, the
+other channel / precision / path variants, the GPU-torch baseline, the shipped configs' hot path, the MSDA / Linear /
+backward rooflines; the tables that do not fit the line go to bench_out/bench_detail.json.
 """
 import argparse
 import json
@@ -95,6 +98,81 @@ def dump_outputs(path, out, seed=0):
     return {"dir": path, "arrays": sorted(host), "rays": n if rows is None else int(rows.numel()), "of_rays": n}
 
 
+def kernel_roofline(args, vol, rays, cfg, out, n_rays, n_rgb, n_sem):
+    """--full: roofline of the dominant kernel, from launches of its own after the timed steps (HIP events on the launch
+    stream, kernel only) and the PMC record of profiles/pmc_traffic.json when it matches the kernel's source"""
+    from selfocc_amd.render import render_rays
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    torch.cuda.synchronize()
+    for e0, e1 in evs:
+        e0.record()
+        render_rays(vol, rays, cfg, outputs=out)
+        e1.record()
+    torch.cuda.synchronize()
+    per_launch = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
+    kern_ms = sum(per_launch) / len(per_launch)
+    alg_bytes, vol_bytes, per_ray_out = algorithmic_bytes(vol, n_rays, n_sem)
+    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+    touch_bytes = n_rays * cfg.n_samples * 8 * (4 + (0 if vol.feat is None else (n_rgb + n_sem) * vol.feat.element_size()))
+    roofline = {
+        "bound": "hbm", "kernel": f"render_fwd_pixgrid<NF={vol.feat.shape[3] if vol.feat is not None else 0}>", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
+        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5),
+        "traffic": None,  # rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE per launch: see profiles/ (filled by hand per round)
+        "kernel_ms": round(kern_ms, 4),
+        "kernel_ms_min_median_max": [round(per_launch[0], 4), round(per_launch[len(per_launch) // 2], 4), round(per_launch[-1], 4)],
+        "algorithmic_bytes": alg_bytes,
+        "note": ("compulsory bytes = volume once + per-ray outputs; the march is gather/VALU bound "
+                 "(volume <= 64 MB sits in L2 / Infinity Cache), touched bytes through L1 per launch = %d" % touch_bytes),
+        "touch_GBps": round(touch_bytes / (kern_ms * 1e-3) / 1e9, 1),
+    }
+    # HBM-side bytes per launch measured with rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes,
+    # scripts/pmc.sh); committed per round under profiles/ because PMC collection cannot run inside bench.py
+    pmc_file = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(pmc_file):
+        key = f"c{args.channels}_{args.feat_dtype}_{'exact' if args.exact else 'fast'}"
+        rec = json.load(open(pmc_file)).get(key)
+        if rec and rec.get("kernel_source_sha1") != kernel_source_hash():
+            # counters taken on an older build of the kernel say nothing about this one
+            roofline["traffic_note"] = (f"profiles/pmc_traffic.json[{key}] was measured on kernel source "
+                                        f"{rec.get('kernel_source_sha1')} != current {kernel_source_hash()}: not reported")
+            rec = None
+        if rec:
+            roofline["traffic"] = rec["traffic_bytes"]
+            roofline["traffic_note"] = rec["note"]
+            if "valu_wave_insts" in rec:   # secondary, compute-side view of the same kernel
+                peak = 256 * 4 * 32 * 2.4e9 / 1e12          # fp32 vector lane-ops / s (157.3 TFLOP/s = 2 flop x this)
+                ach = rec["valu_wave_insts"] * 64 / (kern_ms * 1e-3) / 1e12
+                roofline["valu"] = {"achieved_Tlaneops": round(ach, 2), "peak_Tlaneops": round(peak, 2),
+                                    "frac": round(ach / peak, 3),
+                                    "note": "SQ_INSTS_VALU x 64 lanes / kernel time vs 256 CU x 4 SIMD x 32 lanes x 2.4 GHz"}
+                roofline["valu_frac"] = round(ach / peak, 3)
+            # The OPERATIVE bound of the march, from per-unit utilisations of the same PMC session — not from GRBM_TA_BUSY, which
+            # counts the cycles in which ANY of the 256 texture addressers is busy (0.95 on this kernel; kept as
+            # `ta_any_busy_frac` for continuity) and over-states the load (round-4 review):
+            #   ta_util        = TA_BUSY_avr / (GRBM_GUI_ACTIVE / 8 XCDs)     the AVERAGE addresser's busy share of the kernel
+            #   ta_unit_util   = TA_TA_BUSY_sum / 256 TAs / the same cycles
+            #   l1_gather_frac = bytes gathered through the vector L1 / (64 B/clk/CU x 256 CUs x 2.4 GHz = 39.3 TB/s)
+            # `frac` above stays the HBM number the contract asks for (the volume sits in L2 / MALL).
+            if rec.get("ta_busy_cycles") and rec.get("gui_active_cycles"):
+                roofline["ta_any_busy_frac"] = round(rec["ta_busy_cycles"] / rec["gui_active_cycles"], 3)
+            if rec.get("ta_busy_avr") and rec.get("gui_active_cycles_ta_pass"):
+                per_xcd = rec["gui_active_cycles_ta_pass"] / 8.0
+                roofline["ta_util"] = round(rec["ta_busy_avr"] / per_xcd, 3)
+                if rec.get("ta_ta_busy_sum"):
+                    roofline["ta_unit_util"] = round(rec["ta_ta_busy_sum"] / 256.0 / per_xcd, 3)
+            if rec.get("tcp_total_cache_accesses"):
+                roofline["l1_accesses_per_launch"] = rec["tcp_total_cache_accesses"]
+    roofline["l1_gather_frac"] = round(roofline["touch_GBps"] / L1_PEAK_GBPS, 3)
+    utils = {"TA": roofline.get("ta_util"), "L1": roofline["l1_gather_frac"], "VALU": roofline.get("valu_frac")}
+    if utils["TA"] is not None:
+        top = max((v, k) for k, v in utils.items() if v is not None)
+        # a pipe is "the bound" only when it is (nearly) saturated; otherwise the kernel is limited by instruction issue and
+        # gather latency at the occupancy its registers allow, and the largest utilisation says how far from that pipe's roof
+        roofline["bound_operative"] = top[1] if top[0] >= 0.8 else "issue/latency"
+        roofline["bound_operative_util"] = {k: v for k, v in utils.items() if v is not None}
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -107,6 +185,11 @@ def main():
                          "eval_depth.py path the reference's README quotes) | 4 sdf+rgb | 25 sdf+rgb+21 sem (nuscenes_occ)")
     ap.add_argument("--feat-dtype", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--exact", action="store_true", help="canonical IEEE path (bit-exact with the oracle)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: the render kernel's "
+                         "roofline, parity with the C oracle, CPU / GPU-torch baselines, the other variants, the hot path, the "
+                         "MSDA / Linear / backward rooflines, strong scaling at N > 1 (--no-cpu-baseline, --no-extras and "
+                         "--no-hotpath leave parts out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--shard", default="frames", choices=["frames", "rays"],
@@ -218,78 +301,10 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = rays_per_step_all_ranks * args.steps / elapsed
 
-    # ---- roofline of the dominant kernel: HIP events on the launch stream, kernel only ----
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    torch.cuda.synchronize()
-    for e0, e1 in evs:
-        e0.record()
-        render_rays(vol, rays, cfg, outputs=out)
-        e1.record()
-    torch.cuda.synchronize()
-    per_launch = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
-    kern_ms = sum(per_launch) / len(per_launch)
-    alg_bytes, vol_bytes, per_ray_out = algorithmic_bytes(vol, n_rays, n_sem)
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-    touch_bytes = n_rays * cfg.n_samples * 8 * (4 + (0 if vol.feat is None else (n_rgb + n_sem) * vol.feat.element_size()))
-    roofline = {
-        "bound": "hbm", "kernel": f"render_fwd_pixgrid<NF={vol.feat.shape[3] if vol.feat is not None else 0}>", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
-        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5),
-        "traffic": None,  # rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE per launch: see profiles/ (filled by hand per round)
-        "kernel_ms": round(kern_ms, 4),
-        "kernel_ms_min_median_max": [round(per_launch[0], 4), round(per_launch[len(per_launch) // 2], 4), round(per_launch[-1], 4)],
-        "algorithmic_bytes": alg_bytes,
-        "note": ("compulsory bytes = volume once + per-ray outputs; the march is gather/VALU bound "
-                 "(volume <= 64 MB sits in L2 / Infinity Cache), touched bytes through L1 per launch = %d" % touch_bytes),
-        "touch_GBps": round(touch_bytes / (kern_ms * 1e-3) / 1e9, 1),
-    }
-    # HBM-side bytes per launch measured with rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes,
-    # scripts/pmc.sh); committed per round under profiles/ because PMC collection cannot run inside bench.py
-    pmc_file = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc_file):
-        key = f"c{args.channels}_{args.feat_dtype}_{'exact' if args.exact else 'fast'}"
-        rec = json.load(open(pmc_file)).get(key)
-        if rec and rec.get("kernel_source_sha1") != kernel_source_hash():
-            # counters taken on an older build of the kernel say nothing about this one
-            roofline["traffic_note"] = (f"profiles/pmc_traffic.json[{key}] was measured on kernel source "
-                                        f"{rec.get('kernel_source_sha1')} != current {kernel_source_hash()}: not reported")
-            rec = None
-        if rec:
-            roofline["traffic"] = rec["traffic_bytes"]
-            roofline["traffic_note"] = rec["note"]
-            if "valu_wave_insts" in rec:   # secondary, compute-side view of the same kernel
-                peak = 256 * 4 * 32 * 2.4e9 / 1e12          # fp32 vector lane-ops / s (157.3 TFLOP/s = 2 flop x this)
-                ach = rec["valu_wave_insts"] * 64 / (kern_ms * 1e-3) / 1e12
-                roofline["valu"] = {"achieved_Tlaneops": round(ach, 2), "peak_Tlaneops": round(peak, 2),
-                                    "frac": round(ach / peak, 3),
-                                    "note": "SQ_INSTS_VALU x 64 lanes / kernel time vs 256 CU x 4 SIMD x 32 lanes x 2.4 GHz"}
-                roofline["valu_frac"] = round(ach / peak, 3)
-            # The OPERATIVE bound of the march, from per-unit utilisations of the same PMC session — not from GRBM_TA_BUSY, which
-            # counts the cycles in which ANY of the 256 texture addressers is busy (0.95 on this kernel; kept as
-            # `ta_any_busy_frac` for continuity) and over-states the load (round-4 review):
-            #   ta_util        = TA_BUSY_avr / (GRBM_GUI_ACTIVE / 8 XCDs)     the AVERAGE addresser's busy share of the kernel
-            #   ta_unit_util   = TA_TA_BUSY_sum / 256 TAs / the same cycles
-            #   l1_gather_frac = bytes gathered through the vector L1 / (64 B/clk/CU x 256 CUs x 2.4 GHz = 39.3 TB/s)
-            # `frac` above stays the HBM number the contract asks for (the volume sits in L2 / MALL).
-            if rec.get("ta_busy_cycles") and rec.get("gui_active_cycles"):
-                roofline["ta_any_busy_frac"] = round(rec["ta_busy_cycles"] / rec["gui_active_cycles"], 3)
-            if rec.get("ta_busy_avr") and rec.get("gui_active_cycles_ta_pass"):
-                per_xcd = rec["gui_active_cycles_ta_pass"] / 8.0
-                roofline["ta_util"] = round(rec["ta_busy_avr"] / per_xcd, 3)
-                if rec.get("ta_ta_busy_sum"):
-                    roofline["ta_unit_util"] = round(rec["ta_ta_busy_sum"] / 256.0 / per_xcd, 3)
-            if rec.get("tcp_total_cache_accesses"):
-                roofline["l1_accesses_per_launch"] = rec["tcp_total_cache_accesses"]
-    roofline["l1_gather_frac"] = round(roofline["touch_GBps"] / L1_PEAK_GBPS, 3)
-    utils = {"TA": roofline.get("ta_util"), "L1": roofline["l1_gather_frac"], "VALU": roofline.get("valu_frac")}
-    if utils["TA"] is not None:
-        top = max((v, k) for k, v in utils.items() if v is not None)
-        # a pipe is "the bound" only when it is (nearly) saturated; otherwise the kernel is limited by instruction issue and
-        # gather latency at the occupancy its registers allow, and the largest utilisation says how far from that pipe's roof
-        roofline["bound_operative"] = top[1] if top[0] >= 0.8 else "issue/latency"
-        roofline["bound_operative_util"] = {k: v for k, v in utils.items() if v is not None}
+    roofline = kernel_roofline(args, vol, rays, cfg, out, n_rays, n_rgb, n_sem) if args.full else None
 
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         def time_variant(c, dt, exact, k=10, **kw):
             nr, ns = {1: (0, 0), 4: (3, 0), 25: (3, 21)}[c]
             v = sy.make_volume(name, n_rgb=nr, n_sem=ns, feat_dtype=dt, seed=0).to(dev)
@@ -318,7 +333,7 @@ def main():
     # ---- parity of the timed configuration: the C oracle (float32 canonical order, OpenMP) on EVERY ray of the
     # frame, against the outputs of the very launch that was timed (oracle/ is used as the checker only) ----
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle
         c0 = time.perf_counter()
         ref = oracle.render_fwd(vol_cpu, rays_cpu, cfg)
@@ -350,7 +365,7 @@ def main():
     # (F.grid_sample + autograd gradient + NeuS compositing, oracle/torch_port.py) executed with stock
     # PyTorch-ROCm ops on the MI355X in README-sized 90 000-ray chunks (neus_head.py:329-385).  Baseline only. ----
     gpu_torch_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import torch_port as tp
         ex = sy.explicit_rays(rays_cpu)
         n_base = min(n_rays, 8 * 90_000)
@@ -371,7 +386,7 @@ def main():
         torch.cuda.empty_cache()
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the reference's CPU render path (torch F.grid_sample + NeuS compositing) on the same frame, in
         # README-sized chunks of 90 000 rays (neus_head.py:329-385) until ~12 s of CPU work are spent;
         # oracle/ is used here ONLY as the timed baseline
@@ -403,7 +418,7 @@ def main():
             cpu_baseline["c_oracle_threads"] = os.cpu_count()
 
     hot_path = hot_path_detail = None
-    if rank == 0 and world == 1 and not args.no_hotpath and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_hotpath and not args.no_extras:
         # the rest of the hot path: ALL SEVEN shipped experiment configs (scripts/shipped_cfg/*.json = config/**/*.py dumped by
         # scripts/dump_shipped_configs.py), each built through the registries at its shipped shapes — one training iteration
         # (forward, the config's own loss list, backward) and the evaluation entry the reference's docs pair with it, with the
@@ -427,7 +442,7 @@ def main():
                         "eval_entry": {k: v["eval"]["entry"] for k, v in hot_path_detail.items() if isinstance(v, dict) and "eval" in v}}
 
     roofline_msda = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # the lifter's kernels, where an HBM roofline is meaningful: algorithmic bytes / HIP-event time
         import subprocess
         torch.cuda.empty_cache()
@@ -440,7 +455,7 @@ def main():
             roofline_msda = {"error": repr(e)[:300]}
 
     roofline_linear = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # the encoder's projections (selfocc_linear_fwd): float32 MFMA rate against its peak, next to hipBLASLt
         import subprocess
         torch.cuda.empty_cache()
@@ -457,7 +472,7 @@ def main():
     # round as profiles/pmc_bwd.json next to the text summary it was made from)
     roofline_bwd = None
     bwd_file = os.path.join(ROOT, "profiles", "pmc_bwd.json")
-    if rank == 0 and world == 1 and os.path.exists(bwd_file):
+    if args.full and rank == 0 and world == 1 and os.path.exists(bwd_file):
         rec = json.load(open(bwd_file))
         # algorithmic bytes per launch at the nuscenes_occ training shape: the gradient the kernel produces, written once
         alg = {"render_bwd": 257 * 257 * 25 * 25 * 4,                       # d L / d (sdf + 24-channel feature) volume
@@ -487,7 +502,7 @@ def main():
                 roofline_bwd[name]["write_MB_by_kernel"] = {k.split("<")[0]: round(v["write_kb"] * 1024 / 1e6, 1) for k, v in ks.items()}
 
     strong = None
-    if world > 1 and not split:
+    if args.full and world > 1 and not split:
         # the same ranks, ONE frame split into row blocks (SURVEY cfg3), after the timed region
         f0 = sy.make_rays(name, seed=0)
         v0 = sy.make_volume(name, n_rgb=n_rgb, n_sem=n_sem, feat_dtype=fdt, seed=0).to(dev)
@@ -532,11 +547,8 @@ def main():
 
     if rank == 0:
         # ---- the printed line stays under ~6 KB (the driver keeps `config`, `roofline`, `cpu_baseline` whole and the END of the
-        # line): per-row / per-shape / per-stage tables go to gpurun_out/bench_detail.json; the parity of the timed frame and the
-        # seven shipped configs' totals are in `config` (parsed) AND close the line (kept tail) ----
-        detail = {"roofline_msda": roofline_msda, "roofline_linear": roofline_linear, "roofline_bwd": roofline_bwd,
-                  "hot_path": hot_path_detail, "parity": parity, "extras": extras, "gpu_torch_baseline": gpu_torch_baseline,
-                  "cpu_baseline": cpu_baseline, "roofline": dict(roofline)}
+        # line): with --full, per-row / per-shape / per-stage tables go to bench_out/bench_detail.json; the parity of the timed
+        # frame and the seven shipped configs' totals are in `config` (parsed) AND close the line (kept tail) ----
         cfg_out = {"workload": "BASELINE configs[1]: 6 cams x 450x800 rays, 128 samples/ray, volume 200x200x16",
                    "volume_channels": args.channels, "feat_storage": args.feat_dtype,
                    "rays_per_step_per_gpu": n_rays, "inv_s": args.inv_s, "preheat_steps": args.preheat,
@@ -553,15 +565,19 @@ def main():
                                                                      "low_acc_weighted_depth_err_over_far")}
         if hot_path and "error" not in hot_path:
             cfg_out["hot_path_ms"] = {"train": hot_path["train"], "eval": hot_path["eval"]}
-        # `roofline`: the contract's fields + the per-unit view; the long notes move to the detail file
-        roof = {k: v for k, v in roofline.items() if k not in ("note", "traffic_note", "valu", "kernel_ms_min_median_max", "l1_accesses_per_launch")}
         line = {
             "metric": "rendered rays/sec (6-cam 450x800, 128 samples/ray)",
             "value": round(value, 1), "unit": "rays/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
             "scaling": "strong" if split else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": cfg_out, "roofline": roof, "cpu_baseline": cpu_baseline, "ranks_seen": ranks_seen,
+            "config": cfg_out,
         }
+        if args.full:
+            # `roofline`: the contract's fields + the per-unit view; the long notes move to the detail file
+            line["roofline"] = {k: v for k, v in roofline.items()
+                                if k not in ("note", "traffic_note", "valu", "kernel_ms_min_median_max", "l1_accesses_per_launch")}
+            line["cpu_baseline"] = cpu_baseline
+        line["ranks_seen"] = ranks_seen
         if last_out is not None:
             line["outputs_dumped"] = dump_outputs(args.dump_outputs, last_out)
         if world > 1:   # the all-reduced quantity itself: mean rendered depth over every rank's rays (same on all ranks)
@@ -596,13 +612,17 @@ def main():
             line["parity"] = par_c
         if hot_path:
             line["hot_path"] = hot_path
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_detail.json"), "w") as fd:
-                json.dump({"line": line, "detail": detail}, fd, indent=1)
-            line["detail_file"] = "gpurun_out/bench_detail.json"
-        except OSError:
-            pass
+        if args.full:
+            detail = {"roofline_msda": roofline_msda, "roofline_linear": roofline_linear, "roofline_bwd": roofline_bwd,
+                      "hot_path": hot_path_detail, "parity": parity, "extras": extras, "gpu_torch_baseline": gpu_torch_baseline,
+                      "cpu_baseline": cpu_baseline, "roofline": dict(roofline)}
+            try:
+                os.makedirs(os.path.join(ROOT, "bench_out"), exist_ok=True)
+                with open(os.path.join(ROOT, "bench_out", "bench_detail.json"), "w") as fd:
+                    json.dump({"line": line, "detail": detail}, fd, indent=1)
+                line["detail_file"] = "bench_out/bench_detail.json"
+            except OSError:
+                pass
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 R=$GRAFT_REPO_ROOT; mkdir -p $R/gpurun_out; cd /tmp; export TMPDIR=/tmp
 for tag in bench eval train; do
   case $tag in
-    bench) CMD="python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-hotpath";;
+    bench) CMD="python $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-hotpath";;
     eval)  CMD="python $R/scripts/bench_hotpath_eval.py";;
     train) CMD="python $R/scripts/bench_hotpath_train.py";;
   esac

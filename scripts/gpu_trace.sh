@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 --kernel-trace --stats of one command; top kernels -> gpurun_out/<tag>_kernel_trace.txt
-#   gpurun -- 'bash scripts/gpu_trace.sh r3_x_bench python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-hotpath'
+#   bash scripts/gpu_trace.sh x_bench python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-hotpath
 R=${GRAFT_REPO_ROOT:-$(pwd)}; tag=$1; shift
 mkdir -p $R/gpurun_out; cd /tmp; export TMPDIR=/tmp
 rm -rf /tmp/prof_$tag

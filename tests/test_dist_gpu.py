@@ -358,6 +358,25 @@ def test_bench_two_ranks_on_one_gpu(shard):
     assert abs(line["value"] - per_step / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-3
 
 
+def test_bench_full_two_ranks_reports_strong_scaling():
+    """`--full` at N = 2 (frame per rank, both ranks on cuda:0 over gloo): after the timed steps, the same ranks time ONE
+    frame split into row blocks and the line carries it as `strong_scaling`, next to the render kernel's roofline."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, SELFOCC_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--preheat", "2", "--full", "--no-cpu-baseline", "--no-extras", "--no-hotpath"]
+    r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["roofline"]["kernel_ms"] > 0
+    strong = line["strong_scaling"]
+    assert strong["rays_per_s"] > 0 and strong["rays_per_rank"] == 6 * 450 * 800 // 2
+
+
 def test_bench_plain_python_starts_its_own_ranks():
     """`python bench.py --gpus 2` WITHOUT torchrun (round-4 review: it silently ran one rank and printed n_gpus = 1): bench.py
     re-executes itself under torch.distributed.run, and the one line it prints has n_gpus == --gpus."""
