@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SELFOCC_ABI_VERSION 34
+#define SELFOCC_ABI_VERSION 35
 
 int selfocc_abi_version(void);
 const char *selfocc_last_error(void);
@@ -238,117 +238,104 @@ size_t selfocc_render_bwd_ws_bytes(const so_render_bwd_args *args);
  * model/encoder/bevformer/attention/image_cross_attention.py:340-342 and
  * model/encoder/tpvformer/attention/cross_view_hybrid_attention.py:111-113.
  *
- *   value   (bs, nv, heads, d)            float32
- *   shapes  (L, 2) int32 [H_l, W_l]       starts (L) int32
- *   loc     (bs, nq, heads, L, P, 2)      (x, y) in [0,1]
- *   attw    (bs, nq, heads, L, P)
- *   out     (bs, nq, heads * d)
+ *   out[b,q,h*d+c] = sum_{l,p} attw[b,q,h,l,p] * bilinear(value_l[b, :, h, c], loc[b,q,h,l,p])
+ *
+ * Three forms share one argument struct (fields a form does not name are ignored):
+ *   SO_MSDA_PLAIN  mmcv's op: value (bs,nv,heads,d) float32, loc (bs,nq,heads,L,P,2) (x, y) in [0,1],
+ *                  attw (bs,nq,heads,L,P), out (bs,nq,heads*d); d = 4, 8, 16 or 32.
+ *   SO_MSDA_FUSED  the reference's prologue inside the kernels (softmax over the L*P logits of a (query, head);
+ *                  loc = ref + off / (W_l, H_l); image_cross_attention.py:314-328, cross_view_hybrid_attention.py:88-99),
+ *                  in both directions: sampling locations / attention weights are never materialised.
+ *                  off_raw (bs,nq,heads,L,P,2), logits (bs,nq,heads,L*P), out (bs,nq,heads*d).
+ *   SO_MSDA_CROSS  the camera loop: BEVCrossAttention's re-batch -> offset / weight linears -> MSDA -> scatter-add ->
+ *                  divide-by-count (bevformer/attention/image_cross_attention.py:90-136) as ONE launch per direction.
+ *                  The offsets and logits depend on the query only; each (query, head) loops over the cameras that
+ *                  see it, in camera order:
+ *                    out[q] = sum_{cam: vis[cam][q]} msda(value[cam], ref[cam][q] + off[q] / (W_l, H_l), softmax(logits[q]))
+ *                             / max(#visible cams, 1)
+ *                  value (cams,nv,heads,d), off_raw (nq,heads,L,P,2), logits (nq,heads,L*P), out (nq,heads*d);
+ *                  batch size 1 (as the reference's masks).
+ * FUSED and CROSS: d = 8, 16 or 32 (bfloat16 value: 16 only), L*P <= 256.
  * ---------------------------------------------------------------------------------- */
-int selfocc_msda_fwd(const float *value, const int32_t *shapes, const int32_t *starts,
-                     const float *loc, const float *attw, float *out,
-                     int32_t bs, int32_t nv, int32_t nq, int32_t heads, int32_t d,
-                     int32_t L, int32_t P, void *stream);
+enum { SO_MSDA_PLAIN = 0, SO_MSDA_FUSED = 1, SO_MSDA_CROSS = 2 };
 
-/* Layout of `value` (and of `g_value`) for the fused / camera-loop entry points — the ones this repo's own encoder
- * modules call, so the layout is theirs to choose; selfocc_msda_fwd / _bwd / _bwd_banded keep mmcv's.
+/* Layout of `value` (and of `g_value`) for the fused / camera-loop forms — the ones this repo's own encoder
+ * modules call, so the layout is theirs to choose; the plain form keeps mmcv's.
  *   SO_VALUE_PIXEL_MAJOR (bs, nv, heads, d): mmcv.  A 128-byte cache line holds one pixel of TWO heads.
  *   SO_VALUE_HEAD_MAJOR  (bs, heads, nv, d): a line holds two horizontally adjacent pixels of ONE head, i.e. usually
  *   both x-corners of a bilinear footprint; the gathers of the hw-plane cross-attention run 0.34 ms instead of 0.50. */
 enum { SO_VALUE_PIXEL_MAJOR = 0, SO_VALUE_HEAD_MAJOR = 1 };
 
-/* value_dtype of the same entry points: SO_DTYPE_F32, or SO_DTYPE_BF16 = bfloat16 STORAGE of `value` (the arithmetic
- * is float32 on the exactly widened values; g_value stays float32): halves the 64-byte corner segments the gathers move.
- * Results equal the float32 kernels run on bf16-rounded values; against unrounded float32 values the relative error is
- * the bf16 rounding of `value`, ~2^-9 (opt-in: BASELINE configs[1] allows bf16 storage, the reference computes MSDA in f32). */
+typedef struct so_msda_args {
+    int32_t form;           /* SO_MSDA_*                                                                    */
+    int32_t bs;             /* batch size; the number of cameras for SO_MSDA_CROSS (>= 1)                   */
+    int32_t nv;             /* pixels of all levels of one value map                                        */
+    int32_t nq;             /* queries                                                                      */
+    int32_t heads, d;       /* heads, channels per head                                                     */
+    int32_t L, P;           /* levels, sampling points per level                                            */
+    int32_t value_layout;   /* SO_VALUE_* (FUSED / CROSS; PLAIN: pixel-major)                               */
+    int32_t value_dtype;    /* SO_DTYPE_F32, or SO_DTYPE_BF16 (FUSED / CROSS) = bfloat16 STORAGE of `value`: the
+                               arithmetic is float32 on the exactly widened values, g_value stays float32; halves the
+                               64-byte corner segments the gathers move.  Results equal the float32 kernels run on
+                               bf16-rounded values; against unrounded values the relative error is ~2^-9 (opt-in:
+                               BASELINE configs[1] allows bf16 storage, the reference computes MSDA in f32)       */
+    int32_t value_stride;   /* CROSS forward: floats between consecutive pixels of a pixel-major `value` (0 = dense,
+                               heads*d; else a multiple of 4 >= heads*d): lets `value` be a column block of a wider
+                               matrix, e.g. the three TPV planes' value projections computed by ONE GEMM with
+                               N = 3 * heads * d.  0 everywhere else                                          */
+    int32_t ref_kind;       /* FUSED: 0: ref (bs,nq,L,2)   1: ref (bs,nq,P,2)   2: ref (bs,nq,L,P,2)           */
+    int32_t ol_stride;      /* FUSED / CROSS (ABI 32): floats between consecutive QUERY rows of off_raw and logits (and of
+                               g_off / g_logits).  0 = the dense tensors above.  3 * heads * L * P (or more, even) = ONE row
+                               per query [heads*L*P*2 raw offsets | heads*L*P logits], i.e. the output of the
+                               `sampling_offsets` and `attention_weights` Linears computed as ONE projection with the two
+                               weights stacked (image_cross_attention.py:296-312 reads the same `query` twice); `logits` =
+                               `off_raw` + 2 * heads * L * P then (8-byte aligned), and the backward writes the gradient of
+                               that merged row, which is what ONE input-gradient and ONE weight-gradient pass of the stacked
+                               Linear consume                                                                  */
+    int32_t g_value_stride; /* FUSED / CROSS backward (ABI 32): 0 = g_value has the layout of `value`.  > 0 (>= heads*d) =
+                               g_value is written PIXEL-major into rows of that many floats — (bs, nv) rows, this op's
+                               heads * d channels starting at the pointer —, i.e. straight into a column block of the
+                               row-major gradient of the (stacked) value projection: no head-major -> row-major
+                               transposing copy before its weight- / input-gradient passes                     */
+    const void *value;      /* float32 or bfloat16 per value_dtype                                          */
+    const int32_t *shapes;  /* (L, 2) [H_l, W_l]                                                            */
+    const int32_t *starts;  /* (L) first pixel of each level                                                */
+    const int32_t *host_shapes; /* HOST copy of `shapes` for the banded backward's work decomposition; the
+                               plain backward without it takes the global-atomic scatter                      */
+    const float *loc;       /* PLAIN: (bs,nq,heads,L,P,2)                                                   */
+    const float *attw;      /* PLAIN: (bs,nq,heads,L,P)                                                     */
+    const float *ref;       /* FUSED: per ref_kind;  CROSS: (cams,nq,P,2)                                   */
+    const uint8_t *vis;     /* CROSS: (cams,nq), non-zero = the camera sees the query                       */
+    const float *off_raw;   /* FUSED / CROSS: raw sampling-offset linear output                             */
+    const float *logits;    /* FUSED / CROSS: attention logits before the softmax                           */
+    float *out;             /* forward output                                                               */
+    /* --- backward --------------------------------------------------------------------------------------------- */
+    const float *g_out;     /* gradient of `out` (CROSS: of the camera MEAN)                                */
+    float *g_value;         /* zero-initialised by the caller (accumulated); CROSS: sums over the visible cameras / count */
+    float *g_loc, *g_attw;  /* PLAIN                                                                        */
+    float *g_off, *g_logits; /* FUSED / CROSS: gradients w.r.t. the RAW linear outputs, laid out as off_raw / logits:
+                               g_off = (d out / d loc) / (W_l, H_l), g_logits = aw (g_aw - sum aw g_aw) (softmax backward),
+                               with the softmax / sampling locations recomputed in registers                   */
+    /* Banded (output-stationary) scatter of grad_value (PLAIN with host_shapes; always for FUSED / CROSS): the
+     * sampling points are counting-sorted by (batch, head, level, band of rows); a block owns one band of one level's
+     * map in LDS and adds the points of its list with ds_add_f64 — no global atomics in the scatter, grad_value
+     * accumulated in double and rounded once per list segment (same results as the atomic scatter up to summation
+     * order).  Needs host_shapes (L <= 8) and a 16-byte aligned device workspace of selfocc_msda_ws_bytes() bytes
+     * (26 bytes per sampling point: a 2-byte row key, a 16-byte record, two 4-byte list slots; plus 28 KB of counters
+     * per (batch, head, level); contents undefined before and after).  PLAIN falls back to the atomic scatter when
+     * selfocc_msda_banded_supported() is 0; FUSED / CROSS then fail.                                             */
+    void *workspace;
+    uint64_t workspace_bytes;
+} so_msda_args;
 
-/* Inference form with the reference's prologue fused in (softmax over the L*P logits of a
- * (query, head); loc = ref + off / (W_l, H_l); image_cross_attention.py:314-328,
- * cross_view_hybrid_attention.py:88-99): the sampling_locations / attention_weights tensors are
- * never materialised.   off_raw (bs,nq,heads,L,P,2)  logits (bs,nq,heads,L*P)
- *   ref_kind 0: ref (bs,nq,L,2)   1: ref (bs,nq,P,2)   2: ref (bs,nq,L,P,2)        L*P <= 256 */
-int selfocc_msda_fused_fwd(const void *value, const int32_t *shapes, const int32_t *starts,
-                           const float *ref, int32_t ref_kind, const float *off_raw, const float *logits,
-                           float *out, int32_t bs, int32_t nv, int32_t nq, int32_t heads, int32_t d,
-                           int32_t L, int32_t P, int32_t value_layout, int32_t value_dtype, int32_t ol_stride, void *stream);
-/* ol_stride (ABI 32; the four fused / camera-loop entry points): floats between consecutive QUERY rows of off_raw and logits
- * (and of g_off / g_logits in the backward forms).  0 = the dense tensors described above.  3 * heads * L * P (or more, even)
- * = ONE row per query [heads*L*P*2 raw offsets | heads*L*P logits], i.e. the output of the `sampling_offsets` and
- * `attention_weights` Linears computed as ONE projection with the two weights stacked (image_cross_attention.py:296-312
- * reads the same `query` twice); `logits` = `off_raw` + 2 * heads * L * P then, and the backward forms write the gradient
- * of that merged row, which is what ONE input-gradient and ONE weight-gradient pass of the stacked Linear consume.
- * g_value_stride (ABI 32; the two backward forms): 0 = g_value has the layout of `value`.  > 0 = g_value is written PIXEL-major
- * into rows of that many floats — (bs | cams, nv) rows, this op's heads * d channels starting at the pointer —, i.e. straight
- * into a column block of the row-major gradient of the (stacked) value projection: no head-major -> row-major transposing copy
- * before its weight- / input-gradient passes.  The rows must be zero-initialised by the caller like g_value. */
-
-/* Camera-loop inference form: BEVCrossAttention's re-batch -> offset / weight linears -> MSDA ->
- * scatter-add -> divide-by-count (bevformer/attention/image_cross_attention.py:90-136) as ONE launch.
- * The offsets and logits depend on the query only, so they are given once per query and each
- * (query, head) loops over the cameras that see it (vis != 0), in camera order:
- *   out[q] = sum_{cam: vis[cam][q]} msda(value[cam], ref[cam][q] + off[q] / (W_l, H_l), softmax(logits[q]))
- *            / max(#visible cams, 1)
- *   value (cams,nv,heads,d)  ref (cams,nq,P,2)  vis (cams,nq) u8  off_raw (nq,heads,L,P,2)
- *   logits (nq,heads,L*P)  out (nq,heads*d)            batch size 1 (as the reference's masks), L*P <= 256
- * value_stride: floats between consecutive pixels of `value` (0 = dense, heads*d): lets `value` be a column block
- * of a wider matrix, e.g. the three TPV planes' value projections computed by ONE GEMM with N = 3 * heads * d. */
-int selfocc_msda_cross_fwd(const void *value, const int32_t *shapes, const int32_t *starts,
-                           const float *ref, const uint8_t *vis, const float *off_raw, const float *logits,
-                           float *out, int32_t cams, int32_t nv, int32_t nq, int32_t heads, int32_t d,
-                           int32_t L, int32_t P, int32_t value_stride, int32_t value_layout, int32_t value_dtype,
-                           int32_t ol_stride, void *stream);
-
-/* Training counterpart of selfocc_msda_cross_fwd: g_out (nq, heads*d) is the gradient of the camera MEAN;
- * returns g_value (cams,nv,heads,d; zero-initialised by the caller), g_off (nq,heads,L,P,2) and
- * g_logits (nq,heads,L*P) — sums over the visible cameras / count.  host_shapes and workspace as for
- * selfocc_msda_bwd_banded with bs = cams (selfocc_msda_bwd_banded_workspace(cams, nq, heads, L, P));
- * requires selfocc_msda_banded_supported(host_shapes, cams, nq, heads, d, L, P) == 1 and L*P <= 256. */
-int selfocc_msda_cross_bwd(const void *value, const int32_t *shapes, const int32_t *starts,
-                           const int32_t *host_shapes, const float *ref, const uint8_t *vis,
-                           const float *off_raw, const float *logits, const float *g_out,
-                           float *g_value, float *g_off, float *g_logits, int32_t cams, int32_t nv,
-                           int32_t nq, int32_t heads, int32_t d, int32_t L, int32_t P, int32_t value_layout,
-                           int32_t value_dtype, int32_t ol_stride, int32_t g_value_stride, void *workspace, size_t workspace_bytes,
-                           void *stream);
-
-/* g_value must be zero-initialised by the caller (atomically accumulated). */
-int selfocc_msda_bwd(const float *value, const int32_t *shapes, const int32_t *starts,
-                     const float *loc, const float *attw, const float *g_out,
-                     float *g_value, float *g_loc, float *g_attw,
-                     int32_t bs, int32_t nv, int32_t nq, int32_t heads, int32_t d,
-                     int32_t L, int32_t P, void *stream);
-
-/* Banded (output-stationary) backward, same results as selfocc_msda_bwd up to summation order
- * (grad_value is accumulated in double precision and rounded once per list segment).  The sampling points are
- * counting-sorted by (batch, head, level, band of rows); a block owns one band of one level's map in LDS and
- * adds the points of its list with ds_add_f64 — no global atomics in the scatter, no key scan per band.
- * Needs a HOST copy of `shapes` (L, 2) for the work decomposition (L <= 8) and a 16-byte aligned device
- * workspace of selfocc_msda_bwd_banded_workspace(...) bytes (26 bytes per sampling point: a 2-byte row key, a
- * 16-byte record, two 4-byte list slots; plus 28 KB of counters per (batch, head, level); contents undefined
- * before and after).  g_value must be zero-initialised by the caller.  Falls back to selfocc_msda_bwd when a
- * level is wider than the LDS tile, needs more than 1024 bands, or the call has >= 2^30 sampling points. */
-size_t selfocc_msda_bwd_banded_workspace(int32_t bs, int32_t nq, int32_t heads, int32_t L, int32_t P);
-int selfocc_msda_bwd_banded(const float *value, const int32_t *shapes, const int32_t *starts,
-                            const int32_t *host_shapes, const float *loc, const float *attw,
-                            const float *g_out, float *g_value, float *g_loc, float *g_attw,
-                            int32_t bs, int32_t nv, int32_t nq, int32_t heads, int32_t d,
-                            int32_t L, int32_t P, void *workspace, size_t workspace_bytes, void *stream);
-
-/* Training counterpart of selfocc_msda_fused_fwd: gradients w.r.t. value and the RAW linear outputs
- *   g_off (bs,nq,heads,L,P,2) = (d out / d loc) / (W_l, H_l)
- *   g_logits (bs,nq,heads,L*P) = aw (g_aw - sum aw g_aw)               (softmax backward)
- * with the softmax / sampling locations recomputed in registers (the forward saves nothing but its
- * inputs) and grad_value through the banded LDS-f64 scatter.  host_shapes / workspace as for
- * selfocc_msda_bwd_banded; requires selfocc_msda_banded_supported(...) == 1 and L*P <= 256.
- * g_value must be zero-initialised by the caller. */
-int selfocc_msda_banded_supported(const int32_t *host_shapes, int32_t bs, int32_t nq, int32_t heads,
-                                  int32_t d, int32_t L, int32_t P);
-int selfocc_msda_fused_bwd(const void *value, const int32_t *shapes, const int32_t *starts,
-                           const int32_t *host_shapes, const float *ref, int32_t ref_kind,
-                           const float *off_raw, const float *logits, const float *g_out,
-                           float *g_value, float *g_off, float *g_logits, int32_t bs, int32_t nv,
-                           int32_t nq, int32_t heads, int32_t d, int32_t L, int32_t P, int32_t value_layout,
-                           int32_t value_dtype, int32_t ol_stride, int32_t g_value_stride, void *workspace, size_t workspace_bytes,
-                           void *stream);
+int selfocc_msda_fwd(const so_msda_args *args, void *stream);
+int selfocc_msda_bwd(const so_msda_args *args, void *stream);
+/* bytes of so_msda_args::workspace for these sizes (0: bad sizes); reads form, bs, nq, heads, L and P only */
+size_t selfocc_msda_ws_bytes(const so_msda_args *args);
+/* 1: the banded scatter applies to these shapes, 0: it does not (a level wider than the LDS tile, more than 1024
+ * bands per level or 8 levels, >= 2^30 sampling points), -1: bad arguments.  Reads the form, the sizes and
+ * host_shapes only. */
+int selfocc_msda_banded_supported(const so_msda_args *args);
 
 /* ------------------------------------------------------------------------------------
  * Dense SDF / semantic query on a regular metre lattice + Occ3D occupancy tail.

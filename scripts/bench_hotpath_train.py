@@ -11,8 +11,6 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import torch
 import hotpath_common as hc
-from selfocc_amd.model import bricks as _bricks
-_bricks.HEAD_MAJOR_VALUE = os.environ.get('SO_HEAD_MAJOR', '0') == '1'   # A/B switch of the MSDA value layout
 
 d = torch.device("cuda:0")
 torch.manual_seed(0); np.random.seed(0)

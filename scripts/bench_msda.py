@@ -4,9 +4,9 @@ self-attention (78899 queries, 3 levels, P = 12).
 
 Per kernel: HIP-event time and ALGORITHMIC GB/s — SURVEY §8(d): every distinct input byte once + every
 API-visible output byte once — against the 8 TB/s HBM peak.
-    plain     value + loc + attw + out                       (selfocc_msda_fwd / _bwd_banded)
-    fused     value + ref + off_raw + logits + out           (selfocc_msda_fused_fwd / _fused_bwd)
-    cross     value + ref + vis + off_raw + logits + out     (selfocc_msda_cross_fwd / _cross_bwd, camera loop)
+    plain     value + loc + attw + out                       (selfocc_msda_fwd / _bwd, SO_MSDA_PLAIN, banded backward)
+    fused     value + ref + off_raw + logits + out           (selfocc_msda_fwd / _bwd, SO_MSDA_FUSED)
+    cross     value + ref + vis + off_raw + logits + out     (selfocc_msda_fwd / _bwd, SO_MSDA_CROSS: camera loop)
     linears + kernel: the route the eval encoder takes (the two query Linears through selfocc_linear_fwd, then the kernel)
 `--json`: one JSON object on the last line (bench.py's "roofline_msda").  `--case NAME`: one of the three shapes only
 (scripts/pmc_msda_rows.sh profiles each shape in its own rocprofv3 session, so that a kernel's counters belong to one shape).

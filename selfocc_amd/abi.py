@@ -6,7 +6,7 @@ its exported symbols being callable with these layouts.
 """
 import ctypes as C
 
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 # enums ---------------------------------------------------------------------------
 RAYS_EXPLICIT, RAYS_PIXEL_GRID = 0, 1
@@ -14,6 +14,7 @@ SAMPLE_AT_START, SAMPLE_AT_MID = 0, 1
 BKGD_NONE, BKGD_CONST, BKGD_PER_RAY = 0, 1, 2
 JITTER_NONE, JITTER_SINGLE, JITTER_PER_BIN = 0, 1, 2
 FLAG_DEPTH_DIV_NORM, FLAG_CLAMP_RGB, FLAG_EXACT, FLAG_NO_SKIP, FLAG_NO_FACE_SAFE, FLAG_NO_AHEAD, FLAG_RAY_PER_LANE = 1, 2, 4, 8, 16, 32, 64
+MSDA_PLAIN, MSDA_FUSED, MSDA_CROSS = 0, 1, 2
 VALUE_PIXEL_MAJOR, VALUE_HEAD_MAJOR = 0, 1
 DTYPE_F32, DTYPE_BF16 = 0, 1
 LINEAR_RELU = 1
@@ -68,6 +69,19 @@ class SoRenderBwdArgs(C.Structure):
         ("g_weights", _p), ("g_sdf", _p), ("g_grad", _p),
         ("g_sdf_vol", _p), ("g_feat_vol", _p), ("g_inv_s", _p),
         ("scatter_ws", _p), ("scatter_ws_bytes", C.c_uint64),
+    ]
+
+
+class SoMsdaArgs(C.Structure):
+    _fields_ = [
+        ("form", _i), ("bs", _i), ("nv", _i), ("nq", _i), ("heads", _i), ("d", _i), ("L", _i), ("P", _i),
+        ("value_layout", _i), ("value_dtype", _i), ("value_stride", _i), ("ref_kind", _i),
+        ("ol_stride", _i), ("g_value_stride", _i),
+        ("value", _p), ("shapes", _p), ("starts", _p), ("host_shapes", _p),
+        ("loc", _p), ("attw", _p), ("ref", _p), ("vis", _p), ("off_raw", _p), ("logits", _p),
+        ("out", _p),
+        ("g_out", _p), ("g_value", _p), ("g_loc", _p), ("g_attw", _p), ("g_off", _p), ("g_logits", _p),
+        ("workspace", _p), ("workspace_bytes", C.c_uint64),
     ]
 
 
@@ -143,15 +157,10 @@ SYMBOLS = {
     "selfocc_render_fwd": (C.c_int, [C.POINTER(SoRenderArgs), _p]),
     "selfocc_render_bwd": (C.c_int, [C.POINTER(SoRenderBwdArgs), _p]),
     "selfocc_render_bwd_ws_bytes": (C.c_size_t, [C.POINTER(SoRenderBwdArgs)]),
-    "selfocc_msda_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p] + [_i] * 7 + [_p]),
-    "selfocc_msda_fused_fwd": (C.c_int, [_p, _p, _p, _p, _i, _p, _p, _p] + [_i] * 10 + [_p]),
-    "selfocc_msda_cross_fwd": (C.c_int, [_p] * 8 + [_i] * 11 + [_p]),
-    "selfocc_msda_cross_bwd": (C.c_int, [_p] * 12 + [_i] * 11 + [_p, C.c_size_t, _p]),
-    "selfocc_msda_bwd": (C.c_int, [_p] * 9 + [_i] * 7 + [_p]),
-    "selfocc_msda_banded_supported": (C.c_int, [_p] + [_i] * 6),
-    "selfocc_msda_fused_bwd": (C.c_int, [_p] * 5 + [_i] + [_p] * 6 + [_i] * 11 + [_p, C.c_size_t, _p]),
-    "selfocc_msda_bwd_banded_workspace": (C.c_size_t, [_i] * 5),
-    "selfocc_msda_bwd_banded": (C.c_int, [_p] * 10 + [_i] * 7 + [_p, C.c_size_t, _p]),
+    "selfocc_msda_fwd": (C.c_int, [C.POINTER(SoMsdaArgs), _p]),
+    "selfocc_msda_bwd": (C.c_int, [C.POINTER(SoMsdaArgs), _p]),
+    "selfocc_msda_ws_bytes": (C.c_size_t, [C.POINTER(SoMsdaArgs)]),
+    "selfocc_msda_banded_supported": (C.c_int, [C.POINTER(SoMsdaArgs)]),
     "selfocc_field_query": (C.c_int, [C.POINTER(SoQueryArgs), _p]),
     "selfocc_field_query_bwd": (C.c_int, [C.POINTER(SoQueryArgs), _p, _p, _p, _p, _p]),
     "selfocc_field_volume_bwd": (C.c_int, [_p] * 3 + [_i] * 4 + [_p, _p, _p, _i, _p, _p, _i] + [_p] * 7 + [_p]),

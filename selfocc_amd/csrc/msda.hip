@@ -1145,18 +1145,6 @@ __global__ __launch_bounds__(kBandThreads) void msda_bwd_band_list_kernel(const 
     }
 }
 
-int validate(const float *value, const int32_t *shapes, const int32_t *starts, const float *loc,
-             const float *attw, int bs, int nv, int nq, int heads, int d, int L, int P) {
-    SO_REQUIRE(bs >= 0 && nq >= 0 && nv >= 0, "msda: negative size");
-    SO_REQUIRE((bs == 0 || nq == 0) || (value && shapes && starts && loc && attw), "msda: NULL input pointer");
-    SO_REQUIRE(heads >= 1 && L >= 1 && P >= 1, "msda: heads, L, P must be >= 1");
-    SO_REQUIRE(d == 4 || d == 8 || d == 16 || d == 32, "msda: channels per head must be 4, 8, 16 or 32 (got %d)", d);
-    SO_REQUIRE((long long)bs * nq * heads * L * P < (1LL << 40), "msda: problem too large");
-    SO_REQUIRE((long long)bs * nv * heads * d < (1LL << 31) && (long long)bs * nq * heads * d < (1LL << 31),
-               "msda: value / output tensors must have < 2^31 elements");
-    return 0;
-}
-
 }  // namespace
 
 // Lanes per (b, q, head) group: a power of two G >= d / 4 (whole channel teams) with rounds = ceil(LP / G)
@@ -1196,52 +1184,6 @@ static void so_pick_group_fused(int LP, int d, int &G, int &logG) {
     G = 1 << best_l;
 }
 
-extern "C" int selfocc_msda_fwd(const float *value, const int32_t *shapes, const int32_t *starts,
-                                const float *loc, const float *attw, float *out, int32_t bs,
-                                int32_t nv, int32_t nq, int32_t heads, int32_t d, int32_t L,
-                                int32_t P, void *stream) {
-    if (validate(value, shapes, starts, loc, attw, bs, nv, nq, heads, d, L, P)) return -1;
-    const long long n_groups = (long long)bs * nq * heads;
-    if (n_groups == 0) return 0;
-    SO_REQUIRE(out != nullptr, "msda_fwd: out is NULL");
-    if (nv == 0)   // nothing to sample: every point is outside every (empty) map
-        return (int)hipMemsetAsync(out, 0, (size_t)n_groups * d * sizeof(float), (hipStream_t)stream);
-    const int LP = L * P;
-    int G = 1, logG = 0;
-    so_pick_group(LP, d, 8, G, logG);
-    const int gpb = 256 / G;
-    const long long blocks = (n_groups + gpb - 1) / gpb;
-    SO_REQUIRE(blocks < (1LL << 31), "msda_fwd: grid too large");
-    MsdaDims dm{bs, nv, nq, heads, L, P, 0};
-    hipStream_t st = (hipStream_t)stream;
-#define SO_LAUNCH_G(DD, LG)                                                                       \
-    hipLaunchKernelGGL((msda_fwd_kernel<DD, LG>), dim3((unsigned)blocks), dim3(256), 0, st, value, \
-                       shapes, starts, loc, attw, out, dm)
-    // so_pick_group returns whole channel teams (G >= D / 4): 22 of the 4 x 7 combinations can be reached
-#define SO_LAUNCH(DD, LGMIN)                                                                      \
-    switch (logG) {                                                                               \
-        case 0: SO_LAUNCH_G(DD, (LGMIN > 0 ? LGMIN : 0)); break;                                  \
-        case 1: SO_LAUNCH_G(DD, (LGMIN > 1 ? LGMIN : 1)); break;                                  \
-        case 2: SO_LAUNCH_G(DD, (LGMIN > 2 ? LGMIN : 2)); break;                                  \
-        case 3: SO_LAUNCH_G(DD, 3); break;                                                        \
-        case 4: SO_LAUNCH_G(DD, 4); break;                                                        \
-        case 5: SO_LAUNCH_G(DD, 5); break;                                                        \
-        default: SO_LAUNCH_G(DD, 6); break;                                                       \
-    }
-    SO_REQUIRE((1 << logG) >= d / 4, "msda_fwd: group of %d lanes for %d channels", 1 << logG, d);
-    switch (d) {
-        case 4: SO_LAUNCH(4, 0); break;
-        case 8: SO_LAUNCH(8, 1); break;
-        case 16: SO_LAUNCH(16, 2); break;
-        default: SO_LAUNCH(32, 3); break;
-    }
-#undef SO_LAUNCH
-#undef SO_LAUNCH_G
-    return so_launch_status();
-}
-
-
-
 // The (D, log2 G, value type) combinations of the fused / camera-loop families that can be launched: D = 8, 16, 32 channels per
 // head (the shipped lifters use 16; the plain mmcv-boundary op keeps 4), whole channel teams (G >= D / 4: so_pick_group_fused
 // never returns less), bfloat16 `value` for D = 16 only.  Round 4 instantiated all 4 x 7 x 2 = 56 per family (224 kernels, 6 MB).
@@ -1264,121 +1206,9 @@ extern "C" int selfocc_msda_fwd(const float *value, const int32_t *shapes, const
             SO_REQUIRE(!(bf_), "msda: bfloat16 value is built for 16 channels per head only (got %d)", (int)(d_)); \
             if ((d_) == 8) { SO_REQUIRE(logG_ >= 1, "msda: bad group"); SO_FUSED_LG(8, 1, float) }          \
             else if ((d_) == 32) { SO_REQUIRE(logG_ >= 3, "msda: bad group"); SO_FUSED_LG(32, 3, float) }   \
-            else SO_REQUIRE(false, "msda fused / camera-loop ops: channels per head must be 8, 16 or 32 (got %d); the plain op takes 4", (int)(d_)); \
+            else SO_REQUIRE(false, "msda fused / camera-loop forms: channels per head must be 8, 16 or 32 (got %d); the plain form takes 4", (int)(d_)); \
         }                                                                                 \
     } while (0)
-
-// off_raw / logits row strides of a launch: dense tensors, or one merged [offsets | logits] projection row per query
-static inline int so_set_ol(MsdaDims &dm, int ol_stride, const float *off_raw, const float *logits, const char *who) {
-    const int LP = dm.L * dm.P;
-    if (ol_stride == 0) {
-        dm.off_ld = dm.heads * LP * 2;
-        dm.lg_ld = dm.heads * LP;
-        return 0;
-    }
-    SO_REQUIRE(ol_stride >= 3 * dm.heads * LP && ol_stride % 2 == 0, "%s: ol_stride must be 0 (dense) or an even number >= 3 * heads * L * P = %d (got %d)",
-               who, 3 * dm.heads * LP, ol_stride);
-    SO_REQUIRE((((uintptr_t)off_raw) & 7) == 0, "%s: off_raw must be 8-byte aligned", who);
-    SO_REQUIRE((long long)dm.bs * dm.nq * ol_stride < (1LL << 40), "%s: offsets / logits too large", who);
-    dm.off_ld = dm.lg_ld = ol_stride;
-    return 0;
-}
-
-extern "C" int selfocc_msda_fused_fwd(const void *value, const int32_t *shapes, const int32_t *starts,
-                                      const float *ref, int32_t ref_kind, const float *off_raw, const float *logits,
-                                      float *out, int32_t bs, int32_t nv, int32_t nq, int32_t heads, int32_t d,
-                                      int32_t L, int32_t P, int32_t value_layout, int32_t value_dtype, int32_t ol_stride,
-                                      void *stream) {
-    if (validate((const float *)value, shapes, starts, off_raw, logits, bs, nv, nq, heads, d, L, P)) return -1;
-    const long long n_groups = (long long)bs * nq * heads;
-    if (n_groups == 0) return 0;
-    SO_REQUIRE(out != nullptr && ref != nullptr, "msda_fused_fwd: NULL pointer");
-    SO_REQUIRE(value_dtype == SO_DTYPE_F32 || value_dtype == SO_DTYPE_BF16, "msda_fused_fwd: bad value_dtype");
-    SO_REQUIRE(value_layout == SO_VALUE_PIXEL_MAJOR || value_layout == SO_VALUE_HEAD_MAJOR, "msda_fused_fwd: bad value_layout");
-    SO_REQUIRE(ref_kind >= 0 && ref_kind <= 2, "msda_fused_fwd: ref_kind must be 0, 1 or 2");
-    if (nv == 0)
-        return (int)hipMemsetAsync(out, 0, (size_t)n_groups * d * sizeof(float), (hipStream_t)stream);
-    const int LP = L * P;
-    SO_REQUIRE(LP <= 256, "msda_fused_fwd: L * P must be <= 256 (got %d); use the unfused op", LP);
-    int G = 1, logG = 0;
-    so_pick_group_fused(LP, d, G, logG);
-    const int gpb = 256 / G;
-    const long long blocks = (n_groups + gpb - 1) / gpb;
-    SO_REQUIRE(blocks < (1LL << 31), "msda_fused_fwd: grid too large");
-    MsdaDims dm{bs, nv, nq, heads, L, P, 0, 0, value_layout};
-    if (so_set_ol(dm, ol_stride, off_raw, logits, "msda_fused_fwd")) return -1;
-    hipStream_t st = (hipStream_t)stream;
-#define SO_LAUNCH_VT(DD, LG, VT) \
-        hipLaunchKernelGGL((msda_fused_fwd_kernel<DD, LG, VT>), dim3((unsigned)blocks), dim3(256), 0, st, \
-                           (const VT *)value, shapes, starts, ref, ref_kind, off_raw, logits, out, dm)
-    SO_FUSED_DISPATCH(d, logG, value_dtype == SO_DTYPE_BF16);
-#undef SO_LAUNCH_VT
-    return so_launch_status();
-}
-
-extern "C" int selfocc_msda_cross_fwd(const void *value, const int32_t *shapes, const int32_t *starts,
-                                      const float *ref, const uint8_t *vis, const float *off_raw,
-                                      const float *logits, float *out, int32_t cams, int32_t nv, int32_t nq,
-                                      int32_t heads, int32_t d, int32_t L, int32_t P, int32_t value_stride,
-                                      int32_t value_layout, int32_t value_dtype, int32_t ol_stride, void *stream) {
-    SO_REQUIRE(cams >= 1, "msda_cross_fwd: cams must be >= 1");
-    SO_REQUIRE(value_dtype == SO_DTYPE_F32 || value_dtype == SO_DTYPE_BF16, "msda_cross_fwd: bad value_dtype");
-    SO_REQUIRE(value_layout == SO_VALUE_PIXEL_MAJOR || (value_layout == SO_VALUE_HEAD_MAJOR && value_stride == 0),
-               "msda_cross_fwd: bad value_layout (head-major values are dense: value_stride must be 0)");
-    SO_REQUIRE(value_stride == 0 || (value_stride >= heads * d && value_stride % 4 == 0),
-               "msda_cross_fwd: value_stride must be 0 or a multiple of 4 >= heads * d");
-    SO_REQUIRE((long long)cams * nv * (value_stride ? value_stride : heads * d) < (1LL << 31),
-               "msda_cross_fwd: value must span < 2^31 floats");
-    if (validate((const float *)value, shapes, starts, off_raw, logits, cams, nv, nq, heads, d, L, P)) return -1;
-    const long long n_groups = (long long)nq * heads;
-    if (n_groups == 0) return 0;
-    SO_REQUIRE(out != nullptr && ref != nullptr && vis != nullptr, "msda_cross_fwd: NULL pointer");
-    SO_REQUIRE(n_groups < (1LL << 31), "msda_cross_fwd: nq * heads must be < 2^31");
-    const int LP = L * P;
-    SO_REQUIRE(LP <= 256, "msda_cross_fwd: L * P must be <= 256 (got %d)", LP);
-    if (nv == 0) return (int)hipMemsetAsync(out, 0, (size_t)n_groups * d * sizeof(float), (hipStream_t)stream);
-    int G = 1, logG = 0;
-    so_pick_group_fused(LP, d, G, logG);
-    const int gpb = 256 / G;
-    const long long blocks = (n_groups + gpb - 1) / gpb;
-    SO_REQUIRE(blocks < (1LL << 31), "msda_cross_fwd: grid too large");
-    MsdaDims dm{1, nv, nq, heads, L, P, 0, value_stride, value_layout};
-    if (so_set_ol(dm, ol_stride, off_raw, logits, "msda_cross_fwd")) return -1;
-    hipStream_t st = (hipStream_t)stream;
-#define SO_LAUNCH_VT(DD, LG, VT) \
-        hipLaunchKernelGGL((msda_cross_fwd_kernel<DD, LG, VT>), dim3((unsigned)blocks), dim3(256), 0, st, \
-                           (const VT *)value, shapes, starts, ref, vis, off_raw, logits, out, cams, dm)
-    SO_FUSED_DISPATCH(d, logG, value_dtype == SO_DTYPE_BF16);
-#undef SO_LAUNCH_VT
-    return so_launch_status();
-}
-
-extern "C" int selfocc_msda_bwd(const float *value, const int32_t *shapes, const int32_t *starts,
-                                const float *loc, const float *attw, const float *g_out,
-                                float *g_value, float *g_loc, float *g_attw, int32_t bs,
-                                int32_t nv, int32_t nq, int32_t heads, int32_t d, int32_t L,
-                                int32_t P, void *stream) {
-    if (validate(value, shapes, starts, loc, attw, bs, nv, nq, heads, d, L, P)) return -1;
-    const long long n_pts = (long long)bs * nq * heads * L * P;
-    if (n_pts == 0) return 0;
-    SO_REQUIRE(g_out && g_value && g_loc && g_attw, "msda_bwd: NULL gradient pointer");
-    const long long blocks = (n_pts + 255) / 256;
-    SO_REQUIRE(blocks < (1LL << 31), "msda_bwd: grid too large");
-    MsdaDims dm{bs, nv, nq, heads, L, P, 0};
-    hipStream_t st = (hipStream_t)stream;
-#define SO_LAUNCH(DD)                                                                             \
-    hipLaunchKernelGGL((msda_bwd_kernel<DD>), dim3((unsigned)blocks), dim3(256), 0, st, value,    \
-                       shapes, starts, loc, attw, g_out, g_value, g_loc, g_attw, dm)
-    switch (d) {
-        case 4: SO_LAUNCH(4); break;
-        case 8: SO_LAUNCH(8); break;
-        case 16: SO_LAUNCH(16); break;
-        default: SO_LAUNCH(32); break;
-    }
-#undef SO_LAUNCH
-    return so_launch_status();
-}
-
 
 // ---- banded backward -------------------------------------------------------------------------
 static size_t so_band_key_bytes(long long n_pts) { return (size_t)((n_pts + 8) * 2 + 15) / 16 * 16; }
@@ -1393,31 +1223,20 @@ static size_t so_band_ws_bytes(int bs, int nq, int heads, int L, int P) {
     return so_band_key_bytes(n_pts) + (size_t)n_pts * 16 + so_bin_counter_bytes(bs, heads, L) + (size_t)n_pts * 8;
 }
 
-extern "C" size_t selfocc_msda_bwd_banded_workspace(int32_t bs, int32_t nq, int32_t heads, int32_t L, int32_t P) {
-    if (bs < 0 || nq < 0 || heads < 1 || L < 1 || P < 1) return 0;
-    return so_band_ws_bytes(bs, nq, heads, L, P);
-}
-
 namespace {
+constexpr int kBandBlock = 512;     // threads of the band kernel (its 52 KB tile: two blocks per CU)
+constexpr int kBandSeg = 4096;      // list entries per band-kernel block
+
 struct BandSetup {
     MsdaBinPlan bin;
-    int threads;   // block shape of the band kernel (512 / 1024)
     int tile_px;   // pixels of the largest band
     bool ok;       // false: a level is wider than the LDS tile or needs > kMaxBands bands, or the index space overflows
 };
 
-int so_env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
-
 // bands: as many rows as the tile holds (the fewer bands, the fewer points straddle two)
 int so_band_setup(const int32_t *host_shapes, int bs, int nq, int heads, int d, int L, int P, BandSetup &bsu) {
-    // tuning switches (A/B runs): block shape 512 / 1024, list entries per block
-    static const int env_threads = so_env_int("SELFOCC_BAND_THREADS", 512), env_seg = so_env_int("SELFOCC_BAND_SEG", 4096);
     MsdaBinPlan &bp = bsu.bin;
-    bsu.threads = env_threads == 1024 ? 1024 : 512;
-    const int cap_px = band_tile_bytes(bsu.threads) / (8 * d);
+    const int cap_px = band_tile_bytes(kBandBlock) / (8 * d);
     bsu.ok = L <= 8;
     bsu.tile_px = 0;
     int nb = 0;
@@ -1437,7 +1256,7 @@ int so_band_setup(const int32_t *host_shapes, int bs, int nq, int heads, int d, 
     }
     for (int l = L; l <= 8; ++l) bp.band0[std::min(l, 8)] = nb;
     bp.nbands = nb;
-    bp.seg = std::max(64, env_seg);
+    bp.seg = kBandSeg;
     int lg = 0;
     while ((1LL << lg) < P) ++lg;
     bp.divP.l = lg;
@@ -1495,16 +1314,14 @@ int so_band_scatter(const int32_t *shapes, const int32_t *starts, const float *g
                        cursor, off, w.list, vis, bpb, dm, bp);
     const size_t shm = (size_t)bsu.tile_px * d * sizeof(double);
     // the grid is an upper bound (every point in two bands): blocks past item0[nb] return at once
-#define SO_LAUNCH_T(DD, TT)                                                                                      \
-    {                                                                                                            \
-        /* per launch: the attribute is per device (a process may drive several GPUs) */                         \
-        (void)hipFuncSetAttribute((const void *)msda_bwd_band_list_kernel<DD, TT>,                               \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, band_tile_bytes(TT));              \
-        hipLaunchKernelGGL((msda_bwd_band_list_kernel<DD, TT>), dim3((unsigned)max_items), dim3(TT), shm, st,    \
-                           shapes, starts, g_out, g_value, w.recs, cnt, off, item0, w.list, nb, dm_g, bp);       \
+#define SO_LAUNCH(DD)                                                                                             \
+    {                                                                                                             \
+        /* per launch: the attribute is per device (a process may drive several GPUs) */                          \
+        (void)hipFuncSetAttribute((const void *)msda_bwd_band_list_kernel<DD, kBandBlock>,                        \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, band_tile_bytes(kBandBlock));       \
+        hipLaunchKernelGGL((msda_bwd_band_list_kernel<DD, kBandBlock>), dim3((unsigned)max_items), dim3(kBandBlock), \
+                           shm, st, shapes, starts, g_out, g_value, w.recs, cnt, off, item0, w.list, nb, dm_g, bp);  \
     }
-#define SO_LAUNCH(DD)                                                                                            \
-    if (bsu.threads == 512) SO_LAUNCH_T(DD, 512) else SO_LAUNCH_T(DD, 1024)
     switch (d) {
         case 4: SO_LAUNCH(4); break;
         case 8: SO_LAUNCH(8); break;
@@ -1512,180 +1329,266 @@ int so_band_scatter(const int32_t *shapes, const int32_t *starts, const float *g
         default: SO_LAUNCH(32); break;
     }
 #undef SO_LAUNCH
-#undef SO_LAUNCH_T
     return so_launch_status();
+}
+
+// ---- the argument checks -----------------------------------------------------------------------
+// the form and the sizes: everything selfocc_msda_banded_supported reads besides host_shapes
+int so_msda_check_sizes(const so_msda_args *a) {
+    SO_REQUIRE(a != nullptr, "msda: args is NULL");
+    SO_REQUIRE(a->form == SO_MSDA_PLAIN || a->form == SO_MSDA_FUSED || a->form == SO_MSDA_CROSS,
+               "msda: form must be SO_MSDA_PLAIN, SO_MSDA_FUSED or SO_MSDA_CROSS (got %d)", a->form);
+    SO_REQUIRE(a->form != SO_MSDA_CROSS || a->bs >= 1, "msda (camera loop): bs = cams must be >= 1");
+    SO_REQUIRE(a->bs >= 0 && a->nq >= 0 && a->nv >= 0, "msda: negative size");
+    SO_REQUIRE(a->heads >= 1 && a->L >= 1 && a->P >= 1, "msda: heads, L, P must be >= 1");
+    SO_REQUIRE(a->d == 4 || a->d == 8 || a->d == 16 || a->d == 32,
+               "msda: channels per head must be 4, 8, 16 or 32 (got %d)", a->d);
+    return 0;
+}
+
+// every check of selfocc_msda_fwd / _bwd, before anything is launched: first what every form shares, then what one
+// form adds, then (for a call with work to do) the pointers it reads and writes
+int so_msda_check(const so_msda_args *args, bool bwd) {
+    if (so_msda_check_sizes(args)) return -1;
+    const so_msda_args &a = *args;
+    const bool plain = a.form == SO_MSDA_PLAIN, cross = a.form == SO_MSDA_CROSS;
+    const int hd = a.heads * a.d, LP = a.L * a.P;
+    SO_REQUIRE((long long)a.bs * a.nq * a.heads * LP < (1LL << 40), "msda: problem too large");
+    SO_REQUIRE((long long)a.bs * a.nv * hd < (1LL << 31) && (long long)a.bs * a.nq * hd < (1LL << 31),
+               "msda: value / output tensors must have < 2^31 elements");
+    SO_REQUIRE(a.value_stride == 0 || (cross && !bwd), "msda: value_stride is for the camera-loop forward only (got %d)",
+               a.value_stride);
+    if (plain) {
+        SO_REQUIRE(a.value_layout == SO_VALUE_PIXEL_MAJOR && a.value_dtype == SO_DTYPE_F32,
+                   "msda (plain): value must be float32 and pixel-major");
+        SO_REQUIRE(!bwd || a.g_value_stride == 0, "msda (plain): g_value_stride must be 0");
+    } else {
+        SO_REQUIRE(a.value_dtype == SO_DTYPE_F32 || a.value_dtype == SO_DTYPE_BF16, "msda: bad value_dtype");
+        SO_REQUIRE(a.value_layout == SO_VALUE_PIXEL_MAJOR || a.value_layout == SO_VALUE_HEAD_MAJOR,
+                   "msda: bad value_layout");
+        SO_REQUIRE(a.form != SO_MSDA_FUSED || (a.ref_kind >= 0 && a.ref_kind <= 2), "msda: ref_kind must be 0, 1 or 2");
+        SO_REQUIRE(LP <= 256, "msda: L * P must be <= 256 for the fused / camera-loop forms (got %d); use the plain form", LP);
+        // off_raw / logits: dense tensors, or one merged [offsets | logits] projection row per query
+        SO_REQUIRE(a.ol_stride == 0 || (a.ol_stride >= 3 * a.heads * LP && a.ol_stride % 2 == 0),
+                   "msda: ol_stride must be 0 (dense) or an even number >= 3 * heads * L * P = %d (got %d)",
+                   3 * a.heads * LP, a.ol_stride);
+        SO_REQUIRE(a.ol_stride == 0 || ((((uintptr_t)a.off_raw) | (bwd ? (uintptr_t)a.g_off : 0)) & 7) == 0,
+                   "msda: off_raw and g_off must be 8-byte aligned with an ol_stride");
+        SO_REQUIRE((long long)(cross ? 1 : a.bs) * a.nq * a.ol_stride < (1LL << 40), "msda: offsets / logits too large");
+        SO_REQUIRE(!bwd || a.g_value_stride == 0 || (a.g_value_stride >= hd && (long long)a.bs * a.nv * a.g_value_stride < (1LL << 31)),
+                   "msda: g_value_stride must be 0 or >= heads * d with bs * nv * stride < 2^31 (got %d)", a.g_value_stride);
+    }
+    if (cross) {
+        SO_REQUIRE(a.value_layout == SO_VALUE_PIXEL_MAJOR || a.value_stride == 0,
+                   "msda (camera loop): head-major values are dense: value_stride must be 0");
+        SO_REQUIRE(a.value_stride == 0 || (a.value_stride >= hd && a.value_stride % 4 == 0),
+                   "msda (camera loop): value_stride must be 0 or a multiple of 4 >= heads * d");
+        SO_REQUIRE((long long)a.bs * a.nv * (a.value_stride ? a.value_stride : hd) < (1LL << 31),
+                   "msda (camera loop): value must span < 2^31 floats");
+        SO_REQUIRE((long long)a.nq * a.heads < (1LL << 31), "msda (camera loop): nq * heads must be < 2^31");
+    }
+    if (a.bs == 0 || a.nq == 0) return 0;   // nothing to do: no pointer is read
+#define SO_NEED(p) SO_REQUIRE(a.p != nullptr, "msda: " #p " is NULL")
+    SO_NEED(value); SO_NEED(shapes); SO_NEED(starts);
+    if (plain) { SO_NEED(loc); SO_NEED(attw); }
+    else { SO_NEED(ref); SO_NEED(off_raw); SO_NEED(logits); }
+    if (cross) SO_NEED(vis);
+    if (!bwd) {
+        SO_NEED(out);
+        return 0;
+    }
+    SO_NEED(g_out); SO_NEED(g_value);
+    if (plain) { SO_NEED(g_loc); SO_NEED(g_attw); }
+    else { SO_NEED(g_off); SO_NEED(g_logits); }
+#undef SO_NEED
+    if (plain && a.host_shapes == nullptr) return 0;   // the global-atomic scatter: no workspace
+    SO_REQUIRE(a.host_shapes != nullptr, "msda: host_shapes is NULL (host copy of the (L, 2) level shapes)");
+    SO_REQUIRE(a.L <= 8, "msda: the banded backward takes at most 8 levels (got %d)", a.L);
+    const size_t need = so_band_ws_bytes(a.bs, a.nq, a.heads, a.L, a.P);
+    SO_REQUIRE(a.workspace != nullptr && a.workspace_bytes >= need, "msda: workspace too small (%llu bytes, need %zu)",
+               (unsigned long long)a.workspace_bytes, need);
+    SO_REQUIRE(((uintptr_t)a.workspace & 15) == 0, "msda: workspace must be 16-byte aligned");
+    return 0;
+}
+
+// what the kernels see of a call: the camera-loop forward addresses one camera's value at a time (bs = 1), its backward
+// shares the rows of g_out between the cameras
+MsdaDims so_msda_dims(const so_msda_args &a, bool bwd) {
+    const bool cross = a.form == SO_MSDA_CROSS;
+    MsdaDims dm{cross && !bwd ? 1 : a.bs, a.nv, a.nq, a.heads, a.L, a.P, cross && bwd ? 1 : 0, a.value_stride, a.value_layout};
+    if (a.form != SO_MSDA_PLAIN) {
+        const int LP = a.L * a.P;
+        dm.off_ld = a.ol_stride ? a.ol_stride : a.heads * LP * 2;
+        dm.lg_ld = a.ol_stride ? a.ol_stride : a.heads * LP;
+    }
+    return dm;
 }
 }  // namespace
 
-/* 1: the banded scatter applies to these shapes (selfocc_msda_fused_bwd needs it; selfocc_msda_bwd_banded falls
- * back to selfocc_msda_bwd by itself), 0: it does not, -1: bad arguments */
-extern "C" int selfocc_msda_banded_supported(const int32_t *host_shapes, int32_t bs, int32_t nq, int32_t heads,
-                                             int32_t d, int32_t L, int32_t P) {
-    SO_REQUIRE(host_shapes != nullptr && bs >= 0 && nq >= 0 && heads >= 1 && L >= 1 && P >= 1, "msda banded: bad arguments");
-    SO_REQUIRE(d == 4 || d == 8 || d == 16 || d == 32, "msda: channels per head must be 4, 8, 16 or 32 (got %d)", d);
-    if (L > 8) return 0;
+extern "C" size_t selfocc_msda_ws_bytes(const so_msda_args *a) {
+    if (a == nullptr || a->form < SO_MSDA_PLAIN || a->form > SO_MSDA_CROSS || a->bs < 0 || a->nq < 0 || a->heads < 1 ||
+        a->L < 1 || a->P < 1)
+        return 0;
+    return so_band_ws_bytes(a->bs, a->nq, a->heads, a->L, a->P);
+}
+
+extern "C" int selfocc_msda_banded_supported(const so_msda_args *a) {
+    if (so_msda_check_sizes(a)) return -1;
+    SO_REQUIRE(a->host_shapes != nullptr, "msda banded: host_shapes is NULL");
+    if (a->L > 8) return 0;
     BandSetup bsu;
-    if (so_band_setup(host_shapes, bs, nq, heads, d, L, P, bsu)) return -1;
+    if (so_band_setup(a->host_shapes, a->bs, a->nq, a->heads, a->d, a->L, a->P, bsu)) return -1;
     return bsu.ok ? 1 : 0;
 }
 
-extern "C" int selfocc_msda_bwd_banded(const float *value, const int32_t *shapes, const int32_t *starts,
-                                       const int32_t *host_shapes, const float *loc, const float *attw,
-                                       const float *g_out, float *g_value, float *g_loc, float *g_attw,
-                                       int32_t bs, int32_t nv, int32_t nq, int32_t heads, int32_t d, int32_t L,
-                                       int32_t P, void *workspace, size_t workspace_bytes, void *stream) {
-    if (validate(value, shapes, starts, loc, attw, bs, nv, nq, heads, d, L, P)) return -1;
-    const long long n_pts = (long long)bs * nq * heads * L * P;
-    if (n_pts == 0) return 0;
-    SO_REQUIRE(g_out && g_value && g_loc && g_attw, "msda_bwd_banded: NULL gradient pointer");
-    SO_REQUIRE(host_shapes != nullptr, "msda_bwd_banded: host_shapes is NULL (host copy of the (L, 2) level shapes)");
-    SO_REQUIRE(L <= 8, "msda_bwd_banded: at most 8 levels (got %d); use selfocc_msda_bwd", L);
-    SO_REQUIRE(workspace != nullptr && workspace_bytes >= so_band_ws_bytes(bs, nq, heads, L, P),
-               "msda_bwd_banded: workspace too small (%zu bytes, need %zu)", workspace_bytes,
-               so_band_ws_bytes(bs, nq, heads, L, P));
-    SO_REQUIRE(((uintptr_t)workspace & 15) == 0, "msda_bwd_banded: workspace must be 16-byte aligned");
-    BandSetup bsu;
-    if (so_band_setup(host_shapes, bs, nq, heads, d, L, P, bsu)) return -1;
-    if (!bsu.ok)
-        return selfocc_msda_bwd(value, shapes, starts, loc, attw, g_out, g_value, g_loc, g_attw, bs, nv, nq, heads,
-                                d, L, P, stream);
+extern "C" int selfocc_msda_fwd(const so_msda_args *args, void *stream) {
+    if (so_msda_check(args, false)) return -1;
+    const so_msda_args &a = *args;
+    if (a.bs == 0 || a.nq == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    MsdaDims dm{bs, nv, nq, heads, L, P, 0};
-    const BandWorkspace w = so_band_workspace(workspace, bs, nq, heads, L, P);
-    const long long pblocks = (n_pts + 255) / 256;
-    SO_REQUIRE(pblocks < (1LL << 31), "msda_bwd_banded: grid too large");
-#define SO_LAUNCH(DD)                                                                                        \
-    hipLaunchKernelGGL((msda_bwd_point_kernel<DD>), dim3((unsigned)pblocks), dim3(256), 0, st, value,        \
-                       shapes, starts, loc, attw, g_out, g_loc, g_attw, w.keys, w.recs, dm)
-    switch (d) {
-        case 4: SO_LAUNCH(4); break;
-        case 8: SO_LAUNCH(8); break;
-        case 16: SO_LAUNCH(16); break;
-        default: SO_LAUNCH(32); break;
+    const MsdaDims dm = so_msda_dims(a, false);
+    const long long n_groups = (long long)dm.bs * a.nq * a.heads;
+    if (a.nv == 0)   // nothing to sample: every point is outside every (empty) map
+        return (int)hipMemsetAsync(a.out, 0, (size_t)n_groups * a.d * sizeof(float), st);
+    const int LP = a.L * a.P, d = a.d;
+    int G = 1, logG = 0;
+    if (a.form == SO_MSDA_PLAIN)
+        so_pick_group(LP, d, 8, G, logG);
+    else
+        so_pick_group_fused(LP, d, G, logG);
+    const int gpb = 256 / G;
+    const long long blocks = (n_groups + gpb - 1) / gpb;
+    SO_REQUIRE(blocks < (1LL << 31), "msda_fwd: grid too large");
+    const bool bf16 = a.value_dtype == SO_DTYPE_BF16;
+    if (a.form == SO_MSDA_PLAIN) {
+        const float *value = (const float *)a.value;
+#define SO_LAUNCH_G(DD, LG)                                                                       \
+    hipLaunchKernelGGL((msda_fwd_kernel<DD, LG>), dim3((unsigned)blocks), dim3(256), 0, st, value, \
+                       a.shapes, a.starts, a.loc, a.attw, a.out, dm)
+    // so_pick_group returns whole channel teams (G >= D / 4): 22 of the 4 x 7 combinations can be reached
+#define SO_LAUNCH(DD, LGMIN)                                                                      \
+    switch (logG) {                                                                               \
+        case 0: SO_LAUNCH_G(DD, (LGMIN > 0 ? LGMIN : 0)); break;                                  \
+        case 1: SO_LAUNCH_G(DD, (LGMIN > 1 ? LGMIN : 1)); break;                                  \
+        case 2: SO_LAUNCH_G(DD, (LGMIN > 2 ? LGMIN : 2)); break;                                  \
+        case 3: SO_LAUNCH_G(DD, 3); break;                                                        \
+        case 4: SO_LAUNCH_G(DD, 4); break;                                                        \
+        case 5: SO_LAUNCH_G(DD, 5); break;                                                        \
+        default: SO_LAUNCH_G(DD, 6); break;                                                       \
     }
+        SO_REQUIRE((1 << logG) >= d / 4, "msda_fwd: group of %d lanes for %d channels", 1 << logG, d);
+        switch (d) {
+            case 4: SO_LAUNCH(4, 0); break;
+            case 8: SO_LAUNCH(8, 1); break;
+            case 16: SO_LAUNCH(16, 2); break;
+            default: SO_LAUNCH(32, 3); break;
+        }
 #undef SO_LAUNCH
-    return so_band_scatter(shapes, starts, g_out, g_value, w, bsu, dm, d, nullptr, st);
+#undef SO_LAUNCH_G
+    } else if (a.form == SO_MSDA_FUSED) {
+#define SO_LAUNCH_VT(DD, LG, VT) \
+        hipLaunchKernelGGL((msda_fused_fwd_kernel<DD, LG, VT>), dim3((unsigned)blocks), dim3(256), 0, st, \
+                           (const VT *)a.value, a.shapes, a.starts, a.ref, a.ref_kind, a.off_raw, a.logits, a.out, dm)
+        SO_FUSED_DISPATCH(d, logG, bf16);
+#undef SO_LAUNCH_VT
+    } else {
+#define SO_LAUNCH_VT(DD, LG, VT) \
+        hipLaunchKernelGGL((msda_cross_fwd_kernel<DD, LG, VT>), dim3((unsigned)blocks), dim3(256), 0, st, \
+                           (const VT *)a.value, a.shapes, a.starts, a.ref, a.vis, a.off_raw, a.logits, a.out, a.bs, dm)
+        SO_FUSED_DISPATCH(d, logG, bf16);
+#undef SO_LAUNCH_VT
+    }
+    return so_launch_status();
 }
 
-extern "C" int selfocc_msda_fused_bwd(const void *value, const int32_t *shapes, const int32_t *starts,
-                                      const int32_t *host_shapes, const float *ref, int32_t ref_kind,
-                                      const float *off_raw, const float *logits, const float *g_out,
-                                      float *g_value, float *g_off, float *g_logits, int32_t bs, int32_t nv,
-                                      int32_t nq, int32_t heads, int32_t d, int32_t L, int32_t P, int32_t value_layout,
-                                      int32_t value_dtype, int32_t ol_stride, int32_t g_value_stride, void *workspace,
-                                      size_t workspace_bytes, void *stream) {
-    if (validate((const float *)value, shapes, starts, off_raw, logits, bs, nv, nq, heads, d, L, P)) return -1;
-    SO_REQUIRE(value_dtype == SO_DTYPE_F32 || value_dtype == SO_DTYPE_BF16, "msda_fused_bwd: bad value_dtype");
-    const long long n_groups = (long long)bs * nq * heads;
-    if (n_groups == 0) return 0;
-    SO_REQUIRE(ref && g_out && g_value && g_off && g_logits, "msda_fused_bwd: NULL pointer");
-    SO_REQUIRE(value_layout == SO_VALUE_PIXEL_MAJOR || value_layout == SO_VALUE_HEAD_MAJOR, "msda_fused_bwd: bad value_layout");
-    SO_REQUIRE(ref_kind >= 0 && ref_kind <= 2, "msda_fused_bwd: ref_kind must be 0, 1 or 2");
-    SO_REQUIRE(host_shapes != nullptr, "msda_fused_bwd: host_shapes is NULL (host copy of the (L, 2) level shapes)");
-    const int LP = L * P;
-    SO_REQUIRE(LP <= 256, "msda_fused_bwd: L * P must be <= 256 (got %d); use the unfused op", LP);
-    SO_REQUIRE(workspace != nullptr && workspace_bytes >= so_band_ws_bytes(bs, nq, heads, L, P),
-               "msda_fused_bwd: workspace too small (%zu bytes, need %zu)", workspace_bytes,
-               so_band_ws_bytes(bs, nq, heads, L, P));
-    SO_REQUIRE(((uintptr_t)workspace & 15) == 0, "msda_fused_bwd: workspace must be 16-byte aligned");
-    BandSetup bsu;
-    if (so_band_setup(host_shapes, bs, nq, heads, d, L, P, bsu)) return -1;
-    SO_REQUIRE(bsu.ok, "msda_fused_bwd: the banded scatter does not apply to these shapes "
-                       "(check selfocc_msda_banded_supported and use the unfused op)");
+extern "C" int selfocc_msda_bwd(const so_msda_args *args, void *stream) {
+    if (so_msda_check(args, true)) return -1;
+    const so_msda_args &a = *args;
+    if (a.bs == 0 || a.nq == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    MsdaDims dm{bs, nv, nq, heads, L, P, 0, 0, value_layout};
-    if (so_set_ol(dm, ol_stride, off_raw, logits, "msda_fused_bwd")) return -1;
-    SO_REQUIRE(g_value_stride == 0 || (g_value_stride >= heads * d && (long long)bs * nv * g_value_stride < (1LL << 31)),
-               "msda_fused_bwd: g_value_stride must be 0 or >= heads * d with bs * nv * stride < 2^31 (got %d)", g_value_stride);
-    SO_REQUIRE(ol_stride == 0 || (((uintptr_t)g_off) & 7) == 0, "msda_fused_bwd: g_off must be 8-byte aligned");
-    if (nv == 0) {   // every point is outside every (empty) map: all gradients are zero
-        if (ol_stride)   // merged rows: [offsets | logits] of a query are adjacent
-            return (int)hipMemset2DAsync(g_off, (size_t)ol_stride * sizeof(float), 0, (size_t)3 * heads * LP * sizeof(float), (size_t)bs * nq, st);
-        (void)hipMemsetAsync(g_off, 0, (size_t)n_groups * LP * 2 * sizeof(float), st);
-        return (int)hipMemsetAsync(g_logits, 0, (size_t)n_groups * LP * sizeof(float), st);
+    const MsdaDims dm = so_msda_dims(a, true);
+    const int d = a.d, LP = a.L * a.P;
+    const long long n_pts = (long long)a.bs * a.nq * a.heads * LP;
+    BandSetup bsu{};
+    if (a.host_shapes != nullptr && so_band_setup(a.host_shapes, a.bs, a.nq, a.heads, d, a.L, a.P, bsu)) return -1;
+    if (a.form == SO_MSDA_PLAIN) {
+        const float *value = (const float *)a.value;
+        const long long pblocks = (n_pts + 255) / 256;
+        SO_REQUIRE(pblocks < (1LL << 31), "msda_bwd: grid too large");
+        if (!bsu.ok) {   // no host shapes, or the banded scatter does not apply: global float atomics
+#define SO_LAUNCH(DD)                                                                                 \
+    hipLaunchKernelGGL((msda_bwd_kernel<DD>), dim3((unsigned)pblocks), dim3(256), 0, st, value,       \
+                       a.shapes, a.starts, a.loc, a.attw, a.g_out, a.g_value, a.g_loc, a.g_attw, dm)
+            switch (d) {
+                case 4: SO_LAUNCH(4); break;
+                case 8: SO_LAUNCH(8); break;
+                case 16: SO_LAUNCH(16); break;
+                default: SO_LAUNCH(32); break;
+            }
+#undef SO_LAUNCH
+            return so_launch_status();
+        }
+        const BandWorkspace w = so_band_workspace(a.workspace, a.bs, a.nq, a.heads, a.L, a.P);
+#define SO_LAUNCH(DD)                                                                                 \
+    hipLaunchKernelGGL((msda_bwd_point_kernel<DD>), dim3((unsigned)pblocks), dim3(256), 0, st, value, \
+                       a.shapes, a.starts, a.loc, a.attw, a.g_out, a.g_loc, a.g_attw, w.keys, w.recs, dm)
+        switch (d) {
+            case 4: SO_LAUNCH(4); break;
+            case 8: SO_LAUNCH(8); break;
+            case 16: SO_LAUNCH(16); break;
+            default: SO_LAUNCH(32); break;
+        }
+#undef SO_LAUNCH
+        return so_band_scatter(a.shapes, a.starts, a.g_out, a.g_value, w, bsu, dm, d, nullptr, st);
     }
-    const BandWorkspace w = so_band_workspace(workspace, bs, nq, heads, L, P);
+    // fused / camera loop: the banded scatter is part of the op
+    SO_REQUIRE(bsu.ok, "msda_bwd: the banded scatter does not apply to these shapes "
+                       "(check selfocc_msda_banded_supported and use the plain form)");
+    const long long rows = (long long)(a.form == SO_MSDA_CROSS ? 1 : a.bs) * a.nq;   // query rows of off_raw / logits
+    if (a.nv == 0) {   // every point is outside every (empty) map: all gradients are zero
+        if (a.ol_stride)   // merged rows: [offsets | logits] of a query are adjacent
+            return (int)hipMemset2DAsync(a.g_off, (size_t)a.ol_stride * sizeof(float), 0, (size_t)3 * a.heads * LP * sizeof(float),
+                                         (size_t)rows, st);
+        (void)hipMemsetAsync(a.g_off, 0, (size_t)rows * a.heads * LP * 2 * sizeof(float), st);
+        return (int)hipMemsetAsync(a.g_logits, 0, (size_t)rows * a.heads * LP * sizeof(float), st);
+    }
+    const BandWorkspace w = so_band_workspace(a.workspace, a.bs, a.nq, a.heads, a.L, a.P);
     int G = 1, logG = 0;
     so_pick_group_fused(LP, d, G, logG);
     const int gpb = 256 / G;
-    const long long blocks = (n_groups + gpb - 1) / gpb;
-    SO_REQUIRE(blocks < (1LL << 31), "msda_fused_bwd: grid too large");
-    // (counting the sort's buckets inside this kernel, as selfocc_msda_cross_bwd does, measured slower here: 454 -> 570 us for
-    // 58 us of msda_bin_kernel<false>: 32 groups per block contend for the few buckets of one plane)
+    const long long blocks = (rows * a.heads + gpb - 1) / gpb;
+    SO_REQUIRE(blocks < (1LL << 31), "msda_bwd: grid too large");
+    const bool bf16 = a.value_dtype == SO_DTYPE_BF16;
+    if (a.form == SO_MSDA_FUSED) {
+        // (counting the sort's buckets inside this kernel, as the camera loop does, measured slower here: 454 -> 570 us for
+        // 58 us of msda_bin_kernel<false>: 32 groups per block contend for the few buckets of one plane)
 #define SO_LAUNCH_VT(DD, LG, VT) \
         hipLaunchKernelGGL((msda_fused_bwd_point_kernel<DD, LG, VT>), dim3((unsigned)blocks), dim3(256), 0, st, \
-                           (const VT *)value, shapes, starts, ref, ref_kind, off_raw, logits, g_out, g_off, \
-                           g_logits, w.keys, w.recs, dm)
-    SO_FUSED_DISPATCH(d, logG, value_dtype == SO_DTYPE_BF16);
+                           (const VT *)a.value, a.shapes, a.starts, a.ref, a.ref_kind, a.off_raw, a.logits, a.g_out, a.g_off, \
+                           a.g_logits, w.keys, w.recs, dm)
+        SO_FUSED_DISPATCH(d, logG, bf16);
 #undef SO_LAUNCH_VT
-    return so_band_scatter(shapes, starts, g_out, g_value, w, bsu, dm, d, nullptr, st, false, g_value_stride);
-}
-
-
-extern "C" int selfocc_msda_cross_bwd(const void *value, const int32_t *shapes, const int32_t *starts,
-                                      const int32_t *host_shapes, const float *ref, const uint8_t *vis,
-                                      const float *off_raw, const float *logits, const float *g_out,
-                                      float *g_value, float *g_off, float *g_logits, int32_t cams, int32_t nv,
-                                      int32_t nq, int32_t heads, int32_t d, int32_t L, int32_t P, int32_t value_layout,
-                                      int32_t value_dtype, int32_t ol_stride, int32_t g_value_stride, void *workspace,
-                                      size_t workspace_bytes, void *stream) {
-    SO_REQUIRE(cams >= 1, "msda_cross_bwd: cams must be >= 1");
-    SO_REQUIRE(value_dtype == SO_DTYPE_F32 || value_dtype == SO_DTYPE_BF16, "msda_cross_bwd: bad value_dtype");
-    SO_REQUIRE(value_layout == SO_VALUE_PIXEL_MAJOR || value_layout == SO_VALUE_HEAD_MAJOR, "msda_cross_bwd: bad value_layout");
-    if (validate((const float *)value, shapes, starts, off_raw, logits, cams, nv, nq, heads, d, L, P)) return -1;
-    const long long n_groups = (long long)nq * heads;
-    if (n_groups == 0) return 0;
-    SO_REQUIRE(ref && vis && g_out && g_value && g_off && g_logits, "msda_cross_bwd: NULL pointer");
-    SO_REQUIRE(n_groups < (1LL << 31), "msda_cross_bwd: nq * heads must be < 2^31");
-    SO_REQUIRE(host_shapes != nullptr, "msda_cross_bwd: host_shapes is NULL (host copy of the (L, 2) level shapes)");
-    const int LP = L * P;
-    SO_REQUIRE(LP <= 256, "msda_cross_bwd: L * P must be <= 256 (got %d)", LP);
-    SO_REQUIRE(workspace != nullptr && workspace_bytes >= so_band_ws_bytes(cams, nq, heads, L, P),
-               "msda_cross_bwd: workspace too small (%zu bytes, need %zu)", workspace_bytes,
-               so_band_ws_bytes(cams, nq, heads, L, P));
-    SO_REQUIRE(((uintptr_t)workspace & 15) == 0, "msda_cross_bwd: workspace must be 16-byte aligned");
-    BandSetup bsu;
-    if (so_band_setup(host_shapes, cams, nq, heads, d, L, P, bsu)) return -1;
-    SO_REQUIRE(bsu.ok, "msda_cross_bwd: the banded scatter does not apply to these shapes "
-                       "(check selfocc_msda_banded_supported with bs = cams)");
-    hipStream_t st = (hipStream_t)stream;
-    const long long n_pts = (long long)cams * nq * heads * LP;
-    MsdaDims dm{cams, nv, nq, heads, L, P, 1, 0, value_layout};
-    if (so_set_ol(dm, ol_stride, off_raw, logits, "msda_cross_bwd")) return -1;
-    SO_REQUIRE(g_value_stride == 0 || (g_value_stride >= heads * d && (long long)cams * nv * g_value_stride < (1LL << 31)),
-               "msda_cross_bwd: g_value_stride must be 0 or >= heads * d with cams * nv * stride < 2^31 (got %d)", g_value_stride);
-    SO_REQUIRE(ol_stride == 0 || (((uintptr_t)g_off) & 7) == 0, "msda_cross_bwd: g_off must be 8-byte aligned");
-    if (nv == 0) {
-        if (ol_stride)
-            return (int)hipMemset2DAsync(g_off, (size_t)ol_stride * sizeof(float), 0, (size_t)3 * heads * LP * sizeof(float), (size_t)nq, st);
-        (void)hipMemsetAsync(g_off, 0, (size_t)n_groups * LP * 2 * sizeof(float), st);
-        return (int)hipMemsetAsync(g_logits, 0, (size_t)n_groups * LP * sizeof(float), st);
+        return so_band_scatter(a.shapes, a.starts, a.g_out, a.g_value, w, bsu, dm, d, nullptr, st, false, a.g_value_stride);
     }
-    const BandWorkspace w = so_band_workspace(workspace, cams, nq, heads, L, P);
+    const int cams = a.bs;
     // the point kernel writes the keys of every (camera, query) pair it visits; the bin kernels skip the others by
     // `vis` (P >= 4), otherwise the unvisited keys are preset to "outside"
-    const unsigned char *bin_vis = P >= 4 ? vis : nullptr;
+    const unsigned char *bin_vis = a.P >= 4 ? a.vis : nullptr;
     if (bin_vis == nullptr) (void)hipMemsetD16Async((hipDeviceptr_t)w.keys, (unsigned short)0x8000, (size_t)n_pts, st);
-    int G = 1, logG = 0;
-    so_pick_group_fused(LP, d, G, logG);
-    const int gpb = 256 / G;
-    const long long blocks = (n_groups + gpb - 1) / gpb;
-    SO_REQUIRE(blocks < (1LL << 31), "msda_cross_bwd: grid too large");
     // the point kernel does the sort's counting pass itself (an LDS histogram per block, flushed once) when a block's groups
     // span at most two heads and the histogram fits: saves one pass over the keys (msda_bin_kernel<false>, 0.9 ms per iteration)
-    static const bool count_env = so_env_int("SELFOCC_MSDA_COUNT_IN_POINT", 1) != 0;
     const size_t hist_need = (size_t)2 * cams * bsu.bin.nbands * 2 * sizeof(int);
-    const bool count_here = count_env && nq >= gpb && hist_need <= 32 * 1024;
+    const bool count_here = a.nq >= gpb && hist_need <= 32 * 1024;
     const size_t hist_bytes = count_here ? hist_need : 0;
     if (count_here) {
-        const size_t nb_all = (size_t)cams * heads * bsu.bin.nbands;
+        const size_t nb_all = (size_t)cams * a.heads * bsu.bin.nbands;
         (void)hipMemsetAsync(w.counters, 0, nb_all * 4 * sizeof(int32_t), st);      // cnt and cursor, before the counting kernel
     }
 #define SO_LAUNCH_VT(DD, LG, VT) \
         hipLaunchKernelGGL((msda_cross_bwd_point_kernel<DD, LG, VT>), dim3((unsigned)blocks), dim3(256), hist_bytes, st, \
-                           (const VT *)value, shapes, starts, ref, vis, off_raw, logits, g_out, g_off, g_logits, \
+                           (const VT *)a.value, a.shapes, a.starts, a.ref, a.vis, a.off_raw, a.logits, a.g_out, a.g_off, a.g_logits, \
                            w.keys, w.recs, cams, dm, count_here ? w.counters : nullptr, bsu.bin)
-    SO_FUSED_DISPATCH(d, logG, value_dtype == SO_DTYPE_BF16);
+    SO_FUSED_DISPATCH(d, logG, bf16);
 #undef SO_LAUNCH_VT
-    return so_band_scatter(shapes, starts, g_out, g_value, w, bsu, dm, d, bin_vis, st, count_here, g_value_stride);
+    return so_band_scatter(a.shapes, a.starts, a.g_out, a.g_value, w, bsu, dm, d, bin_vis, st, count_here, a.g_value_stride);
 }

@@ -13,7 +13,7 @@ from ..registry import MODELS
 from ..dropout import dropout_add
 from ..linear import (linear_wgrad, wgrad_supported, linear_fwd, linear_fwd_supported, linear_fwd_heads, linear_dgrad, dgrad_supported,
                       linear_fwd_heads_supported)
-from ..msda import (MultiScaleDeformableAttnFunction, msda_fused_inference, MSDAFusedFunction, to_head_major,
+from ..msda import (MultiScaleDeformableAttnFunction, msda_fused_inference, MSDAFusedFunction,
                     msda_fused_supported, msda_fused_kernels_built, ValueGradSink)
 
 
@@ -124,7 +124,7 @@ LINEAR_FWD_MIN_ROWS = 1024
 
 
 # inference: value_proj writes the head-major layout the MSDA kernels gather fastest from (selfocc_linear_fwd_heads: no
-# transposing copy, unlike HEAD_MAJOR_VALUE below) when the attention has 6 heads x 16 channels (every shipped config)
+# transposing copy) when the attention has 6 heads x 16 channels (every shipped config)
 HEAD_MAJOR_PROJ = os.environ.get('SELFOCC_HEAD_MAJOR_PROJ', '1') == '1'
 
 
@@ -489,11 +489,6 @@ FUSED_FFN_RELU = os.environ.get('SELFOCC_FUSED_FFN_RELU', '1') == '1'
 FUSED_DROPOUT_ADD = os.environ.get('SELFOCC_FUSED_DROPOUT', '1') == '1'
 # training path of deformable_sampling: fused prologue + MSDA in both directions (msda.MSDAFusedFunction)
 FUSED_TRAINING = True
-# True: the fused / camera-loop kernels gather from a head-major copy of the projected value, (bs, heads, nv, d), where a
-# cache line holds x-neighbours of one head.  Measured: camera-loop forward 0.87 -> 0.73 ms, fused
-# forward 0.50 -> 0.47 ms, but the transposing copy per call costs more than that (eval encoder 12.5 -> 12.9 ms), so
-# the default stays mmcv's (bs, nv, heads, d) as projected; the layout pays only if `value` is produced head-major.
-HEAD_MAJOR_VALUE = False
 # True: the projected `value` of the deformable attentions is STORED as bfloat16 for the gathers (forward and backward
 # point kernels); arithmetic and gradients stay float32.  Halves the corner segments the L1-bound gathers move
 # (BASELINE configs[1]: "bf16"); deviates from the reference's float32 MSDA by the bf16 rounding of value (~2^-9
@@ -517,7 +512,7 @@ def deformable_sampling(module, query, value, reference_points, spatial_shapes, 
         assert int((spatial_shapes[:, 0] * spatial_shapes[:, 1]).sum()) == num_value
     LP0 = module.num_levels * module.num_points
     v_hm = None
-    if (key_padding_mask is None and LP0 <= 256 and not HEAD_MAJOR_VALUE and module.value_proj.weight.shape[0] == 96
+    if (key_padding_mask is None and LP0 <= 256 and module.value_proj.weight.shape[0] == 96
             and (not torch.is_grad_enabled() or FUSED_TRAINING)):
         # the projection itself writes (bs, heads, nv, d)
         v_hm = value_proj_head_major([module.value_proj], value.reshape(bs * num_value, -1), num_value, module.num_heads)
@@ -553,11 +548,9 @@ def deformable_sampling(module, query, value, reference_points, spatial_shapes, 
         # inference: softmax + sampling-location prologue fused into the HIP kernel (no loc / weight tensors)
         if ol is None:
             logits = module.attention_weights(query).view(bs, num_query, module.num_heads, LP)
-        hm = HEAD_MAJOR_VALUE
-        if v_hm is not None:
-            value, hm = v_hm, True
-        elif HEAD_MAJOR_VALUE:
-            value = to_head_major(value)
+        hm = v_hm is not None
+        if hm:
+            value = v_hm
         if use_bf16:
             value = value.to(torch.bfloat16)
         return msda_fused_inference(value, spatial_shapes, level_start_index, reference_points, kind,
@@ -566,11 +559,9 @@ def deformable_sampling(module, query, value, reference_points, spatial_shapes, 
         # training: the same fusion in both directions (no loc / weight tensors, no softmax / normalise kernels)
         if ol is None:
             logits = module.attention_weights(query).view(bs, num_query, module.num_heads, LP)
-        hm = HEAD_MAJOR_VALUE
-        if v_hm is not None:
-            value, hm = v_hm, True
-        elif HEAD_MAJOR_VALUE:
-            value = to_head_major(value)
+        hm = v_hm is not None
+        if hm:
+            value = v_hm
         return MSDAFusedFunction.apply(value, spatial_shapes, level_start_index, reference_points, kind,
                                        ol if ol is not None else off, logits, host, hm, use_bf16, mlp,
                                        getattr(v_hm, '_so_grad_sink', None))

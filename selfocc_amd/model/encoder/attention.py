@@ -16,8 +16,7 @@ import torch.nn as nn
 from ...registry import MODELS, build_attention
 from ..bricks import (BaseModule, MultiScaleDeformableAttention, TallLinear, constant_init, xavier_init,
                       deformable_sampling, fused_linear)
-from ...msda import (msda_cross_inference, MSDACrossFunction, msda_fused_supported, msda_fused_kernels_built,
-                     to_head_major)
+from ...msda import (msda_cross_inference, MSDACrossFunction, msda_fused_supported, msda_fused_kernels_built)
 from .. import bricks
 
 
@@ -83,7 +82,7 @@ class BEVCrossAttention(BaseModule):
         self.embed_dims, self.num_cams = embed_dims, num_cams
         self.output_proj = TallLinear(embed_dims, embed_dims)
         self.batch_first = batch_first
-        self.camera_loop = True     # inference: selfocc_msda_cross_fwd instead of re-batch + scatter-add
+        self.camera_loop = True     # inference: the camera-loop MSDA (selfocc_msda_fwd, SO_MSDA_CROSS) instead of re-batch + scatter-add
         self.init_weight()
 
     def init_weight(self):
@@ -166,11 +165,11 @@ class BEVCrossAttention(BaseModule):
                              level_start_index, host_shapes=None, out=None, value_pre=None, post_norm=None):
         """No re-batch (inference: plain op; training: MSDACrossFunction under autograd).  The offset / weight linears depend on the query only, so they run once
         on the num_query rows; one HIP launch loops over the cameras that see each query and averages
-        (selfocc_msda_cross_fwd) — same arithmetic as the re-batched path, camera order preserved."""
+        (SO_MSDA_CROSS) — same arithmetic as the re-batched path, camera order preserved."""
         da = self.deformable_attention
         num_cams, heads, L, P = self.num_cams, da.num_heads, da.num_levels, da.num_points
         _, l, _, _ = value.shape                                            # (cams, nv, bs, C)
-        hm = bricks.HEAD_MAJOR_VALUE
+        hm = False
         sink = None    # (ValueGradSink, g): where the backward puts grad_value (set by bricks.value_proj_head_major)
         if value_pre is not None and value_pre.dim() == 4:
             v, hm = value_pre, True    # TPVCrossAttention already laid this plane's values out head-major
@@ -180,7 +179,7 @@ class BEVCrossAttention(BaseModule):
         else:
             vin = value.permute(2, 0, 1, 3).reshape(num_cams * l, self.embed_dims)
             v_hm = None
-            if not hm and da.value_proj.weight.shape[0] == 96:
+            if da.value_proj.weight.shape[0] == 96:
                 # the projection itself writes (cams, heads, l, d) (selfocc_linear_fwd_heads; under autograd _TallLinearHeads)
                 v_hm = bricks.value_proj_head_major([da.value_proj], vin, l, heads)
             if v_hm is not None:
@@ -188,8 +187,6 @@ class BEVCrossAttention(BaseModule):
                 sink = getattr(v, '_so_grad_sink', None)
             else:
                 v = da.value_proj(vin.view(num_cams, l, self.embed_dims)).view(num_cams, l, heads, -1)
-                if hm:
-                    v = to_head_major(v)
         vis_all = getattr(bev_masks, '_so_visible', None)                   # left by the HIP point_sampling
         visible = vis_all[:, 0] if vis_all is not None else bev_masks[:, 0].any(-1)   # (cams, Q), batch element 0 as the reference
         bf16 = bricks.VALUE_BF16 and self.embed_dims // heads == 16     # the bfloat16 gathers exist for d = 16 only
@@ -260,7 +257,7 @@ class TPVCrossAttention(BaseModule):
             if value.is_cuda and all(a.camera_loop for a in self.attns):
                 # ... and the three planes' value projections of the SAME image features are one GEMM with N = 3 C
                 # (the 68 MB input is read once instead of three times); each plane's kernel reads its column block
-                # in place (selfocc_msda_cross_fwd value_stride)
+                # in place (so_msda_args value_stride)
                 C = self.embed_dims
                 cams, l = value.shape[0], value.shape[1]
                 vin = value.permute(2, 0, 1, 3).reshape(cams * l, C)
@@ -275,11 +272,7 @@ class TPVCrossAttention(BaseModule):
                     v_all = bricks._tall_fwd(vin, w, b).view(cams, l, 3 * C)
                     if bf16:
                         v_all = v_all.to(torch.bfloat16)       # one cast for the three planes
-                    if bricks.HEAD_MAJOR_VALUE:
-                        # one transposing copy for the three planes: (plane, cams, heads, l, d), each plane dense
-                        vpre = list(v_all.view(cams, l, 3, heads0, C // heads0).permute(2, 0, 3, 1, 4).contiguous())
-                    else:
-                        vpre = [v_all[..., i * C:(i + 1) * C] for i in range(3)]
+                    vpre = [v_all[..., i * C:(i + 1) * C] for i in range(3)]
         elif (torch.is_grad_enabled() and bricks.MERGED_VALUE_PROJ_TRAIN and value.is_cuda and query[0].shape[0] == 1
               and value.shape[2] == 1 and all(a.camera_loop for a in self.attns)
               and len({a.deformable_attention.num_heads for a in self.attns}) == 1):

@@ -3,17 +3,17 @@
 native op the reference calls at
 model/encoder/bevformer/attention/image_cross_attention.py:340-342 and
 model/encoder/tpvformer/attention/cross_view_hybrid_attention.py:111-113.
-The arithmetic is csrc/msda.hip behind selfocc_msda_fwd / selfocc_msda_bwd.
+The arithmetic is csrc/msda.hip behind selfocc_msda_fwd / selfocc_msda_bwd: one ``so_msda_args`` struct per call
+(include/selfocc_hip.h), in one of three forms (plain, fused, camera loop).
 """
 import ctypes as C
-import os
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import abi
-from ._lib import lib, check, ptr, current_stream
+from ._lib import lib, check, current_stream
 
 
 def _prep(value, spatial_shapes, level_start_index, sampling_locations, attention_weights):
@@ -32,8 +32,33 @@ def _prep(value, spatial_shapes, level_start_index, sampling_locations, attentio
     return value, sh, st, loc, aw, (bs, nv, nq, heads, d, L, P)
 
 
-# 'banded': selfocc_msda_bwd_banded (LDS f64 accumulation, default); 'atomic': selfocc_msda_bwd (global float
-# atomics; what a C caller without host shapes / workspace gets).  Same gradients up to summation order.
+def _msda_args(form, sizes, workspace_on=None, **fields):
+    """The so_msda_args of one call.  ``sizes`` = (bs, nv, nq, heads, d, L, P); a tensor field is passed as its device
+    pointer, anything else as it is (an int, or None for NULL); ``host_shapes`` (a list) becomes a host int32 array.
+    ``workspace_on``: the device on which to allocate the banded backward's workspace.  The struct holds on to every tensor
+    and array it points into (``keep``) for as long as it lives."""
+    a = abi.SoMsdaArgs(form, *sizes)
+    keep = []
+    for name, v in fields.items():
+        if isinstance(v, torch.Tensor):
+            keep.append(v)
+            v = v.data_ptr()
+        elif name == 'host_shapes' and v is not None:
+            v = (C.c_int32 * len(v))(*v)
+            keep.append(v)
+            v = C.addressof(v)
+        setattr(a, name, v)
+    if workspace_on is not None:
+        nbytes = int(lib().selfocc_msda_ws_bytes(a))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=workspace_on)
+        keep.append(ws)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    a.keep = keep
+    return a
+
+
+# 'banded': the plain backward with host shapes and a workspace (LDS f64 accumulation, default); 'atomic': without them
+# (global float atomics; what a C caller without host shapes / workspace gets).  Same gradients up to summation order.
 BACKWARD_MODE = 'banded'
 
 
@@ -51,9 +76,8 @@ class MultiScaleDeformableAttnFunction(Function):
                                              sampling_locations, attention_weights)
         bs, nv, nq, heads, d, L, P = dims
         out = torch.empty(bs, nq, heads * d, device=value.device, dtype=torch.float32)
-        check(lib().selfocc_msda_fwd(ptr(value), ptr(sh), ptr(st), ptr(loc), ptr(aw), ptr(out),
-                                     bs, nv, nq, heads, d, L, P, current_stream(value.device)),
-              "selfocc_msda_fwd")
+        a = _msda_args(abi.MSDA_PLAIN, dims, value=value, shapes=sh, starts=st, loc=loc, attw=aw, out=out)
+        check(lib().selfocc_msda_fwd(a, current_stream(value.device)), "selfocc_msda_fwd")
         ctx.save_for_backward(value, sh, st, loc, aw)
         ctx.dims = dims
         # host copy of the level shapes for the banded backward's work decomposition (no device read-back
@@ -68,26 +92,15 @@ class MultiScaleDeformableAttnFunction(Function):
     @once_differentiable
     def backward(ctx, grad_output):
         value, sh, st, loc, aw = ctx.saved_tensors
-        bs, nv, nq, heads, d, L, P = ctx.dims
-        g_out = grad_output.contiguous().float()
+        L = ctx.dims[5]
         g_value = torch.zeros_like(value)
         g_loc = torch.empty_like(loc)
         g_aw = torch.empty_like(aw)
-        if ctx.host_shapes is not None and L <= 8 and BACKWARD_MODE == 'banded':
-            import ctypes
-            arr = (ctypes.c_int32 * len(ctx.host_shapes))(*ctx.host_shapes)
-            nbytes = int(lib().selfocc_msda_bwd_banded_workspace(bs, nq, heads, L, P))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=value.device)
-            check(lib().selfocc_msda_bwd_banded(ptr(value), ptr(sh), ptr(st), ctypes.cast(arr, ctypes.c_void_p),
-                                                ptr(loc), ptr(aw), ptr(g_out), ptr(g_value), ptr(g_loc), ptr(g_aw),
-                                                bs, nv, nq, heads, d, L, P, ptr(ws), nbytes,
-                                                current_stream(value.device)),
-                  "selfocc_msda_bwd_banded")
-        else:
-            check(lib().selfocc_msda_bwd(ptr(value), ptr(sh), ptr(st), ptr(loc), ptr(aw), ptr(g_out),
-                                         ptr(g_value), ptr(g_loc), ptr(g_aw),
-                                         bs, nv, nq, heads, d, L, P, current_stream(value.device)),
-                  "selfocc_msda_bwd")
+        host = ctx.host_shapes if (L <= 8 and BACKWARD_MODE == 'banded') else None     # None: the atomic scatter
+        a = _msda_args(abi.MSDA_PLAIN, ctx.dims, value.device if host is not None else None, value=value, shapes=sh,
+                       starts=st, loc=loc, attw=aw, g_out=grad_output.contiguous().float(), g_value=g_value, g_loc=g_loc,
+                       g_attw=g_aw, host_shapes=host)
+        check(lib().selfocc_msda_bwd(a, current_stream(value.device)), "selfocc_msda_bwd")
         return g_value, None, None, g_loc, g_aw, None
 
 
@@ -146,24 +159,61 @@ def _value_dims(value, head_major):
 
 
 def _off_logits_args(sampling_offsets, attention_logits, heads, merged_LP):
-    """(off tensor kept alive, off pointer, logits pointer, nq-leading shape, L, P, ol_stride) for the fused / camera-loop
-    entry points.  Two forms: the dense pair ``sampling_offsets (..., nq, h, L, P, 2)`` + ``attention_logits (..., nq, h, L*P)``,
-    or — ``attention_logits is None`` — ONE merged projection output ``sampling_offsets (..., nq, 3 * h * L * P)`` whose rows
-    are [h*L*P*2 raw offsets | h*L*P logits] (the stacked sampling_offsets | attention_weights Linear, ABI 32 ``ol_stride``);
+    """(off_raw tensor, logits tensor or pointer, nq-leading shape, L, P, ol_stride) for the fused / camera-loop forms.  Two
+    forms: the dense pair ``sampling_offsets (..., nq, h, L, P, 2)`` + ``attention_logits (..., nq, h, L*P)``, or —
+    ``attention_logits is None`` — ONE merged projection output ``sampling_offsets (..., nq, 3 * h * L * P)`` whose rows are
+    [h*L*P*2 raw offsets | h*L*P logits] (the stacked sampling_offsets | attention_weights Linear, ABI 32 ``ol_stride``);
     ``merged_LP = (L, P)``."""
-    import ctypes
     if attention_logits is not None:
         off = sampling_offsets.contiguous().float()
         lg = attention_logits.contiguous().float()
         L, P = off.shape[-3], off.shape[-2]
-        return (off, lg), ptr(off), ptr(lg), off.shape[:-4], L, P, 0
+        return off, lg, off.shape[:-4], L, P, 0
     L, P = merged_LP
     ol = sampling_offsets
     n = 3 * heads * L * P
     assert ol.shape[-1] == n and ol.dtype == torch.float32, (tuple(ol.shape), n)
     if ol.stride(-1) != 1 or (ol.dim() > 1 and ol.stride(-2) % 2) or not ol.reshape(-1, n).is_contiguous():
         ol = ol.contiguous()
-    return (ol,), ptr(ol), ctypes.c_void_p(ol.data_ptr() + 8 * heads * L * P), ol.shape[:-1], L, P, n
+    return ol, ol.data_ptr() + 8 * heads * L * P, ol.shape[:-1], L, P, n
+
+
+def _sampling_fields(form, value, sh, st, ref, ref_kind, vis, sampling_offsets, attention_logits, head_major, merged_LP,
+                     bwd):
+    """(sizes, so_msda_args fields) shared by both directions of the fused (``vis`` None) and camera-loop forms.  The
+    camera-loop forward reads a pixel-major ``value`` that is a column block of a wider (cams * nv, N) matrix in place
+    (``value_stride``); everything else gets a dense copy."""
+    bs, nv, heads, d = _value_dims(value, head_major)
+    off, lg, lead, L, P, ols = _off_logits_args(sampling_offsets, attention_logits, heads, merged_LP)
+    nq = lead[-1]
+    vstride = 0
+    if (form == abi.MSDA_CROSS and not bwd and not head_major and value.dtype in (torch.float32, torch.bfloat16)
+            and not value.is_contiguous() and value.stride(3) == 1 and value.stride(2) == d
+            and value.stride(1) % 4 == 0 and value.stride(0) == nv * value.stride(1)):
+        vstride = value.stride(1)        # a column block of a wider (cams * nv, N) matrix: no copy
+        vdt = abi.DTYPE_BF16 if value.dtype == torch.bfloat16 else abi.DTYPE_F32
+    else:
+        value, vdt = _value_arg(value)
+    ref = ref.contiguous().float()
+    if vis is not None:
+        assert ref.shape == (bs, nq, P, 2) and vis.shape == (bs, nq)
+    return (bs, nv, nq, heads, d, L, P), dict(
+        value=value, value_layout=int(bool(head_major)), value_dtype=vdt, value_stride=vstride, shapes=sh, starts=st,
+        ref=ref, ref_kind=ref_kind, vis=vis, off_raw=off, logits=lg, ol_stride=ols)
+
+
+def _sampling_fwd(form, value, sh, st, ref, ref_kind, vis, sampling_offsets, attention_logits, head_major, merged_LP):
+    if not value.is_cuda:
+        what = "msda_cross_inference" if form == abi.MSDA_CROSS else "msda_fused_inference"
+        raise RuntimeError(f"{what} needs CUDA(HIP) tensors: selfocc_amd has no CPU fallback")
+    sizes, fields = _sampling_fields(form, value, sh, st, ref, ref_kind, vis, sampling_offsets, attention_logits,
+                                     head_major, merged_LP, bwd=False)
+    bs, nv, nq, heads, d = sizes[:5]
+    rows = (nq,) if form == abi.MSDA_CROSS else (bs, nq)
+    out = torch.empty(*rows, heads * d, device=value.device, dtype=torch.float32)
+    check(lib().selfocc_msda_fwd(_msda_args(form, sizes, out=out, **fields), current_stream(value.device)),
+          "selfocc_msda_fwd")
+    return out
 
 
 def msda_fused_inference(value, spatial_shapes, level_start_index, reference_points, ref_kind, sampling_offsets,
@@ -172,20 +222,9 @@ def msda_fused_inference(value, spatial_shapes, level_start_index, reference_poi
     reference_points per ``ref_kind``
     (0: (bs,nq,L,2), 1: (bs,nq,P,2), 2: (bs,nq,L,P,2)); sampling_offsets (bs,nq,h,L,P,2) raw linear
     output; attention_logits (bs,nq,h,L*P) before softmax.  Returns (bs, nq, h*d)."""
-    if not value.is_cuda:
-        raise RuntimeError("msda_fused_inference needs CUDA(HIP) tensors: selfocc_amd has no CPU fallback")
-    bs, nv, heads, d = _value_dims(value, head_major)
-    keep, p_off, p_lg, lead, L, P, ols = _off_logits_args(sampling_offsets, attention_logits, heads, merged_LP)
-    nq = lead[-1]
-    value, vdt = _value_arg(value)
-    ref = reference_points.contiguous().float()
     sh, st = _i32(spatial_shapes, value.device), _i32(level_start_index, value.device)
-    out = torch.empty(bs, nq, heads * d, device=value.device, dtype=torch.float32)
-    check(lib().selfocc_msda_fused_fwd(ptr(value), ptr(sh), ptr(st), ptr(ref), int(ref_kind), p_off, p_lg,
-                                       ptr(out), bs, nv, nq, heads, d, L, P, int(bool(head_major)), vdt, ols,
-                                       current_stream(value.device)),
-          "selfocc_msda_fused_fwd")
-    return out
+    return _sampling_fwd(abi.MSDA_FUSED, value, sh, st, reference_points, int(ref_kind), None, sampling_offsets,
+                         attention_logits, head_major, merged_LP)
 
 
 def msda_cross_inference(value, spatial_shapes, level_start_index, reference_points_cam, visible,
@@ -195,41 +234,20 @@ def msda_cross_inference(value, spatial_shapes, level_start_index, reference_poi
     value (cams,nv,h,d), or (cams,h,nv,d) with ``head_major``; reference_points_cam (cams,nq,P,2); visible (cams,nq) bool — the cameras that see
     each query; sampling_offsets (nq,h,L,P,2) and attention_logits (nq,h,L*P): the raw linear outputs for
     the UN-rebatched queries.  Returns (nq, h*d): the mean over the visible cameras."""
-    if not value.is_cuda:
-        raise RuntimeError("msda_cross_inference needs CUDA(HIP) tensors: selfocc_amd has no CPU fallback")
-    cams, nv, heads, d = _value_dims(value, head_major)
-    keep, p_off, p_lg, lead, L, P, ols = _off_logits_args(sampling_offsets, attention_logits, heads, merged_LP)
-    nq = lead[-1]
-    vstride = 0
-    vdt = abi.DTYPE_BF16 if value.dtype == torch.bfloat16 else abi.DTYPE_F32
-    if (not head_major and value.dtype in (torch.float32, torch.bfloat16) and not value.is_contiguous()
-            and value.stride(3) == 1 and value.stride(2) == d
-            and value.stride(1) % 4 == 0 and value.stride(0) == nv * value.stride(1)):
-        vstride = value.stride(1)        # a column block of a wider (cams * nv, N) matrix: no copy
-    else:
-        value, vdt = _value_arg(value)
-    ref = reference_points_cam.contiguous().float()
-    vis = _u8(visible)
-    assert ref.shape == (cams, nq, P, 2) and vis.shape == (cams, nq)
     sh, st = _i32(spatial_shapes, value.device), _i32(level_start_index, value.device)
-    out = torch.empty(nq, heads * d, device=value.device, dtype=torch.float32)
-    check(lib().selfocc_msda_cross_fwd(ptr(value), ptr(sh), ptr(st), ptr(ref), ptr(vis), p_off, p_lg,
-                                       ptr(out), cams, nv, nq, heads, d, L, P, vstride, int(bool(head_major)), vdt, ols,
-                                       current_stream(value.device)),
-          "selfocc_msda_cross_fwd")
-    return out
+    return _sampling_fwd(abi.MSDA_CROSS, value, sh, st, reference_points_cam, 0, _u8(visible), sampling_offsets,
+                         attention_logits, head_major, merged_LP)
 
 
 def _grad_value_target(grad_sink, value, B, nv, heads, d):
-    """(tensor returned as grad_value, pointer handed to the kernel, g_value_stride): a fresh zeroed tensor in the layout of
-    ``value``, or — with a ValueGradSink — this attention's column block of the shared row-major buffer"""
-    import ctypes
+    """(tensor returned as grad_value, tensor or pointer handed to the kernel, g_value_stride): a fresh zeroed tensor in the
+    layout of ``value``, or — with a ValueGradSink — this attention's column block of the shared row-major buffer"""
     if grad_sink is None:
         g_value = torch.zeros(value.shape, device=value.device, dtype=torch.float32)
-        return g_value, ptr(g_value), 0
+        return g_value, g_value, 0
     sink, g = grad_sink
     buf = sink.slot(g, B, nv, heads, d, value.device)
-    return (buf[:, :, g].permute(0, 2, 1, 3), ctypes.c_void_p(buf.data_ptr() + 4 * g * heads * d), sink.G * heads * d)
+    return buf[:, :, g].permute(0, 2, 1, 3), buf.data_ptr() + 4 * g * heads * d, sink.G * heads * d
 
 
 class ValueGradSink:
@@ -266,63 +284,73 @@ class ValueGradSink:
         return buf.view(buf.shape[0] * buf.shape[1], -1)
 
 
-class MSDAFusedFunction(torch.autograd.Function):
-    """Training form of the fused op: out = MSDA(value, ref + off / (W_l, H_l), softmax(logits)) with the
-    prologue inside the kernels in BOTH directions.  The forward saves only its inputs (no sampling_locations /
-    attention_weights tensors); the backward returns gradients w.r.t. value, the raw offsets and the raw
-    logits (``selfocc_msda_fused_bwd``).  Same math as softmax -> loc -> MultiScaleDeformableAttnFunction."""
+class _SamplingFunction(torch.autograd.Function):
+    """Autograd of the fused and camera-loop forms (MSDAFusedFunction, MSDACrossFunction): the prologue inside the kernels
+    in BOTH directions.  The forward saves only its inputs (no sampling_locations / attention_weights tensors); the
+    backward returns gradients w.r.t. value, the raw offsets and the raw logits.  ``attention_logits is None``:
+    ``sampling_offsets`` is the merged projection output (..., nq, 3 h L P) (rows [offsets | logits], ``merged_LP = (L, P)``)
+    and the backward returns ONE gradient of that shape.  ``grad_sink = (ValueGradSink, g)`` (head-major float32 value
+    only): grad_value is written pixel-major into the sink."""
 
     @staticmethod
-    def forward(ctx, value, spatial_shapes, level_start_index, reference_points, ref_kind, sampling_offsets,
-                attention_logits, host_shapes, head_major=False, value_bf16=False, merged_LP=None, grad_sink=None):
-        """``attention_logits is None``: ``sampling_offsets`` is the merged projection output (bs, nq, 3 h L P) (rows
-        [offsets | logits], ``merged_LP = (L, P)``) and the backward returns ONE gradient of that shape.
-        ``grad_sink = (ValueGradSink, g)`` (head-major float32 value only): grad_value is written pixel-major into the sink."""
+    def run(ctx, form, value, spatial_shapes, level_start_index, ref, ref_kind, visible, sampling_offsets,
+            attention_logits, host_shapes, head_major, value_bf16, merged_LP, grad_sink):
         ctx.grad_sink = grad_sink if (head_major and not value_bf16) else None
         if value_bf16:      # bfloat16 STORAGE of value for the gathers (forward and backward); gradients stay float32
             value = value.to(torch.bfloat16)
-        out = msda_fused_inference(value, spatial_shapes, level_start_index, reference_points, ref_kind,
-                                   sampling_offsets, attention_logits, head_major, merged_LP)
-        ctx.head_major = bool(head_major)
+        vis = None if visible is None else _u8(visible)
         sh, st = _i32(spatial_shapes, value.device), _i32(level_start_index, value.device)
+        out = _sampling_fwd(form, value, sh, st, ref, ref_kind, vis, sampling_offsets, attention_logits, head_major,
+                            merged_LP)
+        ctx.form, ctx.ref_kind, ctx.head_major, ctx.host_shapes = form, ref_kind, bool(head_major), list(host_shapes)
         ctx.merged_LP = merged_LP if attention_logits is None else None
-        if ctx.merged_LP is None:
-            ctx.save_for_backward(value, sh, st, reference_points, sampling_offsets, attention_logits)
-        else:
-            ctx.save_for_backward(value, sh, st, reference_points, sampling_offsets)
-        ctx.ref_kind, ctx.host_shapes = int(ref_kind), list(host_shapes)
+        ctx.save_for_backward(value, sh, st, ref, vis, sampling_offsets, attention_logits)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_output):
-        import ctypes
-        if ctx.merged_LP is None:
-            value, sh, st, ref, off, lg = ctx.saved_tensors
-        else:
-            (value, sh, st, ref, off), lg = ctx.saved_tensors, None
-        ref = ref.contiguous().float()
-        value, vdt = _value_arg(value)
-        bs, nv, heads, d = _value_dims(value, ctx.head_major)
-        keep, p_off, p_lg, lead, L, P, ols = _off_logits_args(off, lg, heads, ctx.merged_LP)
-        nq = lead[-1]
-        g_out = grad_output.contiguous().float()
-        g_value, p_gv, gvs = _grad_value_target(ctx.grad_sink, value, bs, nv, heads, d)
+        value, sh, st, ref, vis, off, lg = ctx.saved_tensors
+        sizes, fields = _sampling_fields(ctx.form, value, sh, st, ref, ctx.ref_kind, vis, off, lg, ctx.head_major,
+                                         ctx.merged_LP, bwd=True)
+        bs, nv, nq, heads, d, L, P = sizes
+        value, ols = fields['value'], fields['ol_stride']
+        g_value, gv, gvs = _grad_value_target(ctx.grad_sink, value, bs, nv, heads, d)
         if ols:
-            g_off = torch.empty(*lead, ols, device=value.device, dtype=torch.float32)
-            g_lg, pg_lg = None, ctypes.c_void_p(g_off.data_ptr() + 8 * heads * L * P)
+            g_off = torch.empty(*fields['off_raw'].shape[:-1], ols, device=value.device, dtype=torch.float32)
+            g_lg, pg_lg = None, g_off.data_ptr() + 8 * heads * L * P
         else:
-            g_off, g_lg = torch.empty_like(keep[0]), torch.empty_like(keep[1])
-            pg_lg = ptr(g_lg)
-        arr = (ctypes.c_int32 * len(ctx.host_shapes))(*ctx.host_shapes)
-        nbytes = int(lib().selfocc_msda_bwd_banded_workspace(bs, nq, heads, L, P))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=value.device)
-        check(lib().selfocc_msda_fused_bwd(ptr(value), ptr(sh), ptr(st), ctypes.cast(arr, ctypes.c_void_p), ptr(ref),
-                                           ctx.ref_kind, p_off, p_lg, ptr(g_out), p_gv, ptr(g_off),
-                                           pg_lg, bs, nv, nq, heads, d, L, P, int(ctx.head_major), vdt, ols, gvs, ptr(ws), nbytes,
-                                           current_stream(value.device)),
-              "selfocc_msda_fused_bwd")
+            g_off, g_lg = torch.empty_like(fields['off_raw']), torch.empty_like(fields['logits'])
+            pg_lg = g_lg
+        a = _msda_args(ctx.form, sizes, value.device, g_out=grad_output.contiguous().float(), g_value=gv,
+                       g_value_stride=gvs, g_off=g_off, g_logits=pg_lg, host_shapes=ctx.host_shapes, **fields)
+        check(lib().selfocc_msda_bwd(a, current_stream(value.device)), "selfocc_msda_bwd")
         return g_value, None, None, None, None, g_off, g_lg, None, None, None, None, None
+
+
+class MSDAFusedFunction(_SamplingFunction):
+    """Training form of the fused op: out = MSDA(value, ref + off / (W_l, H_l), softmax(logits)); same math as softmax ->
+    loc -> MultiScaleDeformableAttnFunction.  See _SamplingFunction."""
+
+    @staticmethod
+    def forward(ctx, value, spatial_shapes, level_start_index, reference_points, ref_kind, sampling_offsets,
+                attention_logits, host_shapes, head_major=False, value_bf16=False, merged_LP=None, grad_sink=None):
+        return _SamplingFunction.run(ctx, abi.MSDA_FUSED, value, spatial_shapes, level_start_index, reference_points,
+                                     int(ref_kind), None, sampling_offsets, attention_logits, host_shapes, head_major,
+                                     value_bf16, merged_LP, grad_sink)
+
+
+class MSDACrossFunction(_SamplingFunction):
+    """Training form of ``msda_cross_inference``: the camera-loop sampling stage of BEVCrossAttention under
+    autograd.  Differentiable inputs: value (cams,nv,h,d), sampling_offsets (nq,h,L,P,2), attention_logits
+    (nq,h,L*P); the reference points and the visibility mask are geometry (no gradient).  See _SamplingFunction."""
+
+    @staticmethod
+    def forward(ctx, value, spatial_shapes, level_start_index, reference_points_cam, visible, sampling_offsets,
+                attention_logits, host_shapes, head_major=False, value_bf16=False, merged_LP=None, grad_sink=None):
+        return _SamplingFunction.run(ctx, abi.MSDA_CROSS, value, spatial_shapes, level_start_index, reference_points_cam,
+                                     0, visible, sampling_offsets, attention_logits, host_shapes, head_major,
+                                     value_bf16, merged_LP, grad_sink)
 
 
 def msda_fused_kernels_built(d, value_bf16=False):
@@ -333,66 +361,7 @@ def msda_fused_kernels_built(d, value_bf16=False):
 
 def msda_fused_supported(host_shapes, bs, nq, heads, d, L, P, value_bf16=False):
     """True when the fused training op applies (banded scatter possible, L * P <= 256)."""
-    import ctypes
     if L * P > 256 or L > 8 or not msda_fused_kernels_built(d, value_bf16):
         return False
-    arr = (ctypes.c_int32 * len(host_shapes))(*host_shapes)
-    return lib().selfocc_msda_banded_supported(ctypes.cast(arr, ctypes.c_void_p), bs, nq, heads, d, L, P) == 1
-
-
-class MSDACrossFunction(torch.autograd.Function):
-    """Training form of ``msda_cross_inference``: the camera-loop sampling stage of BEVCrossAttention under
-    autograd.  Differentiable inputs: value (cams,nv,h,d), sampling_offsets (nq,h,L,P,2), attention_logits
-    (nq,h,L*P); the reference points and the visibility mask are geometry (no gradient)."""
-
-    @staticmethod
-    def forward(ctx, value, spatial_shapes, level_start_index, reference_points_cam, visible, sampling_offsets,
-                attention_logits, host_shapes, head_major=False, value_bf16=False, merged_LP=None, grad_sink=None):
-        """``attention_logits is None``: ``sampling_offsets`` is the merged projection output (nq, 3 h L P); ``grad_sink``: see
-        MSDAFusedFunction."""
-        ctx.grad_sink = grad_sink if (head_major and not value_bf16) else None
-        if value_bf16:
-            value = value.to(torch.bfloat16)
-        out = msda_cross_inference(value, spatial_shapes, level_start_index, reference_points_cam, visible,
-                                   sampling_offsets, attention_logits, head_major, merged_LP)
-        ctx.head_major = bool(head_major)
-        sh, st = _i32(spatial_shapes, value.device), _i32(level_start_index, value.device)
-        ctx.merged_LP = merged_LP if attention_logits is None else None
-        if ctx.merged_LP is None:
-            ctx.save_for_backward(value, sh, st, reference_points_cam, _u8(visible), sampling_offsets, attention_logits)
-        else:
-            ctx.save_for_backward(value, sh, st, reference_points_cam, _u8(visible), sampling_offsets)
-        ctx.host_shapes = list(host_shapes)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_output):
-        import ctypes
-        if ctx.merged_LP is None:
-            value, sh, st, ref, vis, off, lg = ctx.saved_tensors
-        else:
-            (value, sh, st, ref, vis, off), lg = ctx.saved_tensors, None
-        ref = ref.contiguous().float()
-        value, vdt = _value_arg(value)
-        vis = vis.contiguous()
-        cams, nv, heads, d = _value_dims(value, ctx.head_major)
-        keep, p_off, p_lg, lead, L, P, ols = _off_logits_args(off, lg, heads, ctx.merged_LP)
-        nq = lead[-1]
-        g_out = grad_output.contiguous().float()
-        g_value, p_gv, gvs = _grad_value_target(ctx.grad_sink, value, cams, nv, heads, d)
-        if ols:
-            g_off = torch.empty(*lead, ols, device=value.device, dtype=torch.float32)
-            g_lg, pg_lg = None, ctypes.c_void_p(g_off.data_ptr() + 8 * heads * L * P)
-        else:
-            g_off, g_lg = torch.empty_like(keep[0]), torch.empty_like(keep[1])
-            pg_lg = ptr(g_lg)
-        arr = (ctypes.c_int32 * len(ctx.host_shapes))(*ctx.host_shapes)
-        nbytes = int(lib().selfocc_msda_bwd_banded_workspace(cams, nq, heads, L, P))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=value.device)
-        check(lib().selfocc_msda_cross_bwd(ptr(value), ptr(sh), ptr(st), ctypes.cast(arr, ctypes.c_void_p), ptr(ref),
-                                           ptr(vis), p_off, p_lg, ptr(g_out), p_gv, ptr(g_off),
-                                           pg_lg, cams, nv, nq, heads, d, L, P, int(ctx.head_major), vdt, ols, gvs, ptr(ws),
-                                           nbytes, current_stream(value.device)),
-              "selfocc_msda_cross_bwd")
-        return g_value, None, None, None, None, g_off, g_lg, None, None, None, None, None
+    a = _msda_args(abi.MSDA_FUSED, (bs, 0, nq, heads, d, L, P), host_shapes=host_shapes)
+    return lib().selfocc_msda_banded_supported(a) == 1

@@ -31,6 +31,7 @@ def test_struct_layouts_match_header(tmp_path):
               ("so_query_args", "sem_argmax", abi.SoQueryArgs), ("so_occ_args", "sem", abi.SoOccArgs),
               ("so_occ_args", "thresh", abi.SoOccArgs), ("so_reproj_args", "wnorm", abi.SoReprojArgs),
               ("so_reproj_args", "img_h", abi.SoReprojArgs)]
+    fields += [("so_msda_args", f, abi.SoMsdaArgs) for f, _ in abi.SoMsdaArgs._fields_]
     body = "\n".join(f'printf("%zu %zu\\n", sizeof({s}), offsetof({s}, {f}));' for s, f, _ in fields)
     src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{ROOT}/include/selfocc_hip.h"\n'
                    f'int main(void) {{ {body} return 0; }}\n')
@@ -52,15 +53,21 @@ def test_product_never_imports_the_oracle():
                 assert 'liboracle' not in txt and 'oracle_render_fwd' not in txt, os.path.join(dirpath, fn)
 
 
-def test_banded_support_query_is_pure_host_logic():
-    """selfocc_msda_banded_supported / _workspace run without a GPU: decomposition decisions only."""
+def _msda_args(form, bs, nq, heads, d, L, P, host_shapes=None, nv=0):
+    a = abi.SoMsdaArgs(form, bs, nv, nq, heads, d, L, P)
+    if host_shapes is not None:
+        a.keep = (C.c_int32 * (2 * len(host_shapes)))(*[v for hw in host_shapes for v in hw])
+        a.host_shapes = C.addressof(a.keep)
+    return a
+
+
+def test_msda_banded_support_query_is_pure_host_logic():
+    """selfocc_msda_banded_supported / _ws_bytes run without a GPU: decomposition decisions only."""
     from selfocc_amd._lib import lib
     l = lib()
 
     def sup(shapes, bs, nq, heads, d, P):
-        L = len(shapes)
-        arr = (C.c_int32 * (2 * L))(*[v for hw in shapes for v in hw])
-        return l.selfocc_msda_banded_supported(C.cast(arr, C.c_void_p), bs, nq, heads, d, L, P)
+        return l.selfocc_msda_banded_supported(_msda_args(abi.MSDA_FUSED, bs, nq, heads, d, len(shapes), P, shapes))
 
     fpn = [(96, 200), (48, 100), (24, 50), (12, 25)]
     assert sup(fpn, 6, 22016, 6, 16, 8) == 1                      # nuscenes_occ cross-attention
@@ -71,8 +78,48 @@ def test_banded_support_query_is_pure_host_logic():
     assert sup(fpn, 6, 22016, 6, 6, 8) < 0                        # bad channel count: argument error
     assert b"channels per head" in l.selfocc_last_error()
     n = 6 * 22016 * 6 * 4 * 8
-    ws = l.selfocc_msda_bwd_banded_workspace(6, 22016, 6, 4, 8)
+    ws = l.selfocc_msda_ws_bytes(_msda_args(abi.MSDA_CROSS, 6, 22016, 6, 16, 4, 8))
     assert ws >= 18 * n and ws % 16 == 0
+
+
+def test_msda_argument_checks_are_pure_host_logic():
+    """every rejection of the MSDA validator happens before any HIP call: < 0 and a key word in selfocc_last_error()"""
+    from selfocc_amd._lib import lib
+    l = lib()
+    heads, d, L, P, nq = 6, 16, 2, 4, 33
+    shapes = [(6, 10), (3, 5)]
+    fake = C.create_string_buffer(64)      # never dereferenced: every call below fails its checks first
+
+    def call(form, bwd=False, **kw):
+        a = _msda_args(form, 2 if form == abi.MSDA_CROSS else 1, nq, heads, d, L, P, shapes, nv=75)
+        for f in ("value", "shapes", "starts", "loc", "attw", "ref", "vis", "off_raw", "logits", "out", "g_out", "g_value",
+                  "g_loc", "g_attw", "g_off", "g_logits", "workspace"):
+            setattr(a, f, C.addressof(fake))
+        a.workspace_bytes = l.selfocc_msda_ws_bytes(a)
+        for k, v in kw.items():
+            setattr(a, k, v)
+        rc = (l.selfocc_msda_bwd if bwd else l.selfocc_msda_fwd)(a, None)
+        return rc, l.selfocc_last_error()
+
+    cases = [
+        (dict(form=3), b"form"),
+        (dict(form=abi.MSDA_PLAIN, d=6), b"channels per head"),
+        (dict(form=abi.MSDA_FUSED, ref_kind=3), b"ref_kind"),
+        (dict(form=abi.MSDA_FUSED, ol_stride=3 * heads * L * P + 1), b"ol_stride"),
+        (dict(form=abi.MSDA_CROSS, ol_stride=3 * heads * L * P - 2), b"ol_stride"),
+        (dict(form=abi.MSDA_FUSED, bwd=True, g_value_stride=heads * d - 4), b"g_value_stride"),
+        (dict(form=abi.MSDA_FUSED, bwd=True, workspace=None), b"workspace"),
+        (dict(form=abi.MSDA_CROSS, vis=None), b"vis"),
+        (dict(form=abi.MSDA_CROSS, bwd=True, vis=None), b"vis"),
+    ]
+    for kw, word in cases:
+        kw = dict(kw)
+        form = kw.pop("form")
+        rc, err = call(form, **kw)
+        assert rc < 0 and word in err, (form, kw, rc, err)
+    # a bad form is rejected by the two host queries as well
+    assert l.selfocc_msda_banded_supported(_msda_args(3, 1, nq, heads, d, L, P, shapes)) < 0
+    assert l.selfocc_msda_ws_bytes(_msda_args(3, 1, nq, heads, d, L, P)) == 0
 
 
 def test_render_bwd_scatter_workspace_size_is_pure_host_logic():

@@ -621,11 +621,11 @@ def test_odd_offset_logit_row_stride_trains_through_the_two_linears(hip, monkeyp
     assert not bad, (bad, errs)
 
 
-def test_abi32_stride_arguments_are_validated_at_the_c_boundary(hip):
-    """ol_stride / g_value_stride of the fused entry points (include/selfocc_hip.h, ABI 32): a bad value is an error string,
+def test_msda_args_strides_are_validated_at_the_c_boundary(hip):
+    """ol_stride / g_value_stride of so_msda_args (include/selfocc_hip.h; the fields of ABI 32): a bad value is an error string,
     never a wild write."""
     import ctypes as C
-    from selfocc_amd._lib import lib, ptr, current_stream
+    from selfocc_amd._lib import lib, current_stream
     from selfocc_amd import abi
     d0 = torch.device("cuda:0")
     heads, d, L, P, nq, bs = 6, 16, 2, 4, 33, 1
@@ -636,13 +636,20 @@ def test_abi32_stride_arguments_are_validated_at_the_c_boundary(hip):
     ref = torch.rand(bs, nq, L, 2, device=d0)
     ol = torch.randn(bs, nq, 3 * heads * LP, device=d0)
     out = torch.empty(bs, nq, heads * d, device=d0)
-    lg_ptr = C.c_void_p(ol.data_ptr() + 8 * heads * LP)
     st = current_stream(d0)
     l = lib()
 
+    def args(ols, **kw):
+        a = abi.SoMsdaArgs(abi.MSDA_FUSED, bs, nv, nq, heads, d, L, P)
+        a.value_layout, a.value_dtype, a.ol_stride = abi.VALUE_HEAD_MAJOR, abi.DTYPE_F32, ols
+        a.value, a.shapes, a.starts, a.ref = value.data_ptr(), shapes.data_ptr(), starts.data_ptr(), ref.data_ptr()
+        a.off_raw, a.logits, a.out = ol.data_ptr(), ol.data_ptr() + 8 * heads * LP, out.data_ptr()
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
     def fwd(ols):
-        return l.selfocc_msda_fused_fwd(ptr(value), ptr(shapes), ptr(starts), ptr(ref), 0, ptr(ol), lg_ptr, ptr(out), bs, nv, nq, heads,
-                                        d, L, P, 1, abi.DTYPE_F32, ols, st)
+        return l.selfocc_msda_fwd(args(ols), st)
     assert fwd(3 * heads * LP) == 0
     for bad in (3 * heads * LP - 2, 3 * heads * LP + 1, -4):
         assert fwd(bad) != 0 and b"ol_stride" in l.selfocc_last_error()
@@ -650,13 +657,13 @@ def test_abi32_stride_arguments_are_validated_at_the_c_boundary(hip):
     g_out = torch.randn(bs, nq, heads * d, device=d0)
     g_ol = torch.empty_like(ol)
     g_rows = torch.zeros(bs, nv, 2, heads, d, device=d0)
-    nbytes = int(l.selfocc_msda_bwd_banded_workspace(bs, nq, heads, L, P))
+    nbytes = int(l.selfocc_msda_ws_bytes(args(0)))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=d0)
 
     def bwd(gvs):
-        return l.selfocc_msda_fused_bwd(ptr(value), ptr(shapes), ptr(starts), C.cast(host, C.c_void_p), ptr(ref), 0, ptr(ol), lg_ptr,
-                                        ptr(g_out), ptr(g_rows), ptr(g_ol), C.c_void_p(g_ol.data_ptr() + 8 * heads * LP), bs, nv, nq,
-                                        heads, d, L, P, 1, abi.DTYPE_F32, 3 * heads * LP, gvs, ptr(ws), nbytes, st)
+        return l.selfocc_msda_bwd(args(3 * heads * LP, host_shapes=C.addressof(host), g_out=g_out.data_ptr(),
+                                       g_value=g_rows.data_ptr(), g_off=g_ol.data_ptr(), g_logits=g_ol.data_ptr() + 8 * heads * LP,
+                                       g_value_stride=gvs, workspace=ws.data_ptr(), workspace_bytes=nbytes), st)
     assert bwd(2 * heads * d) == 0
     torch.cuda.synchronize()
     assert float(g_rows[:, :, 0].abs().sum()) > 0 and float(g_rows[:, :, 1].abs().sum()) == 0      # only this op's column block is written

@@ -143,7 +143,7 @@ def test_lut_constants_equal_the_reference_tables():
     assert KITTI_CROP == (0, 6, 6, 6, 0, 4)
 
 
-def test_ssc_metric_args_layout_matches_header(tmp_path):
+def test_ssc_metric_args_layout_and_abi_version_match_header(tmp_path):
     fields = [f for f, _ in abi.SoSscMetricArgs._fields_]
     body = "\n".join(f'printf("%zu %zu\\n", sizeof(so_ssc_metric_args), offsetof(so_ssc_metric_args, {f}));'
                      for f in fields)
@@ -156,7 +156,7 @@ def test_ssc_metric_args_layout_matches_header(tmp_path):
     for k, f in enumerate(fields):
         assert int(lines[2 * k]) == C.sizeof(abi.SoSscMetricArgs), f
         assert int(lines[2 * k + 1]) == getattr(abi.SoSscMetricArgs, f).offset, f
-    assert abi.ABI_VERSION == 34
+    assert abi.ABI_VERSION == 35
 
 
 def _valid():
