@@ -130,6 +130,29 @@ enum {
                                    then differ from the canonical result by more than 1e-4          */
 };
 enum { SO_DTYPE_F32 = 0, SO_DTYPE_BF16 = 1 };
+/* activation of the spherical-harmonics colour (so_render_args::sh_act) */
+enum { SO_SH_RELU = 0, SO_SH_SIGMOID = 1 };
+
+/* View-dependent colour (so_render_args::sh_deg / sh_act; model/head/utils/sh_render.py:35-94 of the reference).
+ * With n_rgb == 3 the first n_coef = 3 * n_basis, n_basis = (sh_deg + 1)^2, channels of a voxel row are spherical-
+ * harmonics coefficients, COLOUR-MAJOR: channel c * n_basis + k is basis k of colour c.  Per sample, with f the
+ * trilinearly interpolated channels and (x, y, z) the unit direction the march itself uses (explicit rays: dirs[ray];
+ * pixel grid: the normalised M[:3,:3] (u, v, 1)), not negated:
+ *     raw_c = sum_k Y_k(x, y, z) * f[c * n_basis + k]
+ *     rgb_c = relu(raw_c + 0.5)   (SO_SH_RELU)     or     sigmoid(raw_c)   (SO_SH_SIGMOID)
+ *     Y_0 = C0                                    C0 = 0.28209479177387814
+ *     Y_1 = -C1 y,  Y_2 = C1 z,  Y_3 = -C1 x      C1 = 0.4886025119029199
+ *     Y_4 = C2a xy, Y_5 = -C2a yz, Y_6 = C2b (2 zz - xx - yy), Y_7 = -C2a xz, Y_8 = C2c (xx - yy)
+ *                                                 C2a = 1.0925484305920792, C2b = 0.31539156525252005, C2c = 0.5462742152960396
+ * sh_deg = 0 with SO_SH_RELU is rgb = relu(C0 * raw + 0.5), the formula of every earlier ABI version: the zero-
+ * initialised pair keeps its meaning and runs the kernels it always ran.  Everything after the colour (compositing,
+ * background, SO_FLAG_CLAMP_RGB, depth / acc / max-depth / per-sample outputs) does not depend on sh_deg / sh_act.
+ * Built: sh_deg 0 - 2, both activations, float32 feat_vol, n_sem == 0 whenever sh_deg > 0 or sh_act != SO_SH_RELU,
+ *     feat_stride = 4 / 12 / 28 for sh_deg 0 / 1 / 2 (n_coef rounded up to a multiple of 4; pad channels are never read
+ *     and their gradient stays zero).
+ * These launches always march in the canonical operation order (SO_FLAG_EXACT changes nothing for them).
+ * The two fields sit at the END of so_render_args, after everything a caller of the earlier layout fills, and
+ * SELFOCC_ABI_VERSION is unchanged: a caller that zero-initialises the struct gets the behaviour it always got. */
 
 typedef struct so_render_args {
     /* --- field ------------------------------------------------------------------- */
@@ -138,7 +161,7 @@ typedef struct so_render_args {
     const void *feat_vol; /* NULL when n_rgb + n_sem == 0 */
     int32_t feat_dtype;   /* SO_DTYPE_* */
     int32_t feat_stride;
-    int32_t n_rgb;        /* 0 or 3 (SH degree 0: rgb = relu(C0 * raw + 0.5))          */
+    int32_t n_rgb;        /* 0 or 3 colour OUTPUTS; the colour channels read follow from sh_deg (below) */
     int32_t n_sem;        /* semantic classes; per-sample softmax, weight-composited    */
     /* --- rays -------------------------------------------------------------------- */
     int32_t ray_mode;     /* SO_RAYS_* */
@@ -191,6 +214,9 @@ typedef struct so_render_args {
                          inv_s from it and ignore the host value above: a training loop whose inv_s is
                          a learnable parameter (exp(10 * variance), neus_head.py:631-633) never has to
                          read it back to the host (no stream sync, nothing to go stale).       */
+    /* --- view-dependent colour (see above); zero = degree 0 with relu ------------------ */
+    int32_t sh_deg;         /* 0, 1 or 2: 3 / 12 / 27 coefficient channels                             */
+    int32_t sh_act;         /* SO_SH_*                                                                  */
 } so_render_args;
 
 int selfocc_render_fwd(const so_render_args *args, void *stream);
@@ -228,7 +254,9 @@ typedef struct so_render_bwd_args {
 int selfocc_render_bwd(const so_render_bwd_args *args, void *stream);
 /* bytes of so_render_bwd_args::scatter_ws for this call.  0 = the call is outside the binned path's range — pass
  * NULL then (the atomic path runs): args == NULL, n_rays <= 0 or n_samples <= 0, an axis longer than 1021 grid
- * points, n_rays * n_samples >= 2^31, or a channel count other than 0 / 3 / 8 / 20 / 24. */
+ * points, n_rays * n_samples >= 2^31, or a channel count other than 0 / 3 / 8 / 20 / 24.  Spherical-harmonics launches
+ * (sh_deg > 0 or sh_act != SO_SH_RELU) use the 64-byte record at every degree: it carries d L / d raw_c (3 floats) and the
+ * ray's unit direction (3 floats) in place of a d L / d feature row, and the brick kernel expands Y_k from the direction. */
 size_t selfocc_render_bwd_ws_bytes(const so_render_bwd_args *args);
 
 /* ------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 #!/bin/bash
 # usage (GPU box): scripts/pmc_render.sh <channels> <tag> [quick]  -> PMC means of the render_fwd kernels, stdout + gpurun_out/<tag>_pmc.txt
+#   channels incl. the SDF: 1 | 4 | 25 as shipped, 13 | 28 = spherical-harmonics colour of degree 1 | 2
 #   env SELFOCC_HIP_LIB selects an A/B build; "quick" skips the FETCH_SIZE / WRITE_SIZE passes
 C=$1; TAG=$2; Q=${3:-full}; R=${GRAFT_REPO_ROOT:-$(pwd)}; cd /tmp; export TMPDIR=/tmp
 passes=("SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY" \
@@ -20,7 +21,7 @@ for f in sorted(glob.glob("$R/gpurun_out/pmc_$TAG/p*/p_counter_collection.csv"))
     agg = collections.defaultdict(lambda: collections.defaultdict(list))
     for r in csv.DictReader(open(f)):
         import re
-        m = re.search(r'(render_fwd_\w+<[^>]*>|sdf_brickify_kernel)', r['Kernel_Name'])
+        m = re.search(r'(render_(?:fwd|sh)_\w+<[^>]*>|sdf_brickify_kernel)', r['Kernel_Name'])
         if m:
             agg[m.group(1)][r['Counter_Name']].append(float(r['Counter_Value']))
     ta_pass = any('TA_BUSY_avr' in d for d in agg.values())

@@ -20,6 +20,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 LINEAR_RELU = 1
 LBL_F32, LBL_U8, LBL_I32, LBL_I64 = 0, 1, 2, 3
 MAP_LINEAR, MAP_UPSCALE = 0, 1
+SH_RELU, SH_SIGMOID = 0, 1
 
 _f, _i, _p = C.c_float, C.c_int32, C.c_void_p
 
@@ -59,6 +60,7 @@ class SoRenderArgs(C.Structure):
         ("weights", _p), ("ts", _p), ("deltas", _p), ("sdf", _p), ("grad", _p),
         ("sdf_brick", _p),
         ("inv_s_dev", _p),
+        ("sh_deg", _i), ("sh_act", _i),
     ]
 
 

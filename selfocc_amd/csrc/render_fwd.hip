@@ -14,6 +14,7 @@
 // needed on this path (render_bwd.hip, which must reverse the recurrence, is the kernel
 // that scans across lanes).
 #include "so_device.h"
+#include "sh_device.h"
 
 #ifdef SO_STAGE_STATS
 __device__ unsigned long long g_stage_stats[2];
@@ -25,6 +26,8 @@ extern "C" int selfocc_debug_stage_stats(unsigned long long *out) {
 // render_train.hip
 template <int NF, bool BF16>
 int so_render_fwd_samples(const so_render_args &a, hipStream_t st);
+template <int NB>
+int so_render_sh_samples(const so_render_args &a, hipStream_t st);
 
 namespace {
 
@@ -183,9 +186,12 @@ SO_DEVFN void so_gather_feat_interior(__amdgpu_buffer_rsrc_t rf, int W, int D, u
 }
 
 // MK: the mapping kind (SO_MAP_LINEAR / SO_MAP_UPSCALE), a compile-time choice of so_locate_k
-template <int NF, bool BF16, bool PER_SAMPLE, int MK = SO_MAP_LINEAR>
+// NB > 0: spherical-harmonics colour with NB basis functions (sh_device.h); NF is then the row stride of the coefficients
+template <int NF, bool BF16, bool PER_SAMPLE, int MK = SO_MAP_LINEAR, int NB = 0>
 SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g) {
-    constexpr int NSEM = NF > 4 ? NF - 3 : 0;  // NF = 3 rgb (+1 pad) or 3 rgb + n_sem
+    constexpr int NSEM = (NB == 0 && NF > 4) ? NF - 3 : 0;  // NF = 3 rgb (+1 pad) or 3 rgb + n_sem
+    float Y[NB > 0 ? NB : 1];                   // the ray's basis: once, before the march
+    if constexpr (NB > 0) so_sh_basis<NB>(g.dx, g.dy, g.dz, Y);
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
     const int S = a.n_samples;
     float tnear, tfar;
@@ -239,7 +245,12 @@ SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g)
         float q = wq / fmaxf(dz_, eps32);
         if (q > best_q) { best_q = q; best_t = tz; }
 
-        if constexpr (NF > 0) {
+        if constexpr (NB > 0) {
+            float raw[3];
+            so_sh_gather<NB>(a.feat_vol, H, W, D, c, wk, Y, raw);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) rgb[k] = fmaf(w, so_sh_act(raw[k], a.sh_act), rgb[k]);
+        } else if constexpr (NF > 0) {
             float f[NF];
             so_gather_feat<NF, BF16>(a.feat_vol, H, W, D, c, wk, f);
 #pragma unroll
@@ -1277,6 +1288,50 @@ int dispatch_ps(const so_render_args &a, hipStream_t st) {
     return launch_fwd<NF, BF16, false, 0>(a, st);
 }
 
+// ---- spherical-harmonics colour (sh_deg > 0 or sh_act != relu): ray per lane, canonical march -------------------------------
+// The same thread <-> ray maps as render_fwd_explicit / render_fwd_pixgrid (an 8 x 8 pixel tile per wave).
+template <int NB, int MK>
+__global__ __launch_bounds__(256) void render_sh_explicit(so_render_args a) {
+    const int ray = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ray >= a.n_rays) return;
+    RayGeom g;
+    g.ox = a.origins[3 * (size_t)ray]; g.oy = a.origins[3 * (size_t)ray + 1]; g.oz = a.origins[3 * (size_t)ray + 2];
+    g.dx = a.dirs[3 * (size_t)ray]; g.dy = a.dirs[3 * (size_t)ray + 1]; g.dz = a.dirs[3 * (size_t)ray + 2];
+    g.dn = a.dir_norm ? a.dir_norm[ray] : 1.0f;
+    so_march_exact<so_sh_stride(NB), false, false, MK, NB>(a, ray, g);
+}
+
+template <int NB, int MK>
+__global__ __launch_bounds__(256) void render_sh_pixgrid(so_render_args a, int tiles_x, int tiles_y) {
+    const int b = blockIdx.x;
+    const int cam = b / (tiles_x * tiles_y);
+    const int tb = b - cam * tiles_x * tiles_y;
+    const int ty = tb / tiles_x, tx = tb - ty * tiles_x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ix = tx * 16 + (wave & 1) * 8 + (lane & 7);
+    const int iy = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (ix >= a.nx || iy >= a.ny) return;
+    const int ray = (cam * a.ny + iy) * a.nx + ix;
+    so_march_exact<so_sh_stride(NB), false, false, MK, NB>(a, ray, so_pixel_ray(a, cam, ix, iy));
+}
+
+template <int NB, int MK>
+int launch_sh(const so_render_args &a, hipStream_t st) {
+    if (a.ray_mode == SO_RAYS_EXPLICIT) {
+        hipLaunchKernelGGL((render_sh_explicit<NB, MK>), dim3((a.n_rays + 255) / 256), dim3(256), 0, st, a);
+    } else {
+        const int tiles_x = (a.nx + 15) / 16, tiles_y = (a.ny + 15) / 16;
+        hipLaunchKernelGGL((render_sh_pixgrid<NB, MK>), dim3(tiles_x * tiles_y * a.n_cams), dim3(256), 0, st, a, tiles_x, tiles_y);
+    }
+    return so_launch_status();
+}
+
+template <int NB>
+int dispatch_sh(const so_render_args &a, hipStream_t st) {
+    if (a.weights || a.ts || a.deltas || a.sdf || a.grad) return so_render_sh_samples<NB>(a, st);   // training API
+    return a.map.kind == SO_MAP_UPSCALE ? launch_sh<NB, SO_MAP_UPSCALE>(a, st) : launch_sh<NB, SO_MAP_LINEAR>(a, st);
+}
+
 }  // namespace
 
 int so_validate_mapping(const so_mapping &m) {
@@ -1337,14 +1392,24 @@ int so_validate_render(const so_render_args &a) {
     SO_REQUIRE(a.sdf_vol != nullptr, "sdf_vol is NULL");
     SO_REQUIRE(a.n_samples >= 1, "n_samples must be >= 1");
     SO_REQUIRE(a.n_rays >= 0, "n_rays must be >= 0");
-    SO_REQUIRE(a.n_rgb == 0 || a.n_rgb == 3, "n_rgb must be 0 or 3 (SH degree 0)");
+    SO_REQUIRE(a.n_rgb == 0 || a.n_rgb == 3, "n_rgb must be 0 or 3 (the colour outputs; sh_deg sets the coefficient count)");
     SO_REQUIRE(a.n_sem >= 0, "n_sem must be >= 0");
     SO_REQUIRE(a.n_sem == 0 || a.n_rgb == 3, "semantic channels require n_rgb == 3");
+    SO_REQUIRE(a.sh_deg >= 0 && a.sh_deg <= 2, "sh_deg %d is not built (built: sh_deg 0, 1, 2)", (int)a.sh_deg);
+    SO_REQUIRE(a.sh_act == SO_SH_RELU || a.sh_act == SO_SH_SIGMOID, "sh_act %d is unknown (0 = relu, 1 = sigmoid)", (int)a.sh_act);
     if (a.n_rgb + a.n_sem > 0) {
         SO_REQUIRE(a.feat_vol != nullptr, "feat_vol is NULL but n_rgb + n_sem > 0");
         SO_REQUIRE(a.feat_dtype == SO_DTYPE_F32 || a.feat_dtype == SO_DTYPE_BF16, "bad feat_dtype");
         SO_REQUIRE(a.feat_stride % 4 == 0 && a.feat_stride >= a.n_rgb + a.n_sem,
                    "feat_stride must be a multiple of 4 and >= n_rgb + n_sem");
+    }
+    if (so_sh_launch(a)) {
+        const int n_coef = 3 * (a.sh_deg + 1) * (a.sh_deg + 1);
+        SO_REQUIRE(a.n_sem == 0, "sh_deg > 0 / sh_act = sigmoid with n_sem = %d semantic channels is not built (built: n_sem = 0)",
+                   (int)a.n_sem);
+        SO_REQUIRE(a.feat_dtype == SO_DTYPE_F32, "sh_deg > 0 / sh_act = sigmoid with a bfloat16 feature volume is not built (built: float32)");
+        SO_REQUIRE(a.feat_stride == ((n_coef + 3) & ~3), "sh_deg = %d reads %d coefficients: feat_stride must be %d (got %d)",
+                   (int)a.sh_deg, n_coef, (n_coef + 3) & ~3, (int)a.feat_stride);
     }
     if (a.ray_mode == SO_RAYS_EXPLICIT) {
         SO_REQUIRE(a.n_rays == 0 || (a.origins && a.dirs), "explicit rays need origins and dirs");
@@ -1370,6 +1435,7 @@ extern "C" int selfocc_render_fwd(const so_render_args *args, void *stream) {
     int nf = a.n_rgb + a.n_sem;
     bool bf = a.feat_dtype == SO_DTYPE_BF16;
     if (nf == 0) return dispatch_ps<0, false>(a, st);
+    if (so_sh_launch(a)) return a.sh_deg == 0 ? dispatch_sh<1>(a, st) : (a.sh_deg == 1 ? dispatch_sh<4>(a, st) : dispatch_sh<9>(a, st));
     if (nf == 3) {
         SO_REQUIRE(a.feat_stride == 4, "n_rgb=3, n_sem=0 requires feat_stride == 4");
         return bf ? dispatch_ps<4, true>(a, st) : dispatch_ps<4, false>(a, st);

@@ -22,7 +22,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from ... import abi
+from ... import abi, sh
 from ..._lib import upload
 from ...mapping import GridMeterMapping
 from ...occ import field_query, field_query_autograd, uniform_lattice
@@ -176,10 +176,30 @@ class SDFField(BaseModule):
         self.mapping = GridMeterMapping(**mapping_args)
         self.embed_dims, self.color_dims, self.tpv = embed_dims, color_dims, tpv
         self.size_h, self.size_w, self.size_d = self.mapping.size_h, self.mapping.size_w, self.mapping.size_d
-        if color_dims > 0 and (sh_deg != 0 or sh_act != 'relu'):
-            raise NotImplementedError("the render kernel implements SH degree 0 with relu (every shipped config)")
-        self.n_rgb = 3 if color_dims >= 3 else 0
-        self.n_sem = color_dims - self.n_rgb if color_dims > 3 else 0
+        # view-dependent colour (selfocc_amd/sh.py): the first 3 * (sh_deg + 1)^2 of the color_dims channels are the
+        # spherical-harmonics coefficients, colour-major; what follows them is semantic logits.  Without colour
+        # (color_dims == 0: the depth configs, which leave sh_deg at its default of 2) the two knobs are not read.
+        self.sh_deg, self.sh_act = 0, 'relu'
+        self.n_rgb, self.n_sem = 0, 0
+        if color_dims > 0:
+            if sh_deg not in (0, 1, 2):
+                raise NotImplementedError(f"sh_deg={sh_deg}: the render kernels implement sh_deg 0, 1 and 2")
+            if sh_act not in sh.SH_ACTS:
+                raise NotImplementedError(f"sh_act={sh_act!r}: the render kernels implement 'relu' and 'sigmoid'")
+            n_coef = sh.n_coef(sh_deg)
+            if color_dims < 3 and sh_deg == 0 and sh_act == 'relu':
+                n_coef = 0                               # fewer than three channels: no colour is rendered (as before)
+            elif color_dims < n_coef:
+                raise ValueError(f"color_dims={color_dims} is too small for sh_deg={sh_deg}, which reads {n_coef} colour "
+                                 f"channels (3 x {(sh_deg + 1) ** 2}); pass sh_deg=0 for plain rgb (+ semantic) channels")
+            self.n_rgb, self.n_sem = (3, color_dims - n_coef) if n_coef else (0, 0)
+            if self.n_sem > 0 and (sh_deg > 0 or sh_act != 'relu'):
+                raise NotImplementedError(f"color_dims={color_dims} with sh_deg={sh_deg}, sh_act={sh_act!r} leaves {self.n_sem} "
+                                          "semantic channels: semantic channels are built with sh_deg=0 and sh_act='relu' only")
+            if feat_dtype != torch.float32 and (sh_deg > 0 or sh_act != 'relu'):
+                raise NotImplementedError("sh_deg > 0 / sh_act='sigmoid' are built for a float32 feature volume (got "
+                                          f"{feat_dtype})")
+            self.sh_deg, self.sh_act = sh_deg, sh_act
         out = 1 + color_dims
         layers = []
         for _ in range(density_layers - 1):
@@ -190,6 +210,12 @@ class SDFField(BaseModule):
         self.feat_dtype = feat_dtype
         self.fused_volume = True     # inference uses selfocc_field_volume_fwd when the configuration allows
         self.volume = None
+
+    def _volume(self, sdf, feat_vol):
+        return SDFVolume(self.mapping, sdf, feat_vol, self.n_rgb, self.n_sem, self.sh_deg, self.sh_act)
+
+    def _feat_width(self):
+        return SDFVolume.feat_width(self.n_rgb, self.n_sem, self.sh_deg)
 
     def inv_s(self):
         return torch.exp(self.variance * 10.0).clip(1e-6, 1e6)
@@ -213,19 +239,19 @@ class SDFField(BaseModule):
                 hw, zh, wz = (t.float() for t in representation)
                 assert hw.shape[0] == 1, 'only support bs = 1 currently'
                 linears = [m for m in self.density_net if isinstance(m, nn.Linear)]
-                F = SDFVolume.feat_width(self.n_rgb, self.n_sem)
+                F = self._feat_width()
                 if (self.fused_volume and not torch.is_grad_enabled() and hw.is_cuda
                         and field_volume_supported(C, len(linears), 1 + self.color_dims, F)):
                     # inference: plane sum + MLP + layout in one MFMA kernel, no (H*W*D, C) intermediate
                     sdf, feat_vol = field_volume(hw, zh, wz, (H, W, D), linears, F, self.feat_dtype)
-                    self.volume = SDFVolume(self.mapping, sdf, feat_vol, self.n_rgb, self.n_sem)
+                    self.volume = self._volume(sdf, feat_vol)
                     return self.volume
                 if (self.fused_volume and torch.is_grad_enabled() and hw.is_cuda
                         and field_volume_train_supported(C, len(linears), 1 + self.color_dims, F, self.feat_dtype, (H, W, D))):
                     # training: the same fusion under autograd (fused backward recomputes the activations)
                     sdf, feat_vol = FieldVolumeFunction.apply(hw, zh, wz, linears[0].weight, linears[0].bias,
                                                               linears[1].weight, linears[1].bias, (H, W, D), F)
-                    self.volume = SDFVolume(self.mapping, sdf, feat_vol if F > 0 else None, self.n_rgb, self.n_sem)
+                    self.volume = self._volume(sdf, feat_vol if F > 0 else None)
                     return self.volume
                 feat = hw.reshape(H, W, 1, C) + zh.reshape(D, H, 1, C).permute(1, 2, 0, 3) + \
                     wz.reshape(W, D, 1, C).permute(2, 0, 1, 3)                       # H, W, D, C
@@ -237,14 +263,14 @@ class SDFField(BaseModule):
             sdf = out[..., 0].contiguous()
             feat_vol = None
             if self.color_dims > 0:
-                F = SDFVolume.feat_width(self.n_rgb, self.n_sem)
+                F = self._feat_width()
                 if F == out.shape[-1] - 1:
                     feat_vol = out[..., 1:].contiguous()
                 else:
                     feat_vol = torch.cat([out[..., 1:], out.new_zeros(H, W, D, F - (out.shape[-1] - 1))], -1).contiguous()
                 if self.feat_dtype != torch.float32:
                     feat_vol = feat_vol.to(self.feat_dtype)
-        self.volume = SDFVolume(self.mapping, sdf, feat_vol, self.n_rgb, self.n_sem)
+        self.volume = self._volume(sdf, feat_vol)
         return self.volume
 
     def _differentiable(self):
@@ -259,14 +285,14 @@ class SDFField(BaseModule):
         if self._differentiable():
             q = field_query_autograd(v, xyz.reshape(-1, 3), want_logits=v.n_sem > 0 and v.feat.dtype == torch.float32)
             if v.n_sem > 0 and 'logits' not in q:
-                q['logits'] = field_query(SDFVolume(v.mapping, v.sdf.detach(), v.feat.detach(), v.n_rgb, v.n_sem),
+                q['logits'] = field_query(v.detached(),
                                           xyz.reshape(-1, 3), want_sdf=False, want_logits=True)['logits']
         else:
-            vol = SDFVolume(v.mapping, v.sdf.detach(), None if v.feat is None else v.feat.detach(), v.n_rgb, v.n_sem)
+            vol = v.detached()
             q = field_query(vol, xyz.reshape(-1, 3), want_sdf=True, want_logits=v.n_sem > 0)
         cols = [q['sdf'][:, None]]
         if v.n_rgb:
-            cols.append(torch.zeros(q['sdf'].shape[0], 3, device=xyz.device))  # raw rgb is not consumed by any caller
+            cols.append(torch.zeros(q['sdf'].shape[0], v.n_colour, device=xyz.device))  # raw colour is not consumed by any caller
         if v.n_sem:
             cols.append(q['logits'])
         return torch.cat(cols, -1)
@@ -278,7 +304,7 @@ class SDFField(BaseModule):
         v = self.volume
         if self._differentiable() or v.n_sem == 0 or v.feat is None:
             return None
-        vol = SDFVolume(v.mapping, v.sdf.detach(), v.feat.detach(), v.n_rgb, v.n_sem)
+        vol = v.detached()
         q = field_query(vol, xyz.reshape(-1, 3), want_sdf=True, want_logits=True, want_argmax=True)
         return q['sdf'], q['logits'], q['argmax'].long()
 
@@ -525,7 +551,7 @@ class NeuSHead(BaseModule):
         rays, pix, num_cams, num_rays = self._rays(metas, device)
         cfg = self._render_cfg(False)
         cfg.inv_s_dev = self.model.field.inv_s_device()
-        vol = SDFVolume(vol.mapping, vol.sdf.detach(), None if vol.feat is None else vol.feat.detach(), vol.n_rgb, vol.n_sem)
+        vol = vol.detached()
         if vol.n_rgb == 0 and cfg.bkgd_mode == abi.BKGD_PER_RAY:
             # no colour is rendered (the depth configs): the random background would be drawn (2.16 M x 3 numbers per frame) and never
             # read — nerfstudio's RGBRenderer, which draws it in the reference, is not called for a depth-only head either
@@ -600,8 +626,7 @@ class NeuSHead(BaseModule):
             from ... import dist as sdist
             rays, pix = self._agree_on_lattice(rays, pix, vol, metas)
             full_rays, rays = rays, sdist.shard_rays(rays)
-            vol = SDFVolume(vol.mapping, sdist.replicate_grad_sum(vol.sdf), sdist.replicate_grad_sum(vol.feat),
-                            vol.n_rgb, vol.n_sem)
+            vol = vol.with_tensors(sdist.replicate_grad_sum(vol.sdf), sdist.replicate_grad_sum(vol.feat))
         N, S = rays.n_rays, self.num_samples
         t_rand = None
         if cfg.jitter_mode != abi.JITTER_NONE:

@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-from . import abi
+from . import abi, sh
 from ._lib import lib, check, ptr, current_stream
 
 
@@ -22,6 +22,9 @@ class SDFVolume:
     sdf  : (H, W, D) float32
     feat : (H, W, D, F) float32 / bfloat16 or None; channels = raw colour (3) then
            semantic logits (n_sem); F == 4 when n_sem == 0 (one pad channel).
+    sh_deg / sh_act : view-dependent colour (selfocc_amd/sh.py).  With sh_deg > 0 the colour channels are the
+           3 * (sh_deg + 1)^2 spherical-harmonics coefficients, colour-major, F = 12 / 28 for degree 1 / 2 (float32,
+           n_sem == 0); n_rgb stays 3, the number of colour outputs.
     The reference materialises (1, 1 + color_dims, H, W, D) instead
     (nerfacc_head/bev_nerf.py:74-95); ``from_reference_layout`` converts.
     """
@@ -30,40 +33,57 @@ class SDFVolume:
     feat: Optional[torch.Tensor] = None
     n_rgb: int = 0
     n_sem: int = 0
+    sh_deg: int = 0
+    sh_act: str = 'relu'
 
     @staticmethod
-    def feat_width(n_rgb, n_sem):
+    def feat_width(n_rgb, n_sem, sh_deg=0):
         if n_rgb + n_sem == 0:
             return 0
+        if sh_deg > 0:
+            assert n_rgb == 3 and n_sem == 0, "sh_deg > 0 is built without semantic channels"
+            return sh.feat_stride(sh_deg)
         return 4 if n_sem == 0 else n_rgb + n_sem
 
+    @property
+    def n_colour(self):
+        """colour channels stored per voxel: 3 * (sh_deg + 1)^2 coefficients when colour is rendered"""
+        return sh.n_coef(self.sh_deg) if self.n_rgb else 0
+
     @classmethod
-    def from_reference_layout(cls, mapping, density_color, n_rgb=0, n_sem=0, feat_dtype=torch.float32):
-        """density_color: (1, 1 + n_rgb + n_sem, H, W, D) as in the reference."""
+    def from_reference_layout(cls, mapping, density_color, n_rgb=0, n_sem=0, feat_dtype=torch.float32, sh_deg=0, sh_act='relu'):
+        """density_color: (1, 1 + n_colour + n_sem, H, W, D) as in the reference (n_colour = 3 * (sh_deg + 1)^2 or 0)."""
+        sh.check(sh_deg, sh_act)
         assert density_color.dim() == 5 and density_color.shape[0] == 1
-        assert density_color.shape[1] == 1 + n_rgb + n_sem
+        n_col = sh.n_coef(sh_deg) if n_rgb else 0
+        assert density_color.shape[1] == 1 + n_col + n_sem
         sdf = density_color[0, 0].contiguous().float()
         feat = None
-        if n_rgb + n_sem > 0:
-            F = cls.feat_width(n_rgb, n_sem)
+        if n_col + n_sem > 0:
+            F = cls.feat_width(n_rgb, n_sem, sh_deg)
             H, W, D = sdf.shape
             feat = torch.zeros(H, W, D, F, dtype=feat_dtype, device=sdf.device)
-            feat[..., :n_rgb + n_sem] = density_color[0, 1:].permute(1, 2, 3, 0).to(feat_dtype)
-        return cls(mapping, sdf, feat, n_rgb, n_sem)
+            feat[..., :n_col + n_sem] = density_color[0, 1:].permute(1, 2, 3, 0).to(feat_dtype)
+        return cls(mapping, sdf, feat, n_rgb, n_sem, sh_deg, sh_act)
 
     def to_reference_layout(self):
         ch = [self.sdf[None]]
         if self.feat is not None:
-            ch.append(self.feat[..., :self.n_rgb + self.n_sem].float().permute(3, 0, 1, 2))
+            ch.append(self.feat[..., :self.n_colour + self.n_sem].float().permute(3, 0, 1, 2))
         return torch.cat(ch, 0)[None]
 
+    def with_tensors(self, sdf, feat):
+        """the same field description (mapping, channel meaning) over other tensors"""
+        return SDFVolume(self.mapping, sdf, feat, self.n_rgb, self.n_sem, self.sh_deg, self.sh_act)
+
+    def detached(self):
+        return self.with_tensors(self.sdf.detach(), None if self.feat is None else self.feat.detach())
+
     def cpu(self):
-        return SDFVolume(self.mapping, self.sdf.cpu(), None if self.feat is None else self.feat.cpu(),
-                         self.n_rgb, self.n_sem)
+        return self.with_tensors(self.sdf.cpu(), None if self.feat is None else self.feat.cpu())
 
     def to(self, device):
-        return SDFVolume(self.mapping, self.sdf.to(device), None if self.feat is None else self.feat.to(device),
-                         self.n_rgb, self.n_sem)
+        return self.with_tensors(self.sdf.to(device), None if self.feat is None else self.feat.to(device))
 
 
 @dataclass
@@ -143,6 +163,8 @@ def marshal_render_args(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, per_
     assert tuple(vol.sdf.shape) == (H, W, D), f"sdf volume {tuple(vol.sdf.shape)} != mapping {(H, W, D)}"
     a.sdf_vol = ptr(_c(vol.sdf))
     a.n_rgb, a.n_sem = vol.n_rgb, vol.n_sem
+    sh.check(vol.sh_deg, vol.sh_act)
+    a.sh_deg, a.sh_act = vol.sh_deg, abi.SH_SIGMOID if vol.sh_act == 'sigmoid' else abi.SH_RELU
     if vol.feat is not None:
         assert vol.feat.is_contiguous() and vol.feat.shape[:3] == (H, W, D)
         assert vol.feat.dtype in (torch.float32, torch.bfloat16)
@@ -254,8 +276,9 @@ class _RenderFunction(torch.autograd.Function):
     camera matrices (model/head/nerfacc_head/img2lidar.py:36-69)."""
 
     @staticmethod
-    def forward(ctx, sdf_vol, feat_vol, inv_s, mapping, n_rgb, n_sem, rays, cfg, t_rand, bkgd_rays, want_grad_samples):
-        vol = SDFVolume(mapping, sdf_vol, feat_vol, n_rgb, n_sem)
+    def forward(ctx, sdf_vol, feat_vol, inv_s, mapping, n_rgb, n_sem, rays, cfg, t_rand, bkgd_rays, want_grad_samples,
+                sh_deg=0, sh_act='relu'):
+        vol = SDFVolume(mapping, sdf_vol, feat_vol, n_rgb, n_sem, sh_deg, sh_act)
         # the kernels read inv_s from the device tensor itself: no read-back, no stream sync, nothing to go stale
         cfg_run = RenderConfig(**{**cfg.__dict__, 'inv_s_dev': inv_s.detach().reshape(1).float().contiguous()})
         out = render_rays(vol, rays, cfg_run, per_sample=True, want_grad_samples=want_grad_samples,
@@ -264,7 +287,7 @@ class _RenderFunction(torch.autograd.Function):
         # the config are plain python state
         ctx.has = (feat_vol is not None, t_rand is not None, bkgd_rays is not None)
         ctx.save_for_backward(*[t for t in (sdf_vol, feat_vol, t_rand, bkgd_rays, cfg_run.inv_s_dev) if t is not None])
-        ctx.meta = (mapping, n_rgb, n_sem)
+        ctx.meta = (mapping, n_rgb, n_sem, sh_deg, sh_act)
         ctx.rays, ctx.cfg = rays, RenderConfig(**{**cfg_run.__dict__, 'inv_s_dev': None})
         ctx.inv_s_shape = inv_s.shape
         ctx.keys = ['depth', 'acc'] + (['rgb'] if n_rgb else []) + (['sem'] if n_sem else []) + ['weights'] + \
@@ -282,8 +305,7 @@ class _RenderFunction(torch.autograd.Function):
         t_rand = saved.pop(0) if ctx.has[1] else None
         bkgd_rays = saved.pop(0) if ctx.has[2] else None
         inv_s_dev = saved.pop(0)
-        mapping, n_rgb, n_sem = ctx.meta
-        vol = SDFVolume(mapping, sdf_vol, feat_vol, n_rgb, n_sem)
+        vol = SDFVolume(ctx.meta[0], sdf_vol, feat_vol, *ctx.meta[1:])
         rays, cfg = ctx.rays, RenderConfig(**{**ctx.cfg.__dict__, 'inv_s_dev': inv_s_dev})
         gmap = {k: g for k, g in zip(ctx.keys, grads)}
         a, _out, _keep = marshal_render_args(vol, rays, cfg, per_sample=False, t_rand=t_rand,
@@ -320,7 +342,7 @@ class _RenderFunction(torch.autograd.Function):
         check(lib().selfocc_render_bwd(ba, current_stream(vol.sdf.device)), "selfocc_render_bwd")
         if g_feat is not None and vol.feat.dtype != torch.float32:
             g_feat = g_feat.to(vol.feat.dtype)
-        return (g_sdf_vol, g_feat, g_inv_s.reshape(ctx.inv_s_shape), None, None, None, None, None, None, None, None)
+        return (g_sdf_vol, g_feat, g_inv_s.reshape(ctx.inv_s_shape), None, None, None, None, None, None, None, None, None, None)
 
 
 def render_rays_autograd(vol: SDFVolume, inv_s: torch.Tensor, rays: RaySet, cfg: RenderConfig, *,
@@ -329,7 +351,7 @@ def render_rays_autograd(vol: SDFVolume, inv_s: torch.Tensor, rays: RaySet, cfg:
     depth / acc / rgb / sem / weights / sdf / grad attached to the autograd graph of
     ``vol.sdf``, ``vol.feat`` and ``inv_s``."""
     res = _RenderFunction.apply(vol.sdf, vol.feat, inv_s, vol.mapping, vol.n_rgb, vol.n_sem, rays, cfg,
-                                t_rand, bkgd_rays, want_grad_samples)
+                                t_rand, bkgd_rays, want_grad_samples, vol.sh_deg, vol.sh_act)
     keys = ['depth', 'acc'] + (['rgb'] if vol.n_rgb else []) + (['sem'] if vol.n_sem else []) + ['weights'] + \
         (['sdf', 'grad'] if want_grad_samples else []) + ['ts', 'deltas', 'max_depth', 'nears', 'fars']
     return dict(zip(keys, res))

@@ -51,8 +51,9 @@ def grid_points_meter(mapping):
     return mapping.grid2meter(g)  # (H, W, D, 3) metres (x, y, z)
 
 
-def make_volume(name, n_rgb=0, n_sem=0, feat_dtype=torch.float32, seed=0, n_boxes=40, noise=0.05):
-    """SDF = distance to (random boxes U ground plane) + N(0, noise^2); logits ~ N(0,1)."""
+def make_volume(name, n_rgb=0, n_sem=0, feat_dtype=torch.float32, seed=0, n_boxes=40, noise=0.05, sh_deg=0, sh_act='relu'):
+    """SDF = distance to (random boxes U ground plane) + N(0, noise^2); logits ~ N(0,1).
+    sh_deg > 0: the colour channels are 3 * (sh_deg + 1)^2 spherical-harmonics coefficients ~ N(0,1), colour-major."""
     cfg = CONFIGS[name]
     mapping = make_mapping(name)
     gen = torch.Generator().manual_seed(seed)
@@ -76,11 +77,12 @@ def make_volume(name, n_rgb=0, n_sem=0, feat_dtype=torch.float32, seed=0, n_boxe
     sdf = sdf + noise * torch.randn(sdf.shape, generator=gen)
     feat = None
     if n_rgb + n_sem > 0:
-        F = SDFVolume.feat_width(n_rgb, n_sem)
+        F = SDFVolume.feat_width(n_rgb, n_sem, sh_deg)
+        n_ch = (3 * (sh_deg + 1) ** 2 if n_rgb else 0) + n_sem
         feat = torch.zeros(*sdf.shape, F)
-        feat[..., :n_rgb + n_sem] = torch.randn(*sdf.shape, n_rgb + n_sem, generator=gen)
+        feat[..., :n_ch] = torch.randn(*sdf.shape, n_ch, generator=gen)
         feat = feat.to(feat_dtype)
-    return SDFVolume(mapping, sdf.contiguous().float(), feat, n_rgb, n_sem)
+    return SDFVolume(mapping, sdf.contiguous().float(), feat, n_rgb, n_sem, sh_deg, sh_act)
 
 
 def make_cameras(name, seed=0):
