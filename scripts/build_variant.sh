@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B build: libselfocc_hip_<name>.so = the standard objects with ONE source recompiled under extra flags.
-#   scripts/build_variant.sh stats render_fwd.hip -DSO_STAGE_STATS        (select with SELFOCC_HIP_LIB=<path>)
+#   scripts/build_variant.sh <name> render_fwd.hip <extra hipcc flags>    (select with SELFOCC_HIP_LIB=<path>)
 set -euo pipefail
 name=$1; src=$2; shift 2
 cd "$(dirname "$0")/../selfocc_amd/csrc"

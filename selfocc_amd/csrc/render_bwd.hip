@@ -16,61 +16,13 @@
 // The volume gradient is a scatter of 8 (+ 8 * n_feat) hardware float atomics per sample.
 #include "so_device.h"
 #include "sh_device.h"
+#include "ray_device.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
 constexpr int kMaxM = 8;  // samples per lane: S <= 512
-
-struct RayGeomB {
-    float ox, oy, oz, dx, dy, dz, dn;
-};
-
-SO_DEVFN RayGeomB load_ray(const so_render_args &a, int ray) {
-    RayGeomB g;
-    if (a.ray_mode == SO_RAYS_PIXEL_GRID) {
-        const int per_cam = a.nx * a.ny;
-        const int cam = ray / per_cam, rem = ray - cam * per_cam;
-        const int iy = rem / a.nx, ix = rem - iy * a.nx;
-        const float *M = a.img2lidar + cam * 16;
-        const float u = (float)ix * a.sx + a.ox, v = (float)iy * a.sy + a.oy;
-        g.ox = M[3]; g.oy = M[7]; g.oz = M[11];
-        const float dx = (M[0] * u + M[1] * v) + M[2];
-        const float dy = (M[4] * u + M[5] * v) + M[6];
-        const float dz = (M[8] * u + M[9] * v) + M[10];
-        g.dn = sqrtf((dx * dx + dy * dy) + dz * dz);
-        g.dx = dx / g.dn; g.dy = dy / g.dn; g.dz = dz / g.dn;
-    } else {
-        g.ox = a.origins[3 * (size_t)ray]; g.oy = a.origins[3 * (size_t)ray + 1]; g.oz = a.origins[3 * (size_t)ray + 2];
-        g.dx = a.dirs[3 * (size_t)ray]; g.dy = a.dirs[3 * (size_t)ray + 1]; g.dz = a.dirs[3 * (size_t)ray + 2];
-        g.dn = a.dir_norm ? a.dir_norm[ray] : 1.0f;
-    }
-    return g;
-}
-
-SO_DEVFN float bin01(int j, int n) {
-    const float step = 1.0f / (float)n;
-    return (j < (n + 1) / 2) ? step * (float)j : fmaf(-step, (float)(n - j), 1.0f);
-}
-
-SO_DEVFN float edge_t(const so_render_args &a, int ray, int j, float tn, float tf) {
-    const int n = a.n_samples;
-    float b = bin01(j, n);
-    if (a.jitter_mode != SO_JITTER_NONE) {
-        const float lo = (j == 0) ? b : (b + bin01(j - 1, n)) / 2.0f;
-        const float hi = (j == n) ? b : (bin01(j + 1, n) + b) / 2.0f;
-        const float tr = (a.jitter_mode == SO_JITTER_SINGLE) ? a.t_rand[ray] : a.t_rand[(size_t)ray * (n + 1) + j];
-        b = lo + (hi - lo) * tr;
-    }
-    return b * tf + (1.0f - b) * tn;
-}
-
-SO_DEVFN float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 template <int NF, bool BF16>
 SO_DEVFN void load_feat(const void *vol, size_t vox, float f[NF > 0 ? NF : 1]) {
@@ -147,21 +99,10 @@ SO_DEVFN int rb_key(const RbBin &b, const so_cell &c, int H, int W, int D) {
     return (bh * b.nbw + bw) * b.nbd + bd;
 }
 
-// entry / exit of the ray in the box collider, and the cell of sample i: ONE definition for the ray kernel and the
-// counting pre-pass (they must agree on every sample's brick)
-SO_DEVFN void ray_bounds(const so_render_args &a, const RayGeomB &g, float &tn, float &tf) {
-    const float fx = 1.0f / (g.dx + 1e-6f), fy = 1.0f / (g.dy + 1e-6f), fz = 1.0f / (g.dz + 1e-6f);
-    const float t1 = (a.aabb[0] - g.ox) * fx, t2 = (a.aabb[3] - g.ox) * fx;
-    const float t3 = (a.aabb[1] - g.oy) * fy, t4 = (a.aabb[4] - g.oy) * fy;
-    const float t5 = (a.aabb[2] - g.oz) * fz, t6 = (a.aabb[5] - g.oz) * fz;
-    tn = fmaxf(fmaxf(fminf(t1, t2), fminf(t3, t4)), fminf(t5, t6));
-    tf = fminf(fminf(fmaxf(t1, t2), fmaxf(t3, t4)), fmaxf(t5, t6));
-    tn = fmaxf(tn, a.near_plane);
-    tf = fmaxf(tf, tn + 1e-6f);
-}
-
+// the cell of sample i: ONE definition for the ray kernel and the counting pre-pass (they must agree on every sample's
+// brick; the ray, its collider bounds and the bin edges are those of ray_device.h)
 template <int MK = SO_MAP_LINEAR>
-SO_DEVFN so_cell sample_cell(const so_render_args &a, const RayGeomB &g, float t0, float t1) {
+SO_DEVFN so_cell sample_cell(const so_render_args &a, const RayGeom &g, float t0, float t1) {
     float px, py, pz;
     if (a.sample_pos == SO_SAMPLE_AT_START) {
         px = g.ox + g.dx * t0; py = g.oy + g.dy * t0; pz = g.oz + g.dz * t0;
@@ -222,15 +163,15 @@ SO_DEVFN void rb_count_body(const so_render_args &a, const RbBin &b) {
     const int ray = blockIdx.x * kCountWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (ray < a.n_rays) {   // wave-uniform
         const int S = a.n_samples;
-        const RayGeomB g = load_ray(a, ray);
+        const RayGeom g = so_ray_of(a, ray);
         float tn, tf;
-        ray_bounds(a, g, tn, tf);
+        so_collide(a, g, tn, tf);
         const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
         for (int s0 = 0; s0 < S; s0 += 64) {
             const int smp = s0 + lane;
             int key = -1;
             if (smp < S) {
-                const so_cell c = sample_cell<MK>(a, g, edge_t(a, ray, smp, tn, tf), edge_t(a, ray, smp + 1, tn, tf));
+                const so_cell c = sample_cell<MK>(a, g, so_edge(a, ray, smp, tn, tf), so_edge(a, ray, smp + 1, tn, tf));
                 key = rb_key(b, c, H, W, D) * kShards + rb_shard((long long)ray * S + smp);
             }
             int hl;

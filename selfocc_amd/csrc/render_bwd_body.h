@@ -14,7 +14,7 @@
     auto ray_sum = [&](auto &v, auto nconst) {
         constexpr int N = decltype(nconst)::value;
 #pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = wave_sum(v[k]);
+        for (int k = 0; k < N; ++k) v[k] = so_wave_sum_32to1(v[k]);
         if constexpr (WPR > 1) {
             if (lane == 0) {
 #pragma unroll
@@ -31,12 +31,12 @@
     if (ray >= a.n_rays) return;  // wave-uniform (block-uniform when the waves share a ray)
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
     const int S = a.n_samples;
-    const RayGeomB g = load_ray(a, ray);
+    const RayGeom g = so_ray_of(a, ray);
     float Y[NB > 0 ? NB : 1];
     if constexpr (NB > 0) so_sh_basis<NB>(g.dx, g.dy, g.dz, Y);
 
     float tn, tf;
-    ray_bounds(a, g, tn, tf);
+    so_collide(a, g, tn, tf);
 
     // ---- phase A: per-sample forward state -------------------------------------------------
     so_cell cell[M];
@@ -47,7 +47,7 @@
         const int i = (j * WPR + wstep) * 64 + lane;   // a step covers 64 CONSECUTIVE samples (one per lane)
         live[j] = i < S;
         const int ic = live[j] ? i : S - 1;
-        const float t0 = edge_t(a, ray, ic, tn, tf), t1 = edge_t(a, ray, ic + 1, tn, tf);
+        const float t0 = so_edge(a, ray, ic, tn, tf), t1 = so_edge(a, ray, ic + 1, tn, tf);
         delta[j] = t1 - t0;
         tmid[j] = (t0 + t1) / 2.0f;
         cell[j] = sample_cell<MK>(a, g, t0, t1);
@@ -476,7 +476,7 @@
         }
     }
     if (ba.g_inv_s) {
-        const float t = wave_sum(dinv_s_l);
+        const float t = so_wave_sum_32to1(dinv_s_l);
         // BIN: kInvsSlots partial sums (rb_brick_kernel's first block adds them up) instead of one atomic per wave on ONE word
         if (lane == 0) unsafeAtomicAdd(BIN ? bin.invs_part + (blockIdx.x & (kInvsSlots - 1)) : ba.g_inv_s, t);
     }

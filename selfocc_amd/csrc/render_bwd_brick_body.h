@@ -7,7 +7,7 @@
     if (blockIdx.x == 0 && g_inv_s) {   // the ray kernel's partial sums of d L / d inv_s: one atomic per wave of this block
         float t = 0.0f;
         for (int k = threadIdx.x; k < kInvsSlots; k += NT) t += b.invs_part[k];
-        t = wave_sum(t);
+        t = so_wave_sum_32to1(t);
         if ((threadIdx.x & 63) == 0) unsafeAtomicAdd(g_inv_s, t);
     }
     if ((int)blockIdx.x >= b.n_items[0]) return;

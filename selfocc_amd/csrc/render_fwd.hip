@@ -5,7 +5,9 @@
 //   ray generation -> AABB collider -> S uniform samples -> meter2grid -> trilinear
 //   lookup of the SDF / colour / semantic volume (+ analytic gradient) -> NeuS alpha ->
 //   transmittance -> weights -> depth / acc / rgb / sem / max-depth.
-// No per-sample tensor touches HBM unless the caller asks for the training outputs.
+// No per-sample tensor touches HBM: launches that ask for the per-sample training outputs go to the sample-parallel
+// kernels of render_train.hip (dispatch_ps / dispatch_sh below).  Ray construction, the box collider and the bin edges are
+// those of ray_device.h, shared with render_train.hip and render_bwd.hip; the marches a kernel can run are `enum class March`.
 //
 // Mapping to the hardware: one ray per lane; in pixel-grid mode a 64-lane wavefront owns
 // an 8x8 pixel tile so that, at every march step, the 64 gathers of a wave fall into a
@@ -15,13 +17,7 @@
 // that scans across lanes).
 #include "so_device.h"
 #include "sh_device.h"
-
-#ifdef SO_STAGE_STATS
-__device__ unsigned long long g_stage_stats[2];
-extern "C" int selfocc_debug_stage_stats(unsigned long long *out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stage_stats), sizeof(unsigned long long) * 2);
-}
-#endif
+#include "ray_device.h"
 
 // render_train.hip
 template <int NF, bool BF16>
@@ -31,13 +27,9 @@ int so_render_sh_samples(const so_render_args &a, hipStream_t st);
 
 namespace {
 
-struct RayGeom {
-    float ox, oy, oz, dx, dy, dz, dn;
-};
-
+// The pixel-grid ray of so_ray_of (ray_device.h), operation for operation, for kernels whose block sits on ONE camera: a
+// different code shape on purpose (scalar loads of the camera matrix), not a second definition of the rule.
 SO_DEVFN RayGeom so_pixel_ray(const so_render_args &a, int cam, int ix, int iy) {
-    // RaySampler 'fixed' / 'cellular' lattice (ray_sampler.py:23-31, 58-68) and
-    // Img2LiDAR.forward (img2lidar.py:58-69): origin = M[:3,3], dir = M[:3,:3] (u,v,1)
     // the camera matrix is read-only for the launch and `cam` is block-uniform: constant address space, i.e. scalar loads
     // into SGPRs, also where `a` was re-read through an opaque pointer (so_march_fast_ahead's canonical cell)
     typedef const __attribute__((address_space(4))) float *so_const_fptr;
@@ -52,38 +44,6 @@ SO_DEVFN RayGeom so_pixel_ray(const so_render_args &a, int cam, int ix, int iy) 
     g.dn = sqrtf((dx * dx + dy * dy) + dz * dz);  // neus_head.py:326
     g.dx = dx / g.dn; g.dy = dy / g.dn; g.dz = dz / g.dn;
     return g;
-}
-
-// AABBBoxCollider (sdfstudio / nerfstudio scene_colliders, upstream)
-SO_DEVFN void so_collide(const so_render_args &a, const RayGeom &g, float &tnear, float &tfar) {
-    float fx = 1.0f / (g.dx + 1e-6f), fy = 1.0f / (g.dy + 1e-6f), fz = 1.0f / (g.dz + 1e-6f);
-    float t1 = (a.aabb[0] - g.ox) * fx, t2 = (a.aabb[3] - g.ox) * fx;
-    float t3 = (a.aabb[1] - g.oy) * fy, t4 = (a.aabb[4] - g.oy) * fy;
-    float t5 = (a.aabb[2] - g.oz) * fz, t6 = (a.aabb[5] - g.oz) * fz;
-    tnear = fmaxf(fmaxf(fminf(t1, t2), fminf(t3, t4)), fminf(t5, t6));
-    tfar = fminf(fminf(fmaxf(t1, t2), fmaxf(t3, t4)), fmaxf(t5, t6));
-    tnear = fmaxf(tnear, a.near_plane);
-    tfar = fmaxf(tfar, tnear + 1e-6f);
-}
-
-// torch.linspace(0, 1, n + 1)[j] in float32 (ATen RangeFactories: symmetric halves)
-SO_DEVFN float so_bin(int j, int n) {
-    float step = 1.0f / (float)n;
-    return (j < (n + 1) / 2) ? step * (float)j : fmaf(-step, (float)(n - j), 1.0f);
-}
-
-// UniformSampler bin edge j of a ray (spaced sampler, train_stratified jitter optional)
-SO_DEVFN float so_edge(const so_render_args &a, int ray, int j, float tnear, float tfar) {
-    int n = a.n_samples;
-    float b = so_bin(j, n);
-    if (a.jitter_mode != SO_JITTER_NONE) {
-        float lo = (j == 0) ? b : (b + so_bin(j - 1, n)) / 2.0f;
-        float hi = (j == n) ? b : (so_bin(j + 1, n) + b) / 2.0f;
-        float tr = (a.jitter_mode == SO_JITTER_SINGLE) ? a.t_rand[ray]
-                                                        : a.t_rand[(size_t)ray * (n + 1) + j];
-        b = lo + (hi - lo) * tr;
-    }
-    return b * tfar + (1.0f - b) * tnear;
 }
 
 template <int NF, bool BF16>
@@ -187,7 +147,7 @@ SO_DEVFN void so_gather_feat_interior(__amdgpu_buffer_rsrc_t rf, int W, int D, u
 
 // MK: the mapping kind (SO_MAP_LINEAR / SO_MAP_UPSCALE), a compile-time choice of so_locate_k
 // NB > 0: spherical-harmonics colour with NB basis functions (sh_device.h); NF is then the row stride of the coefficients
-template <int NF, bool BF16, bool PER_SAMPLE, int MK = SO_MAP_LINEAR, int NB = 0>
+template <int NF, bool BF16, int MK = SO_MAP_LINEAR, int NB = 0>
 SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g) {
     constexpr int NSEM = (NB == 0 && NF > 4) ? NF - 3 : 0;  // NF = 3 rgb (+1 pad) or 3 rgb + n_sem
     float Y[NB > 0 ? NB : 1];                   // the ray's basis: once, before the march
@@ -269,14 +229,6 @@ SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g)
 #pragma unroll
                 for (int k = 0; k < NSEM; ++k) sem[k] = fmaf(wd, e[k], sem[k]);
             }
-        }
-        if constexpr (PER_SAMPLE) {
-            size_t o = (size_t)ray * S + i;
-            if (a.weights) a.weights[o] = w;
-            if (a.ts) a.ts[o] = tz;
-            if (a.deltas) a.deltas[o] = dz_;
-            if (a.sdf) a.sdf[o] = sdf;
-            if (a.grad) { a.grad[3 * o] = gx; a.grad[3 * o + 1] = gy; a.grad[3 * o + 2] = gz; }
         }
     }
 
@@ -496,11 +448,6 @@ SO_DEVFN void so_gather_feat_staged(__amdgpu_buffer_rsrc_t rf, const void *__res
                 so_fma4_bcast(f[4 * q + 0], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3], t.x, t.y,
                               t.z, t.w, wgt);
             }
-#ifdef SO_STAGE_SCHED
-            // keep at most SO_STAGE_SCHED corners' reads in flight: without this the scheduler hoists
-            // all 48 ds_read_b128 (192 VGPRs) and the kernel drops to 2 waves / SIMD
-            if constexpr (NF >= 16) { if ((kk % SO_STAGE_SCHED) == SO_STAGE_SCHED - 1) __builtin_amdgcn_sched_barrier(0); }
-#endif
         }
     } else {
 #pragma unroll
@@ -523,6 +470,20 @@ SO_DEVFN void so_gather_feat_staged(__amdgpu_buffer_rsrc_t rf, const void *__res
     __builtin_amdgcn_wave_barrier();   // the next step's stores must not overtake these reads
 }
 
+// The launch arguments re-read from the kernarg segment through a pointer the optimiser cannot see through (the kernels
+// take so_render_args as their FIRST parameter): only the fields used are loaded (s_load), where they are used, and nothing
+// is shared with (or hoisted out of a loop as) the copy the kernel started with.
+SO_DEVFN so_render_args so_reload_args() {
+    typedef const __attribute__((address_space(4))) uint32_t *so_kernarg_ptr;
+    so_kernarg_ptr ka = (so_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    so_render_args ac;
+    static_assert(sizeof(ac) % 4 == 0, "so_render_args is dword-sized");
+#pragma unroll
+    for (unsigned k = 0; k < sizeof(ac) / 4; ++k) ((uint32_t *)&ac)[k] = ka[k];
+    return ac;
+}
+
 // what `fetch` leaves in registers for one march step
 template <int NF>
 struct FastStep {
@@ -539,7 +500,7 @@ struct FastStep {
 
 // `geom()` returns the lane's ray; it is called once up front and again inside the (rare) canonical cell
 // fallback, so that origin / direction / far need not stay in registers across the march loop.
-template <int NF, bool BF16, bool PER_SAMPLE, bool STAGED = false, bool FACE_SAFE = false, class GeomFn>
+template <int NF, bool BF16, bool STAGED = false, bool FACE_SAFE = false, class GeomFn>
 SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool store = true,
                              float *lds = nullptr, int lane = 0, float *sem_lds = nullptr) {
     constexpr int NSEM = NF > 4 ? NF - 3 : 0;
@@ -586,8 +547,8 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
     const __amdgpu_buffer_rsrc_t rb = so_make_rsrc(a.sdf_brick, use_brick ? (size_t)n_cells * 33 : 0);
     const unsigned lane_vox = (unsigned)(((lane >> 4) * W + ((lane >> 2) & 3)) * D + (lane & 3));  // block voxel of this lane
     const __amdgpu_buffer_rsrc_t rf = so_make_rsrc(a.feat_vol, NF > 0 ? (size_t)H * W * D * NF * (BF16 ? 2 : 4) : 0);
-    // free-space skipping (see so_skip_unit): SDF-only launches that write no per-sample tensors
-    constexpr bool CAN_SKIP = (NF == 0) && !PER_SAMPLE;
+    // free-space skipping (see so_skip_unit): SDF-only launches
+    constexpr bool CAN_SKIP = NF == 0;
     const bool use_skip = CAN_SKIP && use_brick && !(a.flags & SO_FLAG_NO_SKIP);          // uniform
     // the ray's own step, rounded UP to skip-code units (>= 1; > 255 never skips)
     const int rcode = use_skip ? max((int)ceilf(dt / so_skip_unit(a.aabb, S)), 1) : 0x7fffffff;
@@ -622,16 +583,9 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
             return so_locate(a.map, px, py, pz);
         } else {
             // 20+ feature channels: registers are the scarce resource (2 waves / SIMD).  The ray and the launch
-            // arguments are re-derived inside this rare branch; the arguments are re-read from the kernarg segment
-            // through a pointer the optimiser cannot see through (both kernels take so_render_args as their FIRST
-            // parameter), otherwise every mapping / camera constant is hoisted out of the march loop into ~40 SGPRs.
-            typedef const __attribute__((address_space(4))) uint32_t *so_kernarg_ptr;
-            so_kernarg_ptr ka = (so_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
-            asm volatile("" : "+s"(ka));
-            so_render_args ac;                       // only the fields used below are actually loaded (s_load)
-            static_assert(sizeof(ac) % 4 == 0, "so_render_args is dword-sized");
-#pragma unroll
-            for (unsigned k = 0; k < sizeof(ac) / 4; ++k) ((uint32_t *)&ac)[k] = ka[k];
+            // arguments are re-derived inside this rare branch from arguments re-read from the kernarg segment
+            // (so_reload_args), otherwise every mapping / camera constant is hoisted out of the march loop into ~40 SGPRs.
+            const so_render_args ac = so_reload_args();
             const RayGeom gc = geom(ac);
             float tn, tf;
             so_collide(ac, gc, tn, tf);
@@ -707,9 +661,6 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
         st.boxed = false; st.pref = false;
         if constexpr (STAGED) {
             st.boxed = so_stage_box(h0, w0, d0, H, W, D, st.hmin, st.wmin, st.dmin);
-#ifdef SO_STAGE_STATS
-            if (lane == 0) atomicAdd(&g_stage_stats[st.boxed ? 0 : 1], 1ull);
-#endif
             if (PIPE && st.boxed && st.hmin + 3 < H && st.wmin + 3 < W && st.dmin + 3 < D) {   // block inside the volume
                 const unsigned vo = ((unsigned)((st.hmin * W + st.wmin) * D + st.dmin) + lane_vox) * (NF * 4u);
 #pragma unroll
@@ -816,16 +767,6 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
                 }
             }
         }
-        if constexpr (PER_SAMPLE) {
-            size_t o = (size_t)ray * S + i;
-            if (a.weights) a.weights[o] = w;
-            if (a.ts) a.ts[o] = t_mid * inv_dn;
-            if (a.deltas) a.deltas[o] = dt * inv_dn;
-            if (a.sdf) a.sdf[o] = sdf;
-            if (a.grad) {
-                a.grad[3 * o] = gvw * kw.k1; a.grad[3 * o + 1] = gvh * kh.k1; a.grad[3 * o + 2] = gvd * kd.k1;
-            }
-        }
     };
 
     // Light kernels (NF < 8) run a two-stage software pipeline with ping-pong register sets: the
@@ -839,18 +780,18 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
             if (i + 1 < S) fetch(i + 1, B);
             consume(i, A);
             if (++i >= S) break;
-            if constexpr (!PER_SAMPLE) { if (so_all(T < 1e-10f)) break; }
+            if (so_all(T < 1e-10f)) break;
             if (i + 1 < S) fetch(i + 1, A);
             consume(i, B);
             if (++i >= S) break;
-            if constexpr (!PER_SAMPLE) { if (so_all(T < 1e-10f)) break; }
+            if (so_all(T < 1e-10f)) break;
         }
     } else {
         for (int i = 0; i < S; ++i) {
             FastStep<NF> A;
             fetch(i, A);
             consume(i, A);
-            if constexpr (!PER_SAMPLE) { if (so_all(T < 1e-10f)) break; }
+            if (so_all(T < 1e-10f)) break;
         }
     }
 
@@ -898,20 +839,6 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
 // A skipped step moves 1 byte per lane through the L1 instead of 33.  Nothing is software-pipelined beyond
 // that: measurements showed the march insensitive to load/compute overlap inside a wave (8 waves / SIMD hide it).
 // ---------------------------------------------------------------------------------------
-// The launch arguments re-read from the kernarg segment through a pointer the optimiser cannot see through (the kernels
-// take so_render_args as their FIRST parameter): only the fields used are loaded (s_load), where they are used, and nothing
-// is shared with (or hoisted out of a loop as) the copy the kernel started with.
-SO_DEVFN so_render_args so_reload_args() {
-    typedef const __attribute__((address_space(4))) uint32_t *so_kernarg_ptr;
-    so_kernarg_ptr ka = (so_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    so_render_args ac;
-    static_assert(sizeof(ac) % 4 == 0, "so_render_args is dword-sized");
-#pragma unroll
-    for (unsigned k = 0; k < sizeof(ac) / 4; ++k) ((uint32_t *)&ac)[k] = ka[k];
-    return ac;
-}
-
 struct AheadStep {
     float gh, gw, gd, fi;         // grid coordinates (the fractions are taken only by the steps that interpolate)
     int h0, w0, d0;
@@ -920,8 +847,7 @@ struct AheadStep {
 };
 
 template <bool FACE_SAFE, class GeomFn>
-SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom, float *lds = nullptr, int lane = 0,
-                                   bool store = true) {
+SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom) {
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
     const int S = a.n_samples;
     const RayGeom g = geom(a);
@@ -941,10 +867,6 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom,
     const unsigned n_cells = (unsigned)(H * W * D);
     const __amdgpu_buffer_rsrc_t rb = so_make_rsrc(a.sdf_brick, (size_t)n_cells * 33);
     const __amdgpu_buffer_rsrc_t rs = so_make_rsrc(vol, (size_t)n_cells * 4);
-#ifdef SO_AHEAD_LDS
-    // A/B: the wave's 4x4x4 corner block through LDS instead of two 16-B record gathers per lane
-    const unsigned lane_vox = (unsigned)(((lane >> 4) * W + ((lane >> 2) & 3)) * D + (lane & 3));
-#endif
     const int rcode = max((int)ceilf(dt / so_skip_unit(a.aabb, S)), 1);
     const int maxdim = max(H, max(W, D));
     const float face_m = 3.0f * 1.1920929e-7f * (float)(1u << (32 - __builtin_clz((unsigned)maxdim)));
@@ -1036,22 +958,6 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom,
             }
             if (!loaded) {
                 if (cur.all_interior) {
-#ifdef SO_AHEAD_LDS
-                    int hmin, wmin, dmin;
-                    const bool boxed = lds != nullptr && so_stage_box(cur.h0, cur.w0, cur.d0, H, W, D, hmin, wmin, dmin) &&
-                                       hmin + 3 < H && wmin + 3 < W && dmin + 3 < D;
-                    if (boxed) {      // lane <-> corner (lane >> 4, (lane >> 2) & 3, lane & 3) of the block: ONE dword load per lane
-                        const unsigned vo = ((unsigned)((hmin * W + wmin) * D + dmin) + lane_vox) * 4u;
-                        lds[lane] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, 0u, 0));
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                        const float *q = lds + (((cur.h0 - hmin) * 4 + (cur.w0 - wmin)) * 4 + (cur.d0 - dmin));
-                        p0 = so_f32x2{q[0], q[16]}; p1 = so_f32x2{q[1], q[17]}; p2 = so_f32x2{q[4], q[20]}; p3 = so_f32x2{q[5], q[21]};
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                    } else
-#endif
                     {   // one 32-B record = the four corner pairs, in the register order so_trilerp_fast_pk takes them
                         // (issuing these loads before locate() above, to run it under them, measured 9 % SLOWER)
                         const so_f4v lo = so_bload4(rb, cur.cell * 32u, 0u), hi = so_bload4(rb, cur.cell * 32u + 16u, 0u);
@@ -1091,7 +997,6 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom,
     if (dt * inv_dn < eps32) best_t = tnear + hdt;
     float depth = dsum * so_fast_rcp(acc + 1e-10f);
     if (a.flags & SO_FLAG_DEPTH_DIV_NORM) depth = depth * inv_dn;
-    if (!store) return;
     if (a.depth) a.depth[ray] = depth;
     if (a.acc) a.acc[ray] = acc;
     if (a.max_depth) a.max_depth[ray] = best_t * inv_dn;
@@ -1099,20 +1004,33 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom,
     if (a.fars) a.fars[ray] = tfar;
 }
 
-// MODE: 0 = canonical (EXACT), 1 = fast, 2 = fast with canonical cell selection near voxel faces,
-//       3 / 4 = the code-ahead skip marcher (SDF-only per-ray launches with brick + skip) without / with it,
-//       5 = canonical under the 'linear_upscale' mapping (g(t) is not affine: no fast path, no brick, no skip)
-template <int NF, bool BF16, bool PER_SAMPLE, int MODE, class GeomFn>
-SO_DEVFN void so_march(const so_render_args &a, int ray, GeomFn geom, float *lds = nullptr, int lane = 0, bool store = true) {
-    if constexpr (MODE == 5) {
-        so_march_exact<NF, BF16, PER_SAMPLE, SO_MAP_UPSCALE>(a, ray, geom(a));
-    } else if constexpr (MODE >= 3) {
-        static_assert(NF == 0 && !PER_SAMPLE, "skip marcher: SDF-only per-ray launches");
-        so_march_fast_ahead<MODE == 4>(a, ray, geom, lds, lane, store);
-    } else if constexpr (MODE != 0) {
-        so_march_fast<NF, BF16, PER_SAMPLE, false, MODE == 2>(a, ray, geom);
+// The march a kernel runs: a compile-time choice of the dispatch below.
+enum class March {
+    Canonical,          // so_march_exact: the oracle's operation order (SO_FLAG_EXACT, jitter, two-segment axes)
+    Fast,               // so_march_fast
+    FastFaceSafe,       // so_march_fast with canonical cell selection near voxel faces
+    Skip,               // so_march_fast_ahead, the code-ahead skip marcher (SDF-only launches with brick + skip codes)
+    SkipFaceSafe,       // so_march_fast_ahead with canonical cell selection near voxel faces
+    CanonicalUpscale,   // so_march_exact under the 'linear_upscale' mapping (g(t) is not affine: no fast path, no brick, no skip)
+};
+constexpr bool so_is_fast(March m) { return m == March::Fast || m == March::FastFaceSafe; }
+constexpr bool so_is_skip(March m) { return m == March::Skip || m == March::SkipFaceSafe; }
+constexpr bool so_face_safe(March m) { return m == March::FastFaceSafe || m == March::SkipFaceSafe; }
+// the fast march with the wave's voxel neighbourhood staged in LDS (so_gather_feat_staged): pixel-grid launches only
+template <int NF, bool BF16>
+constexpr bool so_is_staged(March m) { return so_is_fast(m) && !BF16 && NF >= 4; }
+
+template <int NF, bool BF16, March MODE, class GeomFn>
+SO_DEVFN void so_march(const so_render_args &a, int ray, GeomFn geom) {
+    if constexpr (MODE == March::CanonicalUpscale) {
+        so_march_exact<NF, BF16, SO_MAP_UPSCALE>(a, ray, geom(a));
+    } else if constexpr (so_is_skip(MODE)) {
+        static_assert(NF == 0, "skip marcher: SDF-only launches");
+        so_march_fast_ahead<so_face_safe(MODE)>(a, ray, geom);
+    } else if constexpr (so_is_fast(MODE)) {
+        so_march_fast<NF, BF16, false, so_face_safe(MODE)>(a, ray, geom);
     } else {
-        so_march_exact<NF, BF16, PER_SAMPLE>(a, ray, geom(a));
+        so_march_exact<NF, BF16>(a, ray, geom(a));
     }
 }
 
@@ -1155,38 +1073,32 @@ __global__ __launch_bounds__(256) void sdf_brickify_kernel(const float *__restri
     codes[cell] = (uint8_t)code;
 }
 
-// explicit rays: one ray per thread, linear order
-#ifndef SO_WAVES_FEAT
-#define SO_WAVES_FEAT 2   // min waves / SIMD requested for the feature-carrying kernels (A/B knob)
-#endif
-template <int NF, bool BF16, bool PER_SAMPLE, int MODE>
-__global__ __launch_bounds__(256, (NF >= 8 ? SO_WAVES_FEAT : 1)) void render_fwd_explicit(so_render_args a) {
-    int ray = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ray >= a.n_rays) return;
-    auto geom = [&](const so_render_args &a) __attribute__((always_inline)) {
-        RayGeom g;
-        g.ox = a.origins[3 * (size_t)ray]; g.oy = a.origins[3 * (size_t)ray + 1];
-        g.oz = a.origins[3 * (size_t)ray + 2];
-        g.dx = a.dirs[3 * (size_t)ray]; g.dy = a.dirs[3 * (size_t)ray + 1];
-        g.dz = a.dirs[3 * (size_t)ray + 2];
-        g.dn = a.dir_norm ? a.dir_norm[ray] : 1.0f;
-        return g;
-    };
-    so_march<NF, BF16, PER_SAMPLE, MODE>(a, ray, geom);
+// pixel-grid rays: a block is a 16x16 pixel tile of one camera, each of its four waves an 8x8 sub-tile
+struct TilePixel { int cam, ix, iy, wave, lane; };
+SO_DEVFN TilePixel so_tile_pixel(int tiles_x, int tiles_y) {
+    const int b = blockIdx.x;
+    const int cam = b / (tiles_x * tiles_y);
+    const int tb = b - cam * tiles_x * tiles_y;
+    const int ty = tb / tiles_x, tx = tb - ty * tiles_x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    return {cam, tx * 16 + (wave & 1) * 8 + (lane & 7), ty * 16 + (wave >> 1) * 8 + (lane >> 3), wave, lane};
 }
 
-// pixel-grid rays: block = 16x16 pixel tile of one camera, each wave an 8x8 sub-tile
-template <int NF, bool BF16, bool PER_SAMPLE, int MODE>
+// explicit rays: one ray per thread, linear order.  The feature-carrying kernels ask for 2 waves / SIMD.
+template <int NF, bool BF16, March MODE>
+__global__ __launch_bounds__(256, (NF >= 8 ? 2 : 1)) void render_fwd_explicit(so_render_args a) {
+    int ray = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ray >= a.n_rays) return;
+    auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_explicit_ray(a, ray); };
+    so_march<NF, BF16, MODE>(a, ray, geom);
+}
+
+template <int NF, bool BF16, March MODE>
 SO_DEVFN void pixgrid_body(const so_render_args &a, int tiles_x, int tiles_y) {
-    int b = blockIdx.x;
-    int cam = b / (tiles_x * tiles_y);
-    int tb = b - cam * tiles_x * tiles_y;
-    int ty = tb / tiles_x, tx = tb - ty * tiles_x;
-    int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int ix = tx * 16 + (wave & 1) * 8 + (lane & 7);
-    int iy = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
-    constexpr bool STAGED = MODE != 0 && MODE < 3 && !PER_SAMPLE && !BF16 && NF >= 4;
-    if constexpr (STAGED) {
+    const TilePixel p = so_tile_pixel(tiles_x, tiles_y);
+    const int cam = p.cam, wave = p.wave, lane = p.lane;
+    int ix = p.ix, iy = p.iy;
+    if constexpr (so_is_staged<NF, BF16>(MODE)) {
         // every lane keeps marching (the LDS staging is a whole-wave operation): lanes beyond the
         // lattice edge shadow the nearest real pixel and only skip the final store
         __shared__ __attribute__((aligned(16))) float s_stage[4 * StageGeom<NF>::kWaveDwords];
@@ -1196,58 +1108,43 @@ SO_DEVFN void pixgrid_body(const so_render_args &a, int tiles_x, int tiles_y) {
         auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_pixel_ray(a, cam, ix, iy); };
         constexpr int NSEM_LDS = NF - 3 >= 16 ? NF - 3 : 0;          // so_march_fast::SEM_LDS
         __shared__ float s_sem[NSEM_LDS > 0 ? NSEM_LDS * 256 : 1];
-        so_march_fast<NF, BF16, PER_SAMPLE, true, MODE == 2>(a, ray, geom, real, s_stage + wave * StageGeom<NF>::kWaveDwords, lane,
-                                                             s_sem + threadIdx.x);
+        so_march_fast<NF, BF16, true, so_face_safe(MODE)>(a, ray, geom, real, s_stage + wave * StageGeom<NF>::kWaveDwords, lane,
+                                                          s_sem + threadIdx.x);
     } else {
-#ifdef SO_AHEAD_LDS
-        if constexpr (MODE == 3 || MODE == 4) {
-            // whole-wave LDS staging: lanes beyond the lattice edge shadow the nearest real pixel and skip the stores
-            __shared__ float s_box[4 * 64];
-            const bool real = (ix < a.nx) && (iy < a.ny);
-            ix = min(ix, a.nx - 1); iy = min(iy, a.ny - 1);
-            int ray = (cam * a.ny + iy) * a.nx + ix;
-            auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_pixel_ray(a, cam, ix, iy); };
-            so_march<NF, BF16, PER_SAMPLE, MODE>(a, ray, geom, s_box + wave * 64, lane, real);
-            return;
-        }
-#endif
         if (ix >= a.nx || iy >= a.ny) return;
         int ray = (cam * a.ny + iy) * a.nx + ix;
         auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_pixel_ray(a, cam, ix, iy); };
-        so_march<NF, BF16, PER_SAMPLE, MODE>(a, ray, geom);
+        so_march<NF, BF16, MODE>(a, ray, geom);
     }
 }
 
-template <int NF, bool BF16, bool PER_SAMPLE, int MODE>
-__global__ __launch_bounds__(256, (NF >= 8 ? SO_WAVES_FEAT : 1)) void render_fwd_pixgrid(so_render_args a, int tiles_x,
-                                                                                         int tiles_y) {
-    pixgrid_body<NF, BF16, PER_SAMPLE, MODE>(a, tiles_x, tiles_y);
+template <int NF, bool BF16, March MODE>
+__global__ __launch_bounds__(256, (NF >= 8 ? 2 : 1)) void render_fwd_pixgrid(so_render_args a, int tiles_x, int tiles_y) {
+    pixgrid_body<NF, BF16, MODE>(a, tiles_x, tiles_y);
 }
 // The skip marchers (bench.py's kernel) at 8 waves / SIMD need <= 64 VGPRs AND <= 80 SGPRs: a CU admits
 // floor(800 / (ceil(sgpr / 16) * 16 + 16)) blocks of 256 threads, 7 at 82 - 96 SGPRs although the compiler's occupancy says 8.
 // Left alone the allocator spends 84 (constants the rare canonical branch needs, hoisted); capped it fits in 80 without spilling.
 template <>
-__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<0, false, false, 3>(
+__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<0, false, March::Skip>(
     so_render_args a, int tiles_x, int tiles_y) {
-    pixgrid_body<0, false, false, 3>(a, tiles_x, tiles_y);
+    pixgrid_body<0, false, March::Skip>(a, tiles_x, tiles_y);
 }
 template <>
-__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<0, false, false, 4>(
+__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<0, false, March::SkipFaceSafe>(
     so_render_args a, int tiles_x, int tiles_y) {
-    pixgrid_body<0, false, false, 4>(a, tiles_x, tiles_y);
+    pixgrid_body<0, false, March::SkipFaceSafe>(a, tiles_x, tiles_y);
 }
 
-template <int NF, bool BF16, bool PER_SAMPLE, int MODE>
+template <int NF, bool BF16, March MODE>
 int launch_fwd(const so_render_args &a, hipStream_t st) {
     if (a.ray_mode == SO_RAYS_EXPLICIT) {
         int blocks = (a.n_rays + 255) / 256;
-        hipLaunchKernelGGL((render_fwd_explicit<NF, BF16, PER_SAMPLE, MODE>), dim3(blocks), dim3(256), 0,
-                           st, a);
+        hipLaunchKernelGGL((render_fwd_explicit<NF, BF16, MODE>), dim3(blocks), dim3(256), 0, st, a);
     } else {
         int tiles_x = (a.nx + 15) / 16, tiles_y = (a.ny + 15) / 16;
         int blocks = tiles_x * tiles_y * a.n_cams;
-        hipLaunchKernelGGL((render_fwd_pixgrid<NF, BF16, PER_SAMPLE, MODE>), dim3(blocks), dim3(256), 0,
-                           st, a, tiles_x, tiles_y);
+        hipLaunchKernelGGL((render_fwd_pixgrid<NF, BF16, MODE>), dim3(blocks), dim3(256), 0, st, a, tiles_x, tiles_y);
     }
     return so_launch_status();
 }
@@ -1264,7 +1161,7 @@ int dispatch_ps(const so_render_args &a, hipStream_t st) {
         if constexpr (NF == 24 && BF16) {
             SO_REQUIRE(false, "the 'linear_upscale' mapping is built for n_rgb + n_sem = 0, 3, 8 and float32 24 (got bfloat16 24)");
         } else {
-            return launch_fwd<NF, BF16, false, 5>(a, st);
+            return launch_fwd<NF, BF16, March::CanonicalUpscale>(a, st);
         }
     }
     // the fast path needs g(t) affine in t: no jitter, single-segment axes, the linear mapping kind
@@ -1274,18 +1171,18 @@ int dispatch_ps(const so_render_args &a, hipStream_t st) {
     if (fast) {
         if (a.sdf_brick) {
             const int cells = a.map.h.tot_len * a.map.w.tot_len * a.map.d.tot_len;
-            const int with_codes = (NF == 0 && !per_sample && !(a.flags & SO_FLAG_NO_SKIP)) ? 1 : 0;
+            const int with_codes = (NF == 0 && !(a.flags & SO_FLAG_NO_SKIP)) ? 1 : 0;
             hipLaunchKernelGGL(sdf_brickify_kernel, dim3((cells + 255) / 256), dim3(256), 0, st, a.sdf_vol, a.sdf_brick,
                                a.map.h.tot_len, a.map.w.tot_len, a.map.d.tot_len, a, with_codes);
         }
         if constexpr (NF == 0) {
-            if (!per_sample && a.sdf_brick && !(a.flags & (SO_FLAG_NO_SKIP | SO_FLAG_NO_AHEAD)))
-                return (a.flags & SO_FLAG_NO_FACE_SAFE) ? launch_fwd<0, false, false, 3>(a, st) : launch_fwd<0, false, false, 4>(a, st);
+            if (a.sdf_brick && !(a.flags & (SO_FLAG_NO_SKIP | SO_FLAG_NO_AHEAD)))
+                return (a.flags & SO_FLAG_NO_FACE_SAFE) ? launch_fwd<0, false, March::Skip>(a, st) : launch_fwd<0, false, March::SkipFaceSafe>(a, st);
         }
-        if (!(a.flags & SO_FLAG_NO_FACE_SAFE)) return launch_fwd<NF, BF16, false, 2>(a, st);
-        return launch_fwd<NF, BF16, false, 1>(a, st);
+        if (!(a.flags & SO_FLAG_NO_FACE_SAFE)) return launch_fwd<NF, BF16, March::FastFaceSafe>(a, st);
+        return launch_fwd<NF, BF16, March::Fast>(a, st);
     }
-    return launch_fwd<NF, BF16, false, 0>(a, st);
+    return launch_fwd<NF, BF16, March::Canonical>(a, st);
 }
 
 // ---- spherical-harmonics colour (sh_deg > 0 or sh_act != relu): ray per lane, canonical march -------------------------------
@@ -1294,15 +1191,12 @@ template <int NB, int MK>
 __global__ __launch_bounds__(256) void render_sh_explicit(so_render_args a) {
     const int ray = blockIdx.x * blockDim.x + threadIdx.x;
     if (ray >= a.n_rays) return;
-    RayGeom g;
-    g.ox = a.origins[3 * (size_t)ray]; g.oy = a.origins[3 * (size_t)ray + 1]; g.oz = a.origins[3 * (size_t)ray + 2];
-    g.dx = a.dirs[3 * (size_t)ray]; g.dy = a.dirs[3 * (size_t)ray + 1]; g.dz = a.dirs[3 * (size_t)ray + 2];
-    g.dn = a.dir_norm ? a.dir_norm[ray] : 1.0f;
-    so_march_exact<so_sh_stride(NB), false, false, MK, NB>(a, ray, g);
+    so_march_exact<so_sh_stride(NB), false, MK, NB>(a, ray, so_explicit_ray(a, ray));
 }
 
 template <int NB, int MK>
 __global__ __launch_bounds__(256) void render_sh_pixgrid(so_render_args a, int tiles_x, int tiles_y) {
+    // (written out: through so_tile_pixel the compiler commutes the operands of one scalar multiply and one add)
     const int b = blockIdx.x;
     const int cam = b / (tiles_x * tiles_y);
     const int tb = b - cam * tiles_x * tiles_y;
@@ -1312,7 +1206,7 @@ __global__ __launch_bounds__(256) void render_sh_pixgrid(so_render_args a, int t
     const int iy = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
     if (ix >= a.nx || iy >= a.ny) return;
     const int ray = (cam * a.ny + iy) * a.nx + ix;
-    so_march_exact<so_sh_stride(NB), false, false, MK, NB>(a, ray, so_pixel_ray(a, cam, ix, iy));
+    so_march_exact<so_sh_stride(NB), false, MK, NB>(a, ray, so_pixel_ray(a, cam, ix, iy));
 }
 
 template <int NB, int MK>

@@ -21,66 +21,11 @@
 //   * every per-sample store is a coalesced 256-byte row segment.
 #include "so_device.h"
 #include "sh_device.h"
+#include "ray_device.h"
 
 namespace {
 
-struct TrainRay {
-    float ox, oy, oz, dx, dy, dz, dn;
-};
-
-// RaySampler lattice + Img2LiDAR (ray_sampler.py:23-31, 58-68; img2lidar.py:58-69; neus_head.py:326)
-SO_DEVFN TrainRay so_train_ray(const so_render_args &a, int ray) {
-    TrainRay g;
-    if (a.ray_mode == SO_RAYS_PIXEL_GRID) {
-        const int per_cam = a.nx * a.ny;
-        const int cam = ray / per_cam, rem = ray - cam * per_cam;
-        const int iy = rem / a.nx, ix = rem - iy * a.nx;
-        const float *M = a.img2lidar + cam * 16;
-        const float u = (float)ix * a.sx + a.ox;
-        const float v = (float)iy * a.sy + a.oy;
-        g.ox = M[3]; g.oy = M[7]; g.oz = M[11];
-        const float dx = (M[0] * u + M[1] * v) + M[2];
-        const float dy = (M[4] * u + M[5] * v) + M[6];
-        const float dz = (M[8] * u + M[9] * v) + M[10];
-        g.dn = sqrtf((dx * dx + dy * dy) + dz * dz);
-        g.dx = dx / g.dn; g.dy = dy / g.dn; g.dz = dz / g.dn;
-    } else {
-        g.ox = a.origins[3 * (size_t)ray]; g.oy = a.origins[3 * (size_t)ray + 1]; g.oz = a.origins[3 * (size_t)ray + 2];
-        g.dx = a.dirs[3 * (size_t)ray]; g.dy = a.dirs[3 * (size_t)ray + 1]; g.dz = a.dirs[3 * (size_t)ray + 2];
-        g.dn = a.dir_norm ? a.dir_norm[ray] : 1.0f;
-    }
-    return g;
-}
-
-// AABBBoxCollider, canonical order (identical to render_fwd.hip so_collide)
-SO_DEVFN void so_train_collide(const so_render_args &a, const TrainRay &g, float &tnear, float &tfar) {
-    const float fx = 1.0f / (g.dx + 1e-6f), fy = 1.0f / (g.dy + 1e-6f), fz = 1.0f / (g.dz + 1e-6f);
-    const float t1 = (a.aabb[0] - g.ox) * fx, t2 = (a.aabb[3] - g.ox) * fx;
-    const float t3 = (a.aabb[1] - g.oy) * fy, t4 = (a.aabb[4] - g.oy) * fy;
-    const float t5 = (a.aabb[2] - g.oz) * fz, t6 = (a.aabb[5] - g.oz) * fz;
-    tnear = fmaxf(fmaxf(fminf(t1, t2), fminf(t3, t4)), fminf(t5, t6));
-    tfar = fminf(fminf(fmaxf(t1, t2), fmaxf(t3, t4)), fmaxf(t5, t6));
-    tnear = fmaxf(tnear, a.near_plane);
-    tfar = fmaxf(tfar, tnear + 1e-6f);
-}
-
-SO_DEVFN float so_train_bin(int j, int n) {   // torch.linspace(0, 1, n + 1)[j], float32
-    const float step = 1.0f / (float)n;
-    return (j < (n + 1) / 2) ? step * (float)j : fmaf(-step, (float)(n - j), 1.0f);
-}
-
-SO_DEVFN float so_train_edge(const so_render_args &a, int ray, int j, float tnear, float tfar) {
-    const int n = a.n_samples;
-    float b = so_train_bin(j, n);
-    if (a.jitter_mode != SO_JITTER_NONE) {
-        const float lo = (j == 0) ? b : (b + so_train_bin(j - 1, n)) / 2.0f;
-        const float hi = (j == n) ? b : (so_train_bin(j + 1, n) + b) / 2.0f;
-        const float tr = (a.jitter_mode == SO_JITTER_SINGLE) ? a.t_rand[ray] : a.t_rand[(size_t)ray * (n + 1) + j];
-        b = lo + (hi - lo) * tr;
-    }
-    return b * tfar + (1.0f - b) * tnear;
-}
-
+// so_gather_feat (render_fwd.hip) with four scalar fmaf per 16 bytes where that one issues two packed FMAs: merging the two changes 27 training kernels
 template <int NF, bool BF16>
 SO_DEVFN void so_train_feat(const void *__restrict__ vol, int H, int W, int D, const so_cell &c, const float wk[8],
                             float f[NF > 0 ? NF : 1]) {
@@ -115,12 +60,6 @@ SO_DEVFN void so_train_feat(const void *__restrict__ vol, int H, int W, int D, c
             }
         }
     }
-}
-
-SO_DEVFN float so_wave_sum(float v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
 }
 
 // WPR = waves per ray (1, 2 or 4); a 256-thread block serves 4 / WPR rays.  MK = mapping kind (so_locate_k).

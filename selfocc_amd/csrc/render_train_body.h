@@ -14,9 +14,9 @@
     const int ray_raw = blockIdx.x * RPB + rslot;
     const bool live = ray_raw < a.n_rays;                       // wave-uniform; dead waves still join the barriers
     const int ray = live ? ray_raw : 0;
-    const TrainRay g = so_train_ray(a, ray);
+    const RayGeom g = so_ray_of(a, ray);
     float tnear, tfar;
-    so_train_collide(a, g, tnear, tfar);
+    so_collide(a, g, tnear, tfar);
     const float eps32 = 1.1920928955078125e-07f;
     float Y[NB > 0 ? NB : 1];
     if constexpr (NB > 0) so_sh_basis<NB>(g.dx, g.dy, g.dz, Y);
@@ -39,8 +39,8 @@
         for (int k = 0; k < (NB == 0 ? NF : 0); ++k) f[k] = 0.0f;
         float raw[3] = {0.0f, 0.0f, 0.0f};
         if (valid) {
-            const float t_start = so_train_edge(a, ray, i, tnear, tfar);
-            const float t_end = so_train_edge(a, ray, i + 1, tnear, tfar);
+            const float t_start = so_edge(a, ray, i, tnear, tfar);
+            const float t_end = so_edge(a, ray, i + 1, tnear, tfar);
             const float delta = t_end - t_start;
             t_mid = (t_start + t_end) / 2.0f;
             float px, py, pz;
@@ -132,12 +132,12 @@
     }
 
     // ---- per-ray outputs: wave reductions, then the waves of a ray through LDS ----------------------
-    acc = so_wave_sum(acc);
-    dsum = so_wave_sum(dsum);
+    acc = so_wave_sum_1to32(acc);
+    dsum = so_wave_sum_1to32(dsum);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) rgb[k] = so_wave_sum(rgb[k]);
+    for (int k = 0; k < 3; ++k) rgb[k] = so_wave_sum_1to32(rgb[k]);
 #pragma unroll
-    for (int k = 0; k < NSEM; ++k) sem[k] = so_wave_sum(sem[k]);
+    for (int k = 0; k < NSEM; ++k) sem[k] = so_wave_sum_1to32(sem[k]);
     // arg-max of w / delta: the FIRST maximal sample, like torch.argmax
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) {

@@ -1,6 +1,6 @@
 """CPU: the register budget of the SDF-only skip marcher (the kernel bench.py times), as the gfx950 compiler reports it.
 
-render_fwd_pixgrid<0, false, false, 4> runs at 8 waves / SIMD only with <= 64 VGPRs (allocation granule 8) and <= 80 SGPRs
+render_fwd_pixgrid<0, false, March::SkipFaceSafe> runs at 8 waves / SIMD only with <= 64 VGPRs (allocation granule 8) and <= 80 SGPRs
 (a CU admits floor(800 / (ceil(sgpr / 16) * 16 + 16)) blocks of 256 threads), and without scratch.  The rare canonical
 cell selection near voxel faces re-derives the ray and the mapping inside its branch instead of keeping them live across
 the march loop; this test keeps a later change from quietly bringing them back."""
@@ -36,8 +36,8 @@ def _resources(src):
 @pytest.mark.skipif(not shutil.which(HIPCC), reason="hipcc not present")
 def test_skip_marcher_fits_eight_waves_per_simd():
     table = _resources(os.path.join(ROOT, "selfocc_amd", "csrc", "render_fwd.hip"))
-    # _ZN12_GLOBAL__N_118render_fwd_pixgridILi0ELb0ELb0ELi4EEEv14so_render_argsii = render_fwd_pixgrid<0, false, false, 4>
-    hits = {k: v for k, v in table.items() if "render_fwd_pixgridILi0ELb0ELb0ELi4E" in k}
+    # _ZN12_GLOBAL__N_118render_fwd_pixgridILi0ELb0ELNS_5MarchE4EEEv14so_render_argsii = render_fwd_pixgrid<0, false, March::SkipFaceSafe>
+    hits = {k: v for k, v in table.items() if "render_fwd_pixgridILi0ELb0ELNS_5MarchE4E" in k}
     assert len(hits) == 1, sorted(table)
     r = next(iter(hits.values()))
     assert r["VGPRs"] + r.get("AGPRs", 0) <= 64, r
