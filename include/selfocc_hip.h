@@ -514,6 +514,34 @@ int selfocc_flatten_feats(const float *const *feats, const int32_t *host_hw, int
                           const float *cams_embeds, const float *level_embeds, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * CameraAwareSE fused with the flatten above (model/encoder/tpvformer/modules/camera_se_net.py and its call site
+ * tpvformer_encoder.py:258-277): the per-camera gate and the 1x1 `context_conv`, then the camera / level embeddings, as ONE
+ * batched GEMM from the maps as they lie in memory to the encoders' `value`:
+ *     out[n][start_l + p][b][c] = sum_k w[c][k] gate[b*N+n][k] feats[l][b][n][k][p] + bias[c] + cams_embeds[n][c] + level_embeds[l][c]
+ * feats: HOST array of n_levels device pointers to (B, N, M, h_l, w_l) float32 maps, host_hw[l] = h_l * w_l >= 1 (any
+ * pixel count); gate (B*N, M); w (C, M); bias (C); cams_embeds (N, C); level_embeds (>= n_levels, C); out (N, sum hw, B, C).
+ * Backward, from g = d out (N, sum hw, B, C):
+ *     d_feats[l][b][n][k][p] = sum_c w[c][k] gate[b*N+n][k] g[n][start_l + p][b][c]      (d_feats NULL or d_feats[l] NULL: skipped)
+ *     dwc[b*N+n][c][k]       = sum_{l, p} g[n][start_l + p][b][c] feats[l][b][n][k][p]   (the UNGATED map; (B*N, C, M))
+ *     colsum[l][n][c]        = sum_{p in level l, b} g[n][start_l + p][b][c]             ((n_levels, N, C))
+ * from which the caller folds d w = sum_bn dwc * gate, d gate = sum_c dwc * w, d bias / d embeddings = sums of colsum.
+ * float32 (v_mfma_f32_16x16x4_f32: exact fmaf chains); the backward is deterministic (chunk partials in `workspace`, added in
+ * a fixed order; no float atomics).  Maps, gradients, out, g and the workspace must be 16-byte aligned.
+ * supported (selfocc_camera_se_supported: 1 / 0, host logic only): C in {32, 64, 96, 128}, M = C or 2 C with M <= 192,
+ * 1 <= n_levels <= 8, B, N >= 1 with B * N < 65535.  workspace: selfocc_camera_se_flatten_bwd_workspace(...) bytes (0: unsupported).
+ * Returns 0 / SELFOCC_ERR_*; every argument check happens before anything touches the device.
+ * ---------------------------------------------------------------------------------- */
+int selfocc_camera_se_supported(int32_t B, int32_t N, int32_t C, int32_t M, int32_t n_levels);
+int selfocc_camera_se_flatten_fwd(const float *const *feats, const int32_t *host_hw, int32_t n_levels, int32_t B, int32_t N,
+                                  int32_t C, int32_t M, const float *gate, const float *w, const float *bias,
+                                  const float *cams_embeds, const float *level_embeds, float *out, void *stream);
+size_t selfocc_camera_se_flatten_bwd_workspace(const int32_t *host_hw, int32_t n_levels, int32_t B, int32_t N, int32_t C,
+                                               int32_t M);
+int selfocc_camera_se_flatten_bwd(const float *g, const float *const *feats, const int32_t *host_hw, int32_t n_levels, int32_t B,
+                                  int32_t N, int32_t C, int32_t M, const float *gate, const float *w, float *const *d_feats,
+                                  float *dwc, float *colsum, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * point_sampling of the TPV / BEV encoders (model/encoder/bevformer/utils.py:114-170): project the pillar reference
  * points into every camera.
  *   ref (B, D, Q, 3) metres; lidar2img (B, N, 4, 4) row-major; focal_x / focal_y (N) or NULL (the reference's

@@ -6,7 +6,8 @@ images).  Prints one JSON line: {config: {train: {...stage ms, total}, eval: {..
 Stage times are the MEDIAN over the timed iterations, with Python's cyclic GC collected before and held off during them: a 3 ms
 eval frame whose enqueue takes 1.5 ms of host time shows a single 30 ms collection (the training modules of the same config
 were just deleted) as + 6 ms on the mean of five frames — seen twice in round 6, `host_enqueue_ms` 6 - 8 instead of 1.5 - 2.3.
-    python scripts/bench_hotpath_all.py [--only NAME[,NAME]] [--iters 5]"""
+--camera-aware builds every TPVFormerEncoder with camera_aware=True (the toggle two nuScenes configs carry as a comment).
+    python scripts/bench_hotpath_all.py [--only NAME[,NAME]] [--iters 5] [--camera-aware]"""
 import argparse
 import gc
 import json
@@ -26,10 +27,18 @@ ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--warm", type=int, default=2)
 ap.add_argument("--no-train", action="store_true")
 ap.add_argument("--no-eval", action="store_true")
+ap.add_argument("--camera-aware", action="store_true", help="TPVFormerEncoder(camera_aware=True)")
 args = ap.parse_args()
 d = torch.device("cuda:0")
 names = [n for n in hc.SHIPPED if not args.only or n in args.only.split(",")]
 res = {}
+
+
+def camera_aware(cfg):
+    enc = cfg['model']['encoder']
+    if args.camera_aware and enc['type'] == 'TPVFormerEncoder':
+        enc['camera_aware'] = True
+    return cfg
 
 
 def mean_stages(evs, keys):
@@ -45,7 +54,7 @@ for name in names:
     r = {}
     if not args.no_train:
         os.environ['eval'] = 'false'
-        cfg = hc.shipped(name)
+        cfg = camera_aware(hc.shipped(name))
         mods = hc.build(cfg, d, want_loss=True)
         for m in mods[:3]:
             m.train()
@@ -82,7 +91,7 @@ for name in names:
         torch.cuda.empty_cache()
     if not args.no_eval:
         os.environ['eval'] = 'true'
-        cfg = hc.shipped_for_eval(name)
+        cfg = camera_aware(hc.shipped_for_eval(name))
         mods = hc.build(cfg, d)
         for m in mods[:3]:
             m.eval()
@@ -119,6 +128,7 @@ for name in names:
         torch.cuda.empty_cache()
     r['built_from'] = hc.shipped(name)['source']
     res[name] = r
+res['camera_aware'] = bool(args.camera_aware)
 res['stat'] = f'median of {args.iters} iterations after {args.warm} warm-up, GC held off'
 res['max_mem_GB'] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
 print(json.dumps(res))

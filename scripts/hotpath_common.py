@@ -141,7 +141,11 @@ def frame_inputs(cfg, name, device, seed=0, want_images=True):
     novel[:, 1, 3] += 1.0
     metas = [dict(lidar2img=l2i, img2lidar=c2w, temImg2lidar=c2w, render_img2lidar=novel, img_shape=img,
                   img2prevImg=np.stack([motion(K, 2, 0.3, -0.8)] * n_cams),
-                  img2nextImg=np.stack([motion(K, -2, -0.3, 0.8)] * n_cams))]
+                  img2nextImg=np.stack([motion(K, -2, -0.3, 0.8)] * n_cams),
+                  # camera_aware=True (CameraAwareSE) reads these two; nothing else does.  c2w = pose @ inv(K) (ring_cameras), so
+                  # c2w @ K is the camera-to-ego POSE (rotation + translation in metres).  hc.build() leaves the module's
+                  # BatchNorm1d statistics at 0 / 1, under which focal lengths of ~1e3 saturate the eval-mode gate: fine for timing
+                  intrinsic=np.stack([K] * n_cams), cam2ego=np.stack([c @ K for c in c2w]))]
     g = torch.Generator(device='cpu').manual_seed(1000 + seed)
     feats = [torch.randn(1, n_cams, m['encoder']['embed_dims'], -(-img[0] // s), -(-img[1] // s), generator=g).to(device)
              for s in (8, 16, 32, 64)]

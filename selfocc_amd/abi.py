@@ -173,6 +173,10 @@ SYMBOLS = {
     "selfocc_layernorm_bwd_workspace": (C.c_size_t, [C.c_int64, _i]),
     "selfocc_layernorm_bwd": (C.c_int, [_p] * 8 + [C.c_int64, _i, _p, C.c_size_t, _p]),
     "selfocc_flatten_feats": (C.c_int, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "selfocc_camera_se_supported": (C.c_int, [_i] * 5),
+    "selfocc_camera_se_flatten_fwd": (C.c_int, [_p, _p] + [_i] * 5 + [_p] * 7),
+    "selfocc_camera_se_flatten_bwd_workspace": (C.c_size_t, [_p] + [_i] * 5),
+    "selfocc_camera_se_flatten_bwd": (C.c_int, [_p, _p, _p] + [_i] * 5 + [_p] * 6 + [C.c_size_t, _p]),
     "selfocc_point_sampling": (C.c_int, [_p] * 7 + [_i] * 4 + [C.c_float, C.c_float, _p]),
     "selfocc_linear_wgrad_supported": (C.c_int, [C.c_int64, _i, _i]),
     "selfocc_linear_wgrad_workspace": (C.c_size_t, [C.c_int64, _i, _i]),

@@ -471,10 +471,14 @@ class TPVFormerEncoder(_EncoderBase):
                  num_layers=None, camera_aware=False, camera_aware_mid_channels=None, init_cfg=None, row_shard=False):
         super().__init__(init_cfg)
         self.row_shard = row_shard          # split the plane rows over the ranks (one frame on all ranks; dist.PlaneRowShard)
-        if camera_aware:
-            raise NotImplementedError("camera_aware=True (CameraAwareSE) is off in every shipped config")
+        if camera_aware and row_shard:
+            raise NotImplementedError("camera_aware=True together with row_shard=True is not covered by a test yet (DESIGN "
+                                      "section 7): use one of the two")
         self.embed_dims, self.num_feature_levels, self.num_cams = embed_dims, num_feature_levels, num_cams
         self.camera_aware = camera_aware
+        if camera_aware:
+            from .camera_se import CameraAwareSE
+            self.camera_se_net = CameraAwareSE(embed_dims, camera_aware_mid_channels or embed_dims, embed_dims)
         self.mapping = GridMeterMapping(**mapping_args)
         H, W, Z = self.mapping.size_h, self.mapping.size_w, self.mapping.size_d
         ar = lambda n: torch.arange(n, dtype=torch.float)
@@ -574,7 +578,14 @@ class TPVFormerEncoder(_EncoderBase):
     def forward(self, representation, ms_img_feats=None, metas=None, **kwargs):
         bs = ms_img_feats[0].shape[0]
         tpv_pos, tpv_pos_cat = self._positions(bs)
-        feat, spatial_shapes, level_start_index = self._flatten_feats(ms_img_feats)
+        if self.camera_aware:
+            if self._row_sharding():           # SELFOCC_ENC_SHARD=1 reaches here without the constructor's row_shard
+                raise NotImplementedError("camera_aware=True together with row sharding is not covered by a test yet (DESIGN section 7)")
+            feat = self.camera_se_net.flatten(ms_img_feats, metas, self.cams_embeds, self.level_embeds)
+            spatial_shapes, level_start_index = _level_shapes(tuple((f.shape[3], f.shape[4]) for f in ms_img_feats),
+                                                              ms_img_feats[0].device)
+        else:
+            feat, spatial_shapes, level_start_index = self._flatten_feats(ms_img_feats)
         tpv = self.forward_layers(representation, feat, feat, tpv_pos=tpv_pos, spatial_shapes=spatial_shapes,
                                   level_start_index=level_start_index, img_metas=metas, tpv_pos_cat=tpv_pos_cat)
         return {'representation': tpv}
