@@ -201,9 +201,10 @@ typedef struct so_render_args {
     float *sdf;       /* (n_rays, n_samples)                                           */
     float *grad;      /* (n_rays, n_samples, 3)  d sdf / d (x, y, z) in metres         */
     /* --- optional workspace --------------------------------------------------------- */
-    float *sdf_brick; /* scratch of H*W*D*33 bytes (16-B aligned) or NULL.  When given, the fast
-                         path first re-packs sdf_vol so that the 8 corners of every cell are one
-                         32-B record (2 x 16-B loads per sample instead of 4 x 8-B gathers),
+    float *sdf_brick; /* scratch of H*W*D*17 bytes (16-B aligned; a larger one is fine) or NULL.  When
+                         given, the fast path first re-packs sdf_vol into one 16-B record per cell, the
+                         4 corners of its w-low face, so that the 8 corners of a cell are the records of
+                         cells (h, w, d) and (h, w + 1, d) (2 x 16-B loads per sample instead of 4 x 8-B gathers),
                          followed by one "free-space skip" byte per cell: the largest ray step for
                          which every sample inside the cell has both NeuS sigmoids saturated to
                          exactly 1.0f (alpha is then the constant 1e-5 / (1 + 1e-5) in the

@@ -543,8 +543,8 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
     const unsigned sD = (unsigned)D * 4u, sWD = (unsigned)W * D * 4u;
     const bool use_brick = a.sdf_brick != nullptr;                       // uniform
     const unsigned n_cells = (unsigned)(H * W * D);
-    // brick workspace = 32-B corner records of every cell, then one skip-code byte per cell
-    const __amdgpu_buffer_rsrc_t rb = so_make_rsrc(a.sdf_brick, use_brick ? (size_t)n_cells * 33 : 0);
+    // brick workspace = 16-B records of every cell (sdf_brickify_kernel), then one skip-code byte per cell
+    const __amdgpu_buffer_rsrc_t rb = so_make_rsrc(a.sdf_brick, use_brick ? (size_t)n_cells * 17 : 0);
     const unsigned lane_vox = (unsigned)(((lane >> 4) * W + ((lane >> 2) & 3)) * D + (lane & 3));  // block voxel of this lane
     const __amdgpu_buffer_rsrc_t rf = so_make_rsrc(a.feat_vol, NF > 0 ? (size_t)H * W * D * NF * (BF16 ? 2 : 4) : 0);
     // free-space skipping (see so_skip_unit): SDF-only launches
@@ -628,11 +628,11 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
         st.cell = so_cell_index(h0, w0, d0, W, D);     // only used when every lane is interior
         st.code = 0u;
         if (st.all_interior) {
-            if (use_brick) {   // 8 corners = one 32-B record: 2 wide loads instead of 4 gathers
-                const unsigned vo = st.cell * 32u;
-                const so_f4v lo = so_bload4(rb, vo, 0u), hi = so_bload4(rb, vo + 16u, 0u);
+            if (use_brick) {   // 8 corners = the records of cells (h, w, d) and (h, w + 1, d): 2 wide loads instead of 4 gathers
+                const unsigned vo = st.cell * 16u;
+                const so_f4v lo = so_bload4(rb, vo, 0u), hi = so_bload4(rb, vo, (unsigned)D * 16u);
                 if constexpr (CAN_SKIP) {
-                    if (use_skip) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 32u, 0);
+                    if (use_skip) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 16u, 0);
                 }
                 st.v[0] = lo.x; st.v[4] = lo.y; st.v[1] = lo.z; st.v[5] = lo.w;   // record order: see sdf_brickify_kernel
                 st.v[2] = hi.x; st.v[6] = hi.y; st.v[3] = hi.z; st.v[7] = hi.w;
@@ -830,7 +830,7 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
 // ---------------------------------------------------------------------------------------
 // SDF-only per-ray launches with free-space skipping (the depth-evaluation path, bench.py).
 // PMC of the general march on this workload: the vector-L1 path is the limiter (TA address FIFO full, waves
-// parked in s_waitcnt), not the vector ALU — and a skipped step still fetched its 32-byte corner record,
+// parked in s_waitcnt), not the vector ALU — and a skipped step still fetched its corner records,
 // because the skip code arrived together with it.  Here the skip code runs ONE step ahead of the records:
 //     per step i:  decide skip(i) from code(i) (already here)
 //                  position of step i + 1, issue its 1-byte code load
@@ -838,7 +838,21 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
 //                  composite
 // A skipped step moves 1 byte per lane through the L1 instead of 33.  Nothing is software-pipelined beyond
 // that: measurements showed the march insensitive to load/compute overlap inside a wave (8 waves / SIMD hide it).
+//
+// Free-space steps come in long runs (mean 33 steps at inv_s 20), and inside a run three tests of the general
+// step have a known outcome, so a run loop (`run` below) composites the steps after a skipped one without them:
+//   * the interior test: a lane's grid coordinate is monotone in the step index on every axis, so a wave that is interior
+//     at steps lo and hi is interior at every step between; [i_lo, i_hi] is found once per wave with the test itself;
+//   * the best-weight compare: T does not grow inside a run, so w = kAlphaFree * T does not exceed the run's first w;
+//   * the exit test: see kRunExitFreeSteps.
+// What a lane computes at a step, and every wave-wide decision, is what the step-by-step form computes: same outputs, bit for bit.
 // ---------------------------------------------------------------------------------------
+// A run of n free steps multiplies T by ((1 - kAlphaFree) + 1e-7f) n times, each product rounded: by more than
+// (1 - 1e-5)^n, which is > 0.54 for n <= 60 000.  A lane that enters a run of at most that many steps with T >= 2e-10
+// therefore stays above 1e-10 to its end, and the wave-wide exit test `all lanes T < 1e-10` is false throughout.
+constexpr int kRunExitFreeSteps = 60000;
+constexpr int kSureScan = 8;   // steps tried from either end of the march for the sure-interior range
+
 struct AheadStep {
     float gh, gw, gd, fi;         // grid coordinates (the fractions are taken only by the steps that interpolate)
     int h0, w0, d0;
@@ -865,7 +879,7 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
     const float hdt = 0.5f * dt, hdt_s2 = hdt * s2;
     const float *__restrict__ vol = a.sdf_vol;
     const unsigned n_cells = (unsigned)(H * W * D);
-    const __amdgpu_buffer_rsrc_t rb = so_make_rsrc(a.sdf_brick, (size_t)n_cells * 33);
+    const __amdgpu_buffer_rsrc_t rb = so_make_rsrc(a.sdf_brick, (size_t)n_cells * 17);   // 16-B records, then the code bytes
     const __amdgpu_buffer_rsrc_t rs = so_make_rsrc(vol, (size_t)n_cells * 4);
     const int rcode = max((int)ceilf(dt / so_skip_unit(a.aabb, S)), 1);
     const int maxdim = max(H, max(W, D));
@@ -873,18 +887,49 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
 
     float T = 1.0f, acc = 0.0f, dsum = 0.0f, best_w = -1.0f, best_t = 0.0f;
 
-    auto locate = [&](const int i, AheadStep &st) __attribute__((always_inline)) {
+    // position and cell of step i
+    auto place = [&](const int i, AheadStep &st) __attribute__((always_inline)) {
         st.fi = (float)i;
         const float step = st.fi * dt;
         const float gh = fmaf(Gdh, step, G0h), gw = fmaf(Gdw, step, G0w), gd = fmaf(Gdd, step, G0d);
         st.gh = gh; st.gw = gw; st.gd = gd;
         const int h0 = so_floor_i(gh), w0 = so_floor_i(gw), d0 = so_floor_i(gd);
         st.h0 = h0; st.w0 = w0; st.d0 = d0;
-        st.all_interior = so_all3((unsigned)h0 < (unsigned)(H - 1), (unsigned)w0 < (unsigned)(W - 1),
-                                  (unsigned)d0 < (unsigned)(D - 1));
         st.cell = so_cell_index(h0, w0, d0, W, D);
+    };
+    auto interior = [&](const AheadStep &st) __attribute__((always_inline)) {   // wave-uniform
+        return so_all3((unsigned)st.h0 < (unsigned)(H - 1), (unsigned)st.w0 < (unsigned)(W - 1), (unsigned)st.d0 < (unsigned)(D - 1));
+    };
+    // The steps [i_lo, i_hi] at which every lane of the wave is certainly interior: `interior` holds at both ends, hence
+    // (monotone coordinates: fi * dt, the fma and the floor are each monotone in i) in between.  The ends are looked for
+    // within kSureScan steps of the march's ends; a wave that has none there (rays that graze the volume) gets the empty
+    // range and tests every step.
+    int i_lo = S, i_hi = -1;
+    {
+        AheadStep p;
+        const int n = min(kSureScan, S);
+#pragma nounroll
+        for (int k = 0; k < n; ++k) {
+            place(k, p);
+            if (interior(p)) { i_lo = k; break; }
+        }
+        if (i_lo < S) {
+#pragma nounroll
+            for (int k = S - 1; k >= S - n && k >= i_lo; --k) {
+                place(k, p);
+                if (interior(p)) { i_hi = k; break; }
+            }
+        }
+        if (i_hi < 0) i_lo = S;
+    }
+    auto sure = [&](const int i) __attribute__((always_inline)) { return i >= i_lo && i <= i_hi; };
+
+    auto locate = [&](const int i, AheadStep &st) __attribute__((always_inline)) {
+        place(i, st);
+        st.all_interior = true;
+        if (!sure(i)) st.all_interior = interior(st);
         st.code = 0u;
-        if (st.all_interior) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 32u, 0);
+        if (st.all_interior) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 16u, 0);
     };
     auto near_face = [&](float fh, float fw, float fd) __attribute__((always_inline)) {
         return fmaxf(fmaxf(fabsf(fh - 0.5f), fabsf(fw - 0.5f)), fabsf(fd - 0.5f)) > 0.5f - face_m;
@@ -922,6 +967,7 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
         return so_cell_of(gh, gw, gd);
     };
 
+    // returns whether the step skipped (wave-uniform)
     auto step = [&](const int i, AheadStep &cur, AheadStep &nxt) __attribute__((always_inline)) {
         const bool skip = cur.all_interior && so_all((int)cur.code >= rcode);
         if (i + 1 < S) locate(i + 1, nxt);
@@ -958,9 +1004,10 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
             }
             if (!loaded) {
                 if (cur.all_interior) {
-                    {   // one 32-B record = the four corner pairs, in the register order so_trilerp_fast_pk takes them
+                    {   // the records of cells (h, w, d) and (h, w + 1, d) = the four corner pairs, in the register order
+                        // so_trilerp_fast_pk takes them
                         // (issuing these loads before locate() above, to run it under them, measured 9 % SLOWER)
-                        const so_f4v lo = so_bload4(rb, cur.cell * 32u, 0u), hi = so_bload4(rb, cur.cell * 32u + 16u, 0u);
+                        const so_f4v lo = so_bload4(rb, cur.cell * 16u, 0u), hi = so_bload4(rb, cur.cell * 16u, (unsigned)D * 16u);
                         p0 = lo.xy; p1 = lo.zw; p2 = hi.xy; p3 = hi.zw;
                     }
                 } else {
@@ -978,18 +1025,49 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
         acc = acc + w;
         dsum = fmaf(w, t_mid, dsum);
         if (w > best_w) { best_w = w; best_t = t_mid; }
+        return skip;
+    };
+
+    // The run loop.  On entry step i - 1 skipped and passed the exit test, and `st` holds step i, located.  It composites
+    // steps i, i + 1, ... while they skip and the step after them is inside the sure range (so that `st`, re-located in
+    // place after each decision, needs no interior test), then hands `st` = the located step i back to the general step.
+    // Returns true when the march is over.
+    auto run = [&](int &i, AheadStep &st) __attribute__((always_inline)) {
+        if (i < i_lo || i >= i_hi) return false;
+        auto free_step = [&]() __attribute__((always_inline)) {
+            const float t_mid = fmaf(st.fi, dt, tnear + hdt);
+            ++i;
+            place(i, st);
+            st.all_interior = true;
+            st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 16u, 0);
+            const float w = kAlphaFree * T;
+            T = T * ((1.0f - kAlphaFree) + 1e-7f);
+            acc = acc + w;
+            dsum = fmaf(w, t_mid, dsum);
+        };
+        if (S <= kRunExitFreeSteps && !so_all(T < 2e-10f)) {   // some lane keeps the wave's exit test false: kRunExitFreeSteps
+            while (i < i_hi && so_all((int)st.code >= rcode)) free_step();
+        } else {
+            while (i < i_hi && so_all((int)st.code >= rcode)) {
+                free_step();
+                if (so_all(T < 1e-10f)) return true;
+            }
+        }
+        return false;
     };
 
     {
         AheadStep A, B;
         locate(0, A);
         for (int i = 0;;) {
-            step(i, A, B);
+            const bool sa = step(i, A, B);
             if (++i >= S) break;
             if (so_all(T < 1e-10f)) break;
-            step(i, B, A);
+            if (sa && run(i, B)) break;
+            const bool sb = step(i, B, A);
             if (++i >= S) break;
             if (so_all(T < 1e-10f)) break;
+            if (sb && run(i, A)) break;
         }
     }
 
@@ -1035,42 +1113,59 @@ SO_DEVFN void so_march(const so_render_args &a, int ray, GeomFn geom) {
 }
 
 
-// re-pack of the SDF volume for the fast path: brick[cell] = the 8 corners of cell (h, w, d) as the four pairs
-// (v[k], v[k + 4]), k = 0..3 (k = 2 w + d, so_gather_sdf's numbering), clamped at the upper faces (only interior cells are ever read); codes[cell] = the
-// free-space skip code of the cell (see so_skip_unit), 0 when skipping is off
+// re-pack of the SDF volume for the fast path.  record[cell(h, w, d)] = (v[h][w][d], v[h + 1][w][d], v[h][w][d + 1], v[h + 1][w][d + 1]),
+// 16 bytes: the (h = 0, h = 1) corner pairs of so_trilerp_fast_pk at w = 0.  The pairs at w = 1 are the record of cell
+// (h, w + 1, d), D records further on, so a cell's 8 corners are two 16-B loads and no corner is stored twice along w.
+// Indices are clamped at the upper faces (only interior cells are ever read).  After the records, codes[cell] = the
+// free-space skip code of the cell (see so_skip_unit), 0 when skipping is off.
+// A thread owns a cell: threadIdx.x = d, threadIdx.y = w within the block's columns, blockIdx.x = h, so no index is divided
+// and a wave stores 64 consecutive records.  (A thread per 4 d-cells with float4 row loads measured slower, 13.2 us against
+// the 10.9 us of the 32-byte pass: its record stores were 64 bytes apart from lane to lane.)  With D % 4 == 0 (uniform) the
+// 4 code bytes of an aligned quad of lanes leave as one dword.
 __global__ __launch_bounds__(256) void sdf_brickify_kernel(const float *__restrict__ vol, float *__restrict__ brick,
                                                            int H, int W, int D, so_render_args a, int with_codes) {
-    const int cell = blockIdx.x * blockDim.x + threadIdx.x;
-    if (cell >= H * W * D) return;
-    const int d = cell % D, w = (cell / D) % W, h = cell / (D * W);
-    const int h1 = min(h + 1, H - 1), w1 = min(w + 1, W - 1), d1 = min(d + 1, D - 1);
-    const float *r00 = vol + ((size_t)h * W + w) * D, *r01 = vol + ((size_t)h * W + w1) * D;
-    const float *r10 = vol + ((size_t)h1 * W + w) * D, *r11 = vol + ((size_t)h1 * W + w1) * D;
-    const float v0 = r00[d], v1 = r00[d1], v2 = r01[d], v3 = r01[d1];
-    const float v4 = r10[d], v5 = r10[d1], v6 = r11[d], v7 = r11[d1];
-    float4 *o = (float4 *)(brick + (size_t)cell * 8);
-    o[0] = make_float4(v0, v4, v1, v5);   // the (h = 0, h = 1) corner pairs of so_trilerp_fast_pk, d then w fastest
-    o[1] = make_float4(v2, v6, v3, v7);
-    uint8_t *codes = (uint8_t *)(brick + (size_t)H * W * D * 8);
-    unsigned code = 0u;
-    if (with_codes) {
-        const float m = fminf(fminf(fminf(v0, v1), fminf(v2, v3)), fminf(fminf(v4, v5), fminf(v6, v7)));
-        // per-axis bound of the metre gradient anywhere in the cell: the partial derivative of a trilinear
-        // function is a bilinear blend of the 4 edge differences along that axis
-        const float gd = fmaxf(fmaxf(fabsf(v1 - v0), fabsf(v3 - v2)), fmaxf(fabsf(v5 - v4), fabsf(v7 - v6))) *
-                         (a.map.d.size0 / a.map.d.range0);
-        const float gw = fmaxf(fmaxf(fabsf(v2 - v0), fabsf(v3 - v1)), fmaxf(fabsf(v6 - v4), fabsf(v7 - v5))) *
-                         (a.map.w.size0 / a.map.w.range0);
-        const float gh = fmaxf(fmaxf(fabsf(v4 - v0), fabsf(v5 - v1)), fmaxf(fabsf(v6 - v2), fabsf(v7 - v3))) *
-                         (a.map.h.size0 / a.map.h.range0);
-        const float G = sqrtf((gd * gd + gw * gw) + gh * gh) * 1.001f + 1e-20f;
-        const float slack = m - kSkipArg / so_inv_s(a);                       // metres above the saturation level
-        if (slack > 0.0f && so_inv_s(a) > 0.0f) {
-            const float allow = 2.0f * slack / G / so_skip_unit(a.aabb, a.n_samples);   // in code units
-            code = (unsigned)fminf(floorf(allow * 0.999f), 255.0f);
+    const int h = blockIdx.x, h1 = min(h + 1, H - 1);
+    const size_t n_cells = (size_t)H * W * D;
+    uint8_t *codes = (uint8_t *)(brick + n_cells * 4);
+    // blockDim.x is a power of two: with D % 4 == 0 the lanes 4 q .. 4 q + 3 of a wave hold 4 consecutive cells of one column
+    const bool quads = (D & 3) == 0 && (blockDim.x & 3) == 0;
+    const float kd = a.map.d.size0 / a.map.d.range0, kw = a.map.w.size0 / a.map.w.range0, kh = a.map.h.size0 / a.map.h.range0;
+    for (int w = blockIdx.y * blockDim.y + threadIdx.y; w < W; w += gridDim.y * blockDim.y) {
+        const int w1 = min(w + 1, W - 1);
+        const float *r00 = vol + ((size_t)h * W + w) * D, *r01 = vol + ((size_t)h * W + w1) * D;
+        const float *r10 = vol + ((size_t)h1 * W + w) * D, *r11 = vol + ((size_t)h1 * W + w1) * D;
+        for (int d = threadIdx.x; d < D; d += blockDim.x) {
+            const int d1 = min(d + 1, D - 1);
+            const float v0 = r00[d], v1 = r00[d1], v2 = r01[d], v3 = r01[d1];
+            const float v4 = r10[d], v5 = r10[d1], v6 = r11[d], v7 = r11[d1];
+            const size_t cell = ((size_t)h * W + w) * D + d;
+            ((float4 *)brick)[cell] = make_float4(v0, v4, v1, v5);
+            unsigned code = 0u;
+            if (with_codes) {
+                const float m = fminf(fminf(fminf(v0, v1), fminf(v2, v3)), fminf(fminf(v4, v5), fminf(v6, v7)));
+                // per-axis bound of the metre gradient anywhere in the cell: the partial derivative of a trilinear
+                // function is a bilinear blend of the 4 edge differences along that axis
+                const float gd = fmaxf(fmaxf(fabsf(v1 - v0), fabsf(v3 - v2)), fmaxf(fabsf(v5 - v4), fabsf(v7 - v6))) * kd;
+                const float gw = fmaxf(fmaxf(fabsf(v2 - v0), fabsf(v3 - v1)), fmaxf(fabsf(v6 - v4), fabsf(v7 - v5))) * kw;
+                const float gh = fmaxf(fmaxf(fabsf(v4 - v0), fabsf(v5 - v1)), fmaxf(fabsf(v6 - v2), fabsf(v7 - v3))) * kh;
+                const float G = sqrtf((gd * gd + gw * gw) + gh * gh) * 1.001f + 1e-20f;
+                const float slack = m - kSkipArg / so_inv_s(a);                       // metres above the saturation level
+                if (slack > 0.0f && so_inv_s(a) > 0.0f) {
+                    const float allow = 2.0f * slack / G / so_skip_unit(a.aabb, a.n_samples);   // in code units
+                    code = (unsigned)fminf(floorf(allow * 0.999f), 255.0f);
+                }
+            }
+            if (quads) {
+                // the codes of the lane's quad (quad_perm broadcasts of its lanes 1, 2, 3), stored by its lane 0
+                const unsigned c1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)code, 0x55, 0xf, 0xf, false);
+                const unsigned c2 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)code, 0xaa, 0xf, 0xf, false);
+                const unsigned c3 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)code, 0xff, 0xf, 0xf, false);
+                if ((d & 3) == 0) *(unsigned *)(codes + cell) = code | (c1 << 8) | (c2 << 16) | (c3 << 24);
+            } else {
+                codes[cell] = (uint8_t)code;
+            }
         }
     }
-    codes[cell] = (uint8_t)code;
 }
 
 // pixel-grid rays: a block is a 16x16 pixel tile of one camera, each of its four waves an 8x8 sub-tile
@@ -1170,10 +1265,14 @@ int dispatch_ps(const so_render_args &a, hipStream_t st) {
                 (long long)a.map.h.tot_len * a.map.w.tot_len < (1 << 24) && a.map.d.tot_len < (1 << 24);   // so_cell_index
     if (fast) {
         if (a.sdf_brick) {
-            const int cells = a.map.h.tot_len * a.map.w.tot_len * a.map.d.tot_len;
             const int with_codes = (NF == 0 && !(a.flags & SO_FLAG_NO_SKIP)) ? 1 : 0;
-            hipLaunchKernelGGL(sdf_brickify_kernel, dim3((cells + 255) / 256), dim3(256), 0, st, a.sdf_vol, a.sdf_brick,
-                               a.map.h.tot_len, a.map.w.tot_len, a.map.d.tot_len, a, with_codes);
+            // threadIdx.x = d (a power of two of them), threadIdx.y = w; blockIdx.x = h
+            const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
+            int qx = 1;
+            while (qx < D && qx < 256) qx *= 2;
+            const int wy = 256 / qx;
+            hipLaunchKernelGGL(sdf_brickify_kernel, dim3(H, min((W + wy - 1) / wy, 65535)), dim3(qx, wy), 0, st, a.sdf_vol, a.sdf_brick,
+                               H, W, D, a, with_codes);
         }
         if constexpr (NF == 0) {
             if (a.sdf_brick && !(a.flags & (SO_FLAG_NO_SKIP | SO_FLAG_NO_AHEAD)))

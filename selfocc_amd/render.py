@@ -135,7 +135,7 @@ class RenderConfig:
     depth_div_norm: bool = True
     clamp_rgb: bool = False
     exact: bool = False               # canonical IEEE op order (bit-exact with the oracle), slower
-    brick: bool = True                # fast path: re-pack the SDF volume into 8-corner records per launch
+    brick: bool = True                # fast path: re-pack the SDF volume into 16-byte corner records per launch
     skip: bool = True                 # fast path + brick: composite saturated free-space samples without interpolating
     face_safe: bool = True            # fast path: canonical cell selection within a few ulp of a voxel face (~6 % slower)
     ahead: bool = True                # SDF-only per-ray launches with brick + skip: code-ahead skip marcher (A/B)
@@ -251,14 +251,14 @@ _BRICK_WS = {}
 
 
 def _brick_workspace(sdf):
-    """Per (device, stream, shape) scratch for the 8-corner records of the SDF volume ([H][W][D][8] f32) followed
+    """Per (device, stream, shape) scratch for the 16-byte corner records of the SDF volume ([H][W][D][4] f32) followed
     by one skip-code byte per cell; rewritten by every launch on the launch stream, so it is never stale and two
     streams never share one."""
     key = (sdf.device, torch.cuda.current_stream(sdf.device).cuda_stream, tuple(sdf.shape))
     ws = _BRICK_WS.get(key)
     if ws is None:
         n = sdf.numel()
-        ws = _BRICK_WS[key] = torch.empty((n * 33 + 15) // 16 * 16, dtype=torch.uint8, device=sdf.device)
+        ws = _BRICK_WS[key] = torch.empty((n * 17 + 15) // 16 * 16, dtype=torch.uint8, device=sdf.device)
     return ws
 
 
