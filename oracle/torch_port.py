@@ -313,14 +313,19 @@ def render_port_differentiable(mapping, vol_chw, n_rgb, n_sem, o, d, dn, cfg, in
 # The full loss (incl. SSIM / auto-mask) is pinned against the imported reference class via
 # tests/golden; this function is the oracle of the fused kernel's three outputs.
 # ---------------------------------------------------------------------------------------
+EPS32 = 1.1920929e-07        # torch.finfo(torch.float32).eps, the reference's clamp at its own (float32) precision
+
+
 def reproj_sample_port(weights, ts, deltas, pix, curr_rgb, T_prev, T_next, img_prev, img_next, img_h, img_w):
+    """float32 inputs: the reference's arithmetic.  float64 inputs: the same function (the two eps clamps stay at
+    float32's, not float64's finfo), the high-precision reference of the kernel tests."""
     R, S = weights.shape
     ray_idx = torch.arange(R).unsqueeze(-1).repeat(1, S).flatten()
     weight, t = weights.flatten(), ts.flatten()
     rays = pix[ray_idx]
     if deltas is not None:
         delta = deltas.flatten().detach()
-        eps = torch.finfo(delta.dtype).eps
+        eps = EPS32
         weight = weight.clone()
         weight[delta < eps] = 0.
         weight = weight / delta.clamp_min(eps)
@@ -361,7 +366,7 @@ def reproj_sample_port(weights, ts, deltas, pix, curr_rgb, T_prev, T_next, img_p
     weight[~general_mask.flatten()] = 0.
     weight_sum = torch.zeros(R, dtype=weight.dtype)
     weight_sum.index_add_(-1, ray_idx, weight)
-    weight_sum = weight_sum.clamp_min(torch.finfo(torch.float32).eps)
+    weight_sum = weight_sum.clamp_min(EPS32)
     weight = weight / torch.gather(weight_sum, -1, ray_idx)
     l1 = torch.zeros(R, dtype=diff.dtype)
     l1 = l1.index_add(-1, ray_idx, weight * diff.flatten())

@@ -5,11 +5,15 @@ import math
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 import oracle
 from oracle import torch_port as tp
 from selfocc_amd import synthetic as sy
+from selfocc_amd._lib import SelfOccHipError
+from selfocc_amd.mapping import GridMeterMapping
 from selfocc_amd.occ import field_query, uniform_lattice, occ_resample, MeanIoU, OPENSEED2NUSCENES
+from selfocc_amd.render import SDFVolume
 
 pytestmark = pytest.mark.gpu
 D0 = torch.device("cuda:0")
@@ -93,3 +97,141 @@ def test_iou_counts_binary_and_empty(hip):
     t = torch.tensor([1, 0, 0, 1, 1], dtype=torch.int32, device=D0)
     m._after_step(p, t)
     assert m.counts.cpu().tolist() == [[3, 3], [2, 2], [3, 3]]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The class lookup (so_team_lookup: 8 lanes per point, lane j owns channels j, j + 8, ...) on inputs where float32
+# arithmetic is exact — integer values on a small grid, coordinates on a dyadic lattice — so that tied maxima survive the
+# interpolation and the first-maximum rule across lanes and rounds decides the result; channel counts below, at and
+# above the team width, so that lanes without a channel exist.
+# ---------------------------------------------------------------------------------------------------------------------
+CHANNELS = [1, 2, 7, 8, 9, 17, 32]
+GRID = (5, 9, 3)
+
+
+def _first_max(v):
+    """index of the first maximum along the last axis, without relying on argmax's tie rule"""
+    idx = torch.arange(v.shape[-1]).expand_as(v)
+    return torch.where(v == v.max(dim=-1, keepdim=True).values, idx, torch.full_like(idx, v.shape[-1])).min(dim=-1).values
+
+
+_EXACT = {}
+
+
+def _exact_resample_case(C):
+    """(grid, logits, coords, sampled, sampled logits, first-maximum class): integers in [-2, 2] on a 5 x 9 x 3 grid, every
+    multiple of 1 / 16 from -4 / 16 to 20 / 16 per axis (15 625 points = 488 x 32 + 9, some in the zero padding).
+    Plain torch on the CPU, computed once per C; float32 grid_sample equals float64 bit for bit on these inputs."""
+    if C not in _EXACT:
+        g = torch.Generator().manual_seed(100 + C)
+        grid = torch.randint(-2, 3, GRID, generator=g).float()
+        logits = torch.randint(-2, 3, GRID + (C,), generator=g).float()
+        ax = torch.arange(-4, 21, dtype=torch.float32) / 16
+        coords = torch.stack(torch.meshgrid(ax, ax, ax, indexing='ij'), dim=-1).contiguous()       # along (H, W, D)
+        gs = (coords[..., [2, 1, 0]] * 2 - 1)[None]
+        sampled = F.grid_sample(grid[None, None], gs, mode='bilinear', align_corners=True)[0, 0]
+        sl = F.grid_sample(logits.permute(3, 0, 1, 2)[None], gs, mode='bilinear', align_corners=True)[0]
+        for a32, src in ((sampled, grid[None, None]), (sl, logits.permute(3, 0, 1, 2)[None])):
+            a64 = F.grid_sample(src.double(), gs.double(), mode='bilinear', align_corners=True)
+            assert torch.equal(a32.double().reshape(-1), a64.reshape(-1))
+        sl = sl.permute(1, 2, 3, 0).contiguous()
+        cls = _first_max(sl)
+        assert torch.equal(torch.argmax(sl, dim=-1), cls)          # torch.argmax returns the first maximum too
+        _EXACT[C] = (grid, logits, coords, sampled, sl, cls)
+    return _EXACT[C]
+
+
+def test_exact_cases_have_ties():
+    """the inputs do what they are for: at C = 17 a large share of the points has a tied maximum, away from the padding too"""
+    _, _, coords, _, sl, _ = _exact_resample_case(17)
+    tied = ((sl == sl.max(dim=-1, keepdim=True).values).sum(dim=-1) > 1)
+    inside = ((coords > 0) & (coords < 1)).all(dim=-1)
+    padded_out = (sl == 0).all(dim=-1)                      # every corner in the zero padding: a tie of another kind
+    assert tied.float().mean() > 0.3 and (tied & ~padded_out).float().mean() > 0.15 and tied[inside].float().mean() > 0.1
+    assert (~inside).any() and padded_out.any()
+
+
+CROPS = [(0, 0, 0, 0, 0, 0), (1, 2, 3, 0, 0, 4), (13, 12, 0, 0, 0, 0)]      # the last one empties the first axis
+
+
+@pytest.mark.parametrize("permute_lut", [False, True], ids=["identity_lut", "permuted_lut"])
+@pytest.mark.parametrize("C", CHANNELS)
+def test_occ_resample_exact_ties_and_thresholds(hip, C, permute_lut):
+    grid, logits, coords, sampled, sl, cls = _exact_resample_case(C)
+    lut = torch.randperm(C, generator=torch.Generator().manual_seed(C)).tolist() if permute_lut else list(range(C))
+    thresh = 0.5
+    assert (sampled == thresh).any() and (sampled < thresh).any() and (sampled > thresh).any()
+    n = coords.shape[0]
+    gd, cd, ld = grid.to(D0), coords.to(D0), logits.to(D0)
+    for density in (False, True):
+        for crop in CROPS:
+            occ = ((sampled >= thresh) if density else (sampled <= thresh)).to(torch.int32)
+            occ[:crop[0]] = 0
+            occ[n - crop[1]:] = 0
+            occ[:, :crop[2]] = 0
+            occ[:, n - crop[3]:] = 0
+            occ[:, :, :crop[4]] = 0
+            occ[:, :, n - crop[5]:] = 0
+            sem = occ * torch.tensor(lut, dtype=torch.int32)[cls]
+            got = occ_resample(gd, cd, thresh, logits=ld, lut=lut, crop=crop, density=density, want_sampled=True)
+            assert torch.equal(got['sampled'].cpu(), sampled), (density, crop)
+            assert torch.equal(got['occ'].cpu(), occ), (density, crop)
+            assert torch.equal(got['sem'].cpu(), sem), (density, crop)
+            assert (occ.sum() == 0) == (crop == CROPS[2])
+
+
+def test_occ_resample_too_many_classes_raises(hip):
+    grid, _, coords, _, _, _ = _exact_resample_case(1)
+    logits = torch.zeros(GRID + (33,))
+    with pytest.raises(SelfOccHipError, match="33"):
+        occ_resample(grid.to(D0), coords.to(D0), 0.5, logits=logits.to(D0), lut=list(range(33)))
+
+
+def _exact_volume(n_rgb, n_sem, feat_dtype, seed):
+    """5 x 9 x 3 voxels over 8 m x 16 m x 4 m (a voxel is 2 m), integer SDF and logits; the colour channels and three pad
+    channels past n_rgb + n_sem hold 64, which would win every arg-max if a lane read them"""
+    mapping = GridMeterMapping(nonlinear_mode='linear', h_size=[4, 0], h_range=[8.0, 0], h_half=True, w_size=[8, 0],
+                               w_range=[16.0, 0], w_half=True, d_size=[2, 0], d_range=[0.0, 4.0, 4.0])
+    assert (mapping.size_h, mapping.size_w, mapping.size_d) == GRID
+    g = torch.Generator().manual_seed(seed)
+    sdf = torch.randint(-2, 3, GRID, generator=g).float()
+    feat = torch.full(GRID + (n_rgb + n_sem + 3,), 64.0)
+    feat[..., n_rgb:n_rgb + n_sem] = torch.randint(-2, 3, GRID + (n_sem,), generator=g).float()
+    return SDFVolume(mapping, sdf, feat.to(feat_dtype), n_rgb, n_sem)
+
+
+def _exact_lattice():
+    """metres whose grid coordinates are multiples of 1 / 4 (h, d) and 1 / 2 (w): voxel centres, cell midpoints, and a
+    margin outside the volume; 21 x 19 x 11 = 4 389 points = 137 x 32 + 5"""
+    ys = torch.arange(-2, 19, dtype=torch.float32) * 0.5
+    xs = torch.arange(-1, 18, dtype=torch.float32)
+    zs = torch.arange(-1, 10, dtype=torch.float32) * 0.5
+    return torch.stack(torch.meshgrid(xs, ys, zs, indexing='ij'), dim=-1).reshape(-1, 3).contiguous()
+
+
+@pytest.mark.parametrize("feat_dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("n_rgb", [0, 3])
+@pytest.mark.parametrize("n_sem", CHANNELS)
+def test_field_query_exact_ties(hip, n_sem, n_rgb, feat_dtype):
+    vol = _exact_volume(n_rgb, n_sem, feat_dtype, seed=10 * n_sem + n_rgb)
+    assert vol.feat.shape[3] > n_rgb + n_sem
+    xyz = _exact_lattice()
+    h = tp.field_lookup(vol.mapping, vol.to_reference_layout(), xyz)
+    h64 = tp.field_lookup(vol.mapping, vol.to_reference_layout().double(), xyz.double())
+    assert torch.equal(h.double(), h64)                             # the reference itself is exact on these inputs
+    ref_logits = h[:, 1 + n_rgb:]
+    assert ref_logits.shape[1] == n_sem and ref_logits.abs().max() <= 2
+    cls = _first_max(ref_logits)
+    assert torch.equal(torch.argmax(ref_logits, dim=-1), cls)
+    if n_sem >= 7:
+        assert ((ref_logits == ref_logits.max(dim=-1, keepdim=True).values).sum(dim=-1) > 1).float().mean() > 0.15
+    got = field_query(vol.to(D0), xyz.to(D0), want_sdf=True, want_logits=True, want_argmax=True)
+    assert torch.equal(got['sdf'].cpu(), h[:, 0])
+    assert torch.equal(got['logits'].cpu(), ref_logits)
+    assert torch.equal(got['argmax'].cpu().long(), cls)
+
+
+def test_field_query_too_many_classes_raises(hip):
+    vol = _exact_volume(0, 33, torch.float32, seed=0)
+    with pytest.raises(SelfOccHipError, match="33"):
+        field_query(vol.to(D0), _exact_lattice().to(D0), want_logits=True, want_argmax=True)
