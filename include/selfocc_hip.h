@@ -154,6 +154,18 @@ enum { SO_SH_RELU = 0, SO_SH_SIGMOID = 1 };
  * The two fields sit at the END of so_render_args, after everything a caller of the earlier layout fills, and
  * SELFOCC_ABI_VERSION is unchanged: a caller that zero-initialises the struct gets the behaviour it always got. */
 
+/* Semantic classes (so_render_args::n_sem, with sh_deg == 0, sh_act == SO_SH_RELU, n_rgb == 3).  Built: n_sem = 0 and every
+ * n_sem from 2 to 21.  A voxel row is [r, g, b, logit_0 .. logit_{n_sem - 1}, pad] and feat_stride MUST be 3 + n_sem rounded
+ * up to a multiple of 4: 8 (2 - 5 classes), 12 (6 - 9), 16 (10 - 13), 20 (14 - 17) or 24 (18 - 21).  The up to three pad
+ * channels may hold anything: they are never read into a result, and a backward never writes their gradient (it stays what
+ * the caller put there: zero).  sem and g_sem are (n_rays, n_sem), without a pad.  5 and 21 classes (rows without a pad) run
+ * the kernels they always ran; the other class counts run the render_ns_* kernels of the row width, which compare the last
+ * three channels with n_sem.  Those march face-safe: SO_FLAG_NO_FACE_SAFE is ignored for them.
+ * Refused on the host, by name in selfocc_last_error(): n_sem == 1 (one class renders `acc`), n_sem >= 22 (the binned backward
+ * record and the 32-lanes-per-sample brick kernel end at 24 channels), any other feat_stride, a bfloat16 feat_vol at a class
+ * count other than 21, and n_sem > 0 together with sh_deg > 0 or SO_SH_SIGMOID.  No field is added and SELFOCC_ABI_VERSION is
+ * unchanged. */
+
 typedef struct so_render_args {
     /* --- field ------------------------------------------------------------------- */
     so_mapping map;

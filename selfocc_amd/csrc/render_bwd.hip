@@ -75,7 +75,7 @@ SO_DEVFN int rb_shard(long long sample) { return (int)(sample >> 8) & (kShards -
 template <int NF, int NB = 0>
 struct RbRec {
     static constexpr int NCH = NB > 0 ? 3 * NB : (NF == 4 ? 3 : NF);                 // feature channels with a gradient
-    static constexpr int RECF = NB > 0 ? 16 : (NF >= 20 ? 32 : (NF >= 4 ? 16 : 8));  // floats per record
+    static constexpr int RECF = NB > 0 ? 16 : (NF >= 12 ? 32 : (NF >= 4 ? 16 : 8));  // floats per record (>= NF + 8)
     static constexpr int LPG = NB > 0 ? 32 : RECF;                                    // lanes per sample in rb_brick_kernel
     static constexpr int RW = NCH + 1;                                                // tile row: features then the sdf column
 };
@@ -138,12 +138,24 @@ SO_DEVFN int rb_run(int key, int lane, int &head_lane) {
 template <int NF, bool BF16, int M, int WPR, bool BIN, int MK = SO_MAP_LINEAR>
 __global__ __launch_bounds__(256) void render_bwd_kernel(so_render_bwd_args ba, RbBin bin) {
     constexpr int NB = NF < 0 ? 1 : 0;   // no spherical harmonics (spelled value-dependent: the NB > 0 branches are never instantiated)
+    constexpr bool MASKED = false;
 #include "render_bwd_body.h"
 }
 template <int NB, int M, int WPR, bool BIN, int MK>
 __global__ __launch_bounds__(256) void render_bwd_sh_kernel(so_render_bwd_args ba, RbBin bin) {
     constexpr int NF = so_sh_stride(NB);
     constexpr bool BF16 = false;
+    constexpr bool MASKED = false;
+#include "render_bwd_body.h"
+}
+// any class count from 2 to 21: float32 rows of NF = 8, 12, 16, 20, 24 floats with a.n_sem in [NF - 6, NF - 3] logits
+// and up to three pad channels.  The binned scatter shares rb_brick_kernel<NF> with the unmasked widths: a pad channel's
+// record entry is an exact 0, which the brick kernel does not add.
+template <int NF, int M, int WPR, bool BIN, int MK>
+__global__ __launch_bounds__(256) void render_ns_bwd_kernel(so_render_bwd_args ba, RbBin bin) {
+    constexpr int NB = NF < 0 ? 1 : 0;
+    constexpr bool BF16 = false;
+    constexpr bool MASKED = true;
 #include "render_bwd_body.h"
 }
 
@@ -338,7 +350,7 @@ inline bool rb_in_range(const so_render_args &a) {
            (size_t)a.n_rays * a.n_samples < ((size_t)1 << 31);
 }
 
-template <int NF, bool BF16, bool BIN, int MK, int NB = 0>
+template <int NF, bool BF16, bool BIN, int MK, int NB = 0, bool MASKED = false>
 int launch_ray(const so_render_bwd_args &ba, const RbBin &bin, hipStream_t st) {
     const int S = ba.fwd.n_samples;
     const int m = (S + 63) / 64;
@@ -346,7 +358,8 @@ int launch_ray(const so_render_bwd_args &ba, const RbBin &bin, hipStream_t st) {
         const int blocks = ba.fwd.n_rays;
 #define SO_L(MM)                                                                                                        \
     do {                                                                                                                \
-        if constexpr (NB > 0) hipLaunchKernelGGL((render_bwd_sh_kernel<NB, MM, 4, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin); \
+        if constexpr (MASKED) hipLaunchKernelGGL((render_ns_bwd_kernel<NF, MM, 4, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin); \
+        else if constexpr (NB > 0) hipLaunchKernelGGL((render_bwd_sh_kernel<NB, MM, 4, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin); \
         else hipLaunchKernelGGL((render_bwd_kernel<NF, BF16, MM, 4, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin);  \
     } while (0)
         if (m <= 4) SO_L(1);
@@ -356,7 +369,8 @@ int launch_ray(const so_render_bwd_args &ba, const RbBin &bin, hipStream_t st) {
         const int blocks = (ba.fwd.n_rays + 3) / 4;
 #define SO_L(MM)                                                                                                        \
     do {                                                                                                                \
-        if constexpr (NB > 0) hipLaunchKernelGGL((render_bwd_sh_kernel<NB, MM, 1, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin); \
+        if constexpr (MASKED) hipLaunchKernelGGL((render_ns_bwd_kernel<NF, MM, 1, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin); \
+        else if constexpr (NB > 0) hipLaunchKernelGGL((render_bwd_sh_kernel<NB, MM, 1, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin); \
         else hipLaunchKernelGGL((render_bwd_kernel<NF, BF16, MM, 1, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin);  \
     } while (0)
         if (m <= 1) SO_L(1);
@@ -366,11 +380,11 @@ int launch_ray(const so_render_bwd_args &ba, const RbBin &bin, hipStream_t st) {
     return so_launch_status();
 }
 
-template <int NF, bool BF16, int MK, int NB = 0>
+template <int NF, bool BF16, int MK, int NB = 0, bool MASKED = false>
 int launch_mk(const so_render_bwd_args &ba, hipStream_t st) {
     const so_render_args &a = ba.fwd;
     const bool binned = ba.scatter_ws != nullptr && rb_in_range(a) && (ba.g_sdf_vol || ba.g_feat_vol);
-    if (!binned) return launch_ray<NF, BF16, false, MK, NB>(ba, RbBin{}, st);
+    if (!binned) return launch_ray<NF, BF16, false, MK, NB, MASKED>(ba, RbBin{}, st);
     RbBin bin;
     int max_items = 0;
     const size_t need = rb_layout<NF, NB>(a, rb_chunk(), (char *)ba.scatter_ws, &bin, &max_items);
@@ -385,7 +399,7 @@ int launch_mk(const so_render_bwd_args &ba, hipStream_t st) {
                        dim3(kCountWaves * 64), 0, st, a, bin);
     hipLaunchKernelGGL(rb_scan1_kernel, dim3(sblocks), dim3(1024), 0, st, bin);
     hipLaunchKernelGGL(rb_scan2_kernel, dim3(sblocks), dim3(1024), 0, st, bin);
-    if (int rc = launch_ray<NF, BF16, true, MK, NB>(ba, bin, st)) return rc;
+    if (int rc = launch_ray<NF, BF16, true, MK, NB, MASKED>(ba, bin, st)) return rc;
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
     const size_t lds = (size_t)kTileVox * RbRec<NF, NB>::RW * 8;
     if constexpr (NB > 0) {
@@ -418,6 +432,12 @@ int launch_m(const so_render_bwd_args &ba, hipStream_t st) {
     return launch_mk<NF, BF16, SO_MAP_LINEAR>(ba, st);
 }
 
+template <int NF>
+int launch_ns(const so_render_bwd_args &ba, hipStream_t st) {
+    if (ba.fwd.map.kind == SO_MAP_UPSCALE) return launch_mk<NF, false, SO_MAP_UPSCALE, 0, true>(ba, st);
+    return launch_mk<NF, false, SO_MAP_LINEAR, 0, true>(ba, st);
+}
+
 template <int NB>
 int launch_sh(const so_render_bwd_args &ba, hipStream_t st) {
     if (ba.fwd.map.kind == SO_MAP_UPSCALE) return launch_mk<so_sh_stride(NB), false, SO_MAP_UPSCALE, NB>(ba, st);
@@ -438,12 +458,12 @@ extern "C" size_t selfocc_render_bwd_ws_bytes(const so_render_bwd_args *args) {
                              : (a.sh_deg == 1 ? rb_layout<12, 4>(a, rb_chunk(), nullptr, nullptr, nullptr)
                                               : rb_layout<28, 9>(a, rb_chunk(), nullptr, nullptr, nullptr));
     }
-    switch (a.n_rgb + a.n_sem == 3 ? 4 : a.n_rgb + a.n_sem) {
+    if (a.n_sem == 1 || a.n_sem > 21 || a.n_sem < 0) return 0;   // not built (so_validate_render)
+    switch (a.n_rgb + a.n_sem == 0 ? 0 : (3 + a.n_sem + 3) & ~3) {   // the row width: 64-byte records up to 8 floats, 128-byte above
         case 0: return rb_layout<0>(a, rb_chunk(), nullptr, nullptr, nullptr);
         case 4: return rb_layout<4>(a, rb_chunk(), nullptr, nullptr, nullptr);
         case 8: return rb_layout<8>(a, rb_chunk(), nullptr, nullptr, nullptr);
-        case 24: return rb_layout<24>(a, rb_chunk(), nullptr, nullptr, nullptr);
-        default: return 0;
+        default: return rb_layout<24>(a, rb_chunk(), nullptr, nullptr, nullptr);
     }
 }
 
@@ -463,14 +483,14 @@ extern "C" int selfocc_render_bwd(const so_render_bwd_args *args, void *stream) 
         SO_REQUIRE(a.feat_stride == 4, "n_rgb=3, n_sem=0 requires feat_stride == 4");
         return bf ? launch_m<4, true>(ba, st) : launch_m<4, false>(ba, st);
     }
-    SO_REQUIRE(a.feat_stride == nf, "semantic volumes require feat_stride == n_rgb + n_sem");
-    switch (nf) {
-        case 8:
-            SO_REQUIRE(!bf, "render_bwd: bfloat16 feature volumes: n_rgb + n_sem must be 3 or 24 (got 8)");
-            return launch_m<8, false>(ba, st);
-        case 24: return bf ? launch_m<24, true>(ba, st) : launch_m<24, false>(ba, st);
-        default: break;
+    // so_validate_render: n_sem in 2 .. 21, feat_stride = 3 + n_sem rounded up to 4, bfloat16 at 21 classes only
+    if (nf == 8) return launch_m<8, false>(ba, st);            // the shipped widths: rows without a pad channel
+    if (nf == 24) return bf ? launch_m<24, true>(ba, st) : launch_m<24, false>(ba, st);
+    switch (a.feat_stride) {                                   // any other class count: the masked family of its row width
+        case 8: return launch_ns<8>(ba, st);
+        case 12: return launch_ns<12>(ba, st);
+        case 16: return launch_ns<16>(ba, st);
+        case 20: return launch_ns<20>(ba, st);
+        default: return launch_ns<24>(ba, st);
     }
-    SO_REQUIRE(false, "unsupported n_rgb + n_sem = %d (built: 3, 8, 24)", nf);
-    return -1;
 }

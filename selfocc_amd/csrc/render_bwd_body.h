@@ -1,11 +1,13 @@
 // render_bwd_body.h — the body of the ray kernels of render_bwd.hip, included once per kernel template (no include guard).
 // The including kernel provides its by-value arguments `so_render_bwd_args ba`, `RbBin bin` and the compile-time constants
-// NF, BF16, M, WPR, BIN, MK, NB.  Textual sharing instead of a common device function: the shipped kernels must stay the code
+// NF, BF16, M, WPR, BIN, MK, NB, MASKED (SO_SEM_ON, so_device.h: d L / d feature stays an exact 0 in a pad channel, and neither
+// scatter adds a zero).  Textual sharing instead of a common device function: the shipped kernels must stay the code
 // they are, and a body that takes the arguments by reference compiles to different registers.
     static_assert(WPR == 1 || WPR == 4, "waves per ray");
     constexpr int RECF = RbRec<NF, NB>::RECF, NCH = RbRec<NF, NB>::NCH;
     const so_render_args &a = ba.fwd;
     constexpr int NSEM = (NB == 0 && NF > 4) ? NF - 3 : 0;
+    const int nsem = MASKED ? a.n_sem : NSEM;   // the launch's class count (uniform)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int ray = WPR == 1 ? blockIdx.x * 4 + wave : blockIdx.x;
     const int wstep = WPR == 1 ? 0 : wave;   // position of this wave inside a step group
@@ -209,10 +211,13 @@
             if constexpr (NSEM > 0) {
                 float mx = lg[0];
 #pragma unroll
-                for (int k = 1; k < NSEM; ++k) mx = fmaxf(mx, lg[k]);
+                for (int k = 1; k < NSEM; ++k) if (SO_SEM_ON(k)) mx = fmaxf(mx, lg[k]);
                 float den = 0.0f;
 #pragma unroll
-                for (int k = 0; k < NSEM; ++k) { lg[k] = so_expf(lg[k] - mx); den += lg[k]; }
+                for (int k = 0; k < NSEM; ++k) {
+                    if (SO_SEM_ON(k)) { lg[k] = so_expf(lg[k] - mx); den += lg[k]; }
+                    else lg[k] = 0.0f;
+                }
                 const float iden = 1.0f / den;
 #pragma unroll
                 for (int k = 0; k < NSEM; ++k) pk_s[(j * NSEM + k) * 256 + threadIdx.x] = lg[k] * iden;
@@ -234,7 +239,7 @@
         float g_semr[NSEM > 0 ? NSEM : 1];
         if constexpr (NSEM > 0) {
 #pragma unroll
-            for (int k = 0; k < NSEM; ++k) g_semr[k] = ba.g_sem ? ba.g_sem[(size_t)ray * NSEM + k] : 0.0f;
+            for (int k = 0; k < NSEM; ++k) g_semr[k] = (ba.g_sem && SO_SEM_ON(k)) ? ba.g_sem[(size_t)ray * nsem + k] : 0.0f;
         }
         // pass 2: full feature vector per sample: Gw += g_rgb . col + g_sem . p; scatter d L / d feat.
         // The scatter is TRANSPOSED through LDS: each lane parks {cell, 8 corner weights, d L / d f[NF]}
@@ -275,10 +280,10 @@
                     for (int k = 0; k < NSEM; ++k) pk[k] = pk_s[(j * NSEM + k) * 256 + threadIdx.x];
                     float gp = 0.0f;
 #pragma unroll
-                    for (int k = 0; k < NSEM; ++k) gp = fmaf(g_semr[k], pk[k], gp);
+                    for (int k = 0; k < NSEM; ++k) if (SO_SEM_ON(k)) gp = fmaf(g_semr[k], pk[k], gp);
                     Gw[j] += gp;
 #pragma unroll
-                    for (int k = 0; k < NSEM; ++k) df[3 + k] = w[j] * pk[k] * (g_semr[k] - gp);  // softmax backward
+                    for (int k = 0; k < NSEM; ++k) if (SO_SEM_ON(k)) df[3 + k] = w[j] * pk[k] * (g_semr[k] - gp);  // softmax backward
                 }
             }
             if constexpr (BIN) {

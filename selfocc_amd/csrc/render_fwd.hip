@@ -24,6 +24,8 @@ template <int NF, bool BF16>
 int so_render_fwd_samples(const so_render_args &a, hipStream_t st);
 template <int NB>
 int so_render_sh_samples(const so_render_args &a, hipStream_t st);
+template <int NF>
+int so_render_ns_samples(const so_render_args &a, hipStream_t st);
 
 namespace {
 
@@ -147,9 +149,12 @@ SO_DEVFN void so_gather_feat_interior(__amdgpu_buffer_rsrc_t rf, int W, int D, u
 
 // MK: the mapping kind (SO_MAP_LINEAR / SO_MAP_UPSCALE), a compile-time choice of so_locate_k
 // NB > 0: spherical-harmonics colour with NB basis functions (sh_device.h); NF is then the row stride of the coefficients
-template <int NF, bool BF16, int MK = SO_MAP_LINEAR, int NB = 0>
+// MASKED (the render_ns_* kernels): the row holds a.n_sem <= NF - 3 logits and up to three pad channels; SO_SEM_ON
+// (so_device.h) keeps a pad channel out of the soft-max and the outputs.  Unmasked it is the constant `true`.
+template <int NF, bool BF16, int MK = SO_MAP_LINEAR, int NB = 0, bool MASKED = false>
 SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g) {
     constexpr int NSEM = (NB == 0 && NF > 4) ? NF - 3 : 0;  // NF = 3 rgb (+1 pad) or 3 rgb + n_sem
+    const int nsem = MASKED ? a.n_sem : NSEM;                // wave-uniform
     float Y[NB > 0 ? NB : 1];                   // the ray's basis: once, before the march
     if constexpr (NB > 0) so_sh_basis<NB>(g.dx, g.dy, g.dz, Y);
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
@@ -221,13 +226,16 @@ SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g)
             if constexpr (NSEM > 0) {
                 float m = f[3];
 #pragma unroll
-                for (int k = 1; k < NSEM; ++k) m = fmaxf(m, f[3 + k]);
+                for (int k = 1; k < NSEM; ++k) if (SO_SEM_ON(k)) m = fmaxf(m, f[3 + k]);
                 float e[NSEM], den = 0.0f;
 #pragma unroll
-                for (int k = 0; k < NSEM; ++k) { e[k] = so_expf(f[3 + k] - m); den = den + e[k]; }
+                for (int k = 0; k < NSEM; ++k) {
+                    if (SO_SEM_ON(k)) { e[k] = so_expf(f[3 + k] - m); den = den + e[k]; }
+                    else e[k] = 0.0f;
+                }
                 float wd = w / den;
 #pragma unroll
-                for (int k = 0; k < NSEM; ++k) sem[k] = fmaf(wd, e[k], sem[k]);
+                for (int k = 0; k < NSEM; ++k) if (SO_SEM_ON(k)) sem[k] = fmaf(wd, e[k], sem[k]);
             }
         }
     }
@@ -255,7 +263,7 @@ SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g)
         if constexpr (NSEM > 0) {
             if (a.sem) {
 #pragma unroll
-                for (int k = 0; k < NSEM; ++k) a.sem[(size_t)ray * NSEM + k] = sem[k];
+                for (int k = 0; k < NSEM; ++k) if (SO_SEM_ON(k)) a.sem[(size_t)ray * nsem + k] = sem[k];
             }
         }
     }
@@ -500,10 +508,11 @@ struct FastStep {
 
 // `geom()` returns the lane's ray; it is called once up front and again inside the (rare) canonical cell
 // fallback, so that origin / direction / far need not stay in registers across the march loop.
-template <int NF, bool BF16, bool STAGED = false, bool FACE_SAFE = false, class GeomFn>
+template <int NF, bool BF16, bool STAGED = false, bool FACE_SAFE = false, bool MASKED = false, class GeomFn>
 SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool store = true,
                              float *lds = nullptr, int lane = 0, float *sem_lds = nullptr) {
     constexpr int NSEM = NF > 4 ? NF - 3 : 0;
+    const int nsem = MASKED ? a.n_sem : NSEM;   // wave-uniform (see so_march_exact)
     // The staged 24-channel float32 kernel keeps its 21 semantic accumulators in LDS (sem_lds[k * 256 + thread];
     // read-modify-write of a lane-private slot; ds_add_f32 measured 5 x slower) instead of registers: at 2 waves / SIMD the 256-VGPR budget was 14 - 19 registers short and the spills
     // went through the texture path the march is bound by (32 scratch accesses per sample beside 9 real loads).
@@ -750,20 +759,24 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
             if constexpr (NSEM > 0) {
                 float m = f[3];
 #pragma unroll
-                for (int k = 1; k < NSEM; ++k) m = fmaxf(m, f[3 + k]);
+                for (int k = 1; k < NSEM; ++k) if (SO_SEM_ON(k)) m = fmaxf(m, f[3 + k]);
                 float e[NSEM], den = 0.0f;
 #pragma unroll
                 for (int k = 0; k < NSEM; ++k) {
-                    e[k] = so_fast_exp2((f[3 + k] - m) * 1.44269504088896341f);
-                    den = den + e[k];
+                    if (SO_SEM_ON(k)) {
+                        e[k] = so_fast_exp2((f[3 + k] - m) * 1.44269504088896341f);
+                        den = den + e[k];
+                    } else {
+                        e[k] = 0.0f;
+                    }
                 }
                 const float wd = w * so_fast_rcp(den);
                 if constexpr (SEM_LDS) {
 #pragma unroll
-                    for (int k = 0; k < NSEM; ++k) sem_lds[k * 256] = fmaf(wd, e[k], sem_lds[k * 256]);      // lane-private slot
+                    for (int k = 0; k < NSEM; ++k) if (SO_SEM_ON(k)) sem_lds[k * 256] = fmaf(wd, e[k], sem_lds[k * 256]);      // lane-private slot
                 } else {
 #pragma unroll
-                    for (int k = 0; k < NSEM; ++k) sem[k] = fmaf(wd, e[k], sem[k]);
+                    for (int k = 0; k < NSEM; ++k) if (SO_SEM_ON(k)) sem[k] = fmaf(wd, e[k], sem[k]);
                 }
             }
         }
@@ -821,7 +834,7 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
         if constexpr (NSEM > 0) {
             if (a.sem) {
 #pragma unroll
-                for (int k = 0; k < NSEM; ++k) a.sem[(size_t)ray * NSEM + k] = SEM_LDS ? sem_lds[k * 256] : sem[k];
+                for (int k = 0; k < NSEM; ++k) if (SO_SEM_ON(k)) a.sem[(size_t)ray * nsem + k] = SEM_LDS ? sem_lds[k * 256] : sem[k];
             }
         }
     }
@@ -1098,17 +1111,17 @@ constexpr bool so_face_safe(March m) { return m == March::FastFaceSafe || m == M
 template <int NF, bool BF16>
 constexpr bool so_is_staged(March m) { return so_is_fast(m) && !BF16 && NF >= 4; }
 
-template <int NF, bool BF16, March MODE, class GeomFn>
+template <int NF, bool BF16, March MODE, bool MASKED = false, class GeomFn>
 SO_DEVFN void so_march(const so_render_args &a, int ray, GeomFn geom) {
     if constexpr (MODE == March::CanonicalUpscale) {
-        so_march_exact<NF, BF16, SO_MAP_UPSCALE>(a, ray, geom(a));
+        so_march_exact<NF, BF16, SO_MAP_UPSCALE, 0, MASKED>(a, ray, geom(a));
     } else if constexpr (so_is_skip(MODE)) {
         static_assert(NF == 0, "skip marcher: SDF-only launches");
         so_march_fast_ahead<so_face_safe(MODE)>(a, ray, geom);
     } else if constexpr (so_is_fast(MODE)) {
-        so_march_fast<NF, BF16, false, so_face_safe(MODE)>(a, ray, geom);
+        so_march_fast<NF, BF16, false, so_face_safe(MODE), MASKED>(a, ray, geom);
     } else {
-        so_march_exact<NF, BF16>(a, ray, geom(a));
+        so_march_exact<NF, BF16, SO_MAP_LINEAR, 0, MASKED>(a, ray, geom(a));
     }
 }
 
@@ -1188,7 +1201,7 @@ __global__ __launch_bounds__(256, (NF >= 8 ? 2 : 1)) void render_fwd_explicit(so
     so_march<NF, BF16, MODE>(a, ray, geom);
 }
 
-template <int NF, bool BF16, March MODE>
+template <int NF, bool BF16, March MODE, bool MASKED = false>
 SO_DEVFN void pixgrid_body(const so_render_args &a, int tiles_x, int tiles_y) {
     const TilePixel p = so_tile_pixel(tiles_x, tiles_y);
     const int cam = p.cam, wave = p.wave, lane = p.lane;
@@ -1203,13 +1216,13 @@ SO_DEVFN void pixgrid_body(const so_render_args &a, int tiles_x, int tiles_y) {
         auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_pixel_ray(a, cam, ix, iy); };
         constexpr int NSEM_LDS = NF - 3 >= 16 ? NF - 3 : 0;          // so_march_fast::SEM_LDS
         __shared__ float s_sem[NSEM_LDS > 0 ? NSEM_LDS * 256 : 1];
-        so_march_fast<NF, BF16, true, so_face_safe(MODE)>(a, ray, geom, real, s_stage + wave * StageGeom<NF>::kWaveDwords, lane,
+        so_march_fast<NF, BF16, true, so_face_safe(MODE), MASKED>(a, ray, geom, real, s_stage + wave * StageGeom<NF>::kWaveDwords, lane,
                                                           s_sem + threadIdx.x);
     } else {
         if (ix >= a.nx || iy >= a.ny) return;
         int ray = (cam * a.ny + iy) * a.nx + ix;
         auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_pixel_ray(a, cam, ix, iy); };
-        so_march<NF, BF16, MODE>(a, ray, geom);
+        so_march<NF, BF16, MODE, MASKED>(a, ray, geom);
     }
 }
 
@@ -1244,6 +1257,56 @@ int launch_fwd(const so_render_args &a, hipStream_t st) {
     return so_launch_status();
 }
 
+// ---- any class count from 2 to 21: the marches above with MASKED = true, one family per row width --------------
+// NF = the row width (8, 12, 16, 20, 24), float32 rows; the class count a.n_sem in [NF - 6, NF - 3] is a launch argument.
+// Launches with 5 or 21 classes keep the kernels above.
+template <int NF, March MODE>
+__global__ __launch_bounds__(256, 2) void render_ns_explicit(so_render_args a) {
+    int ray = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ray >= a.n_rays) return;
+    auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_explicit_ray(a, ray); };
+    so_march<NF, false, MODE, true>(a, ray, geom);
+}
+template <int NF, March MODE>
+__global__ __launch_bounds__(256, 2) void render_ns_pixgrid(so_render_args a, int tiles_x, int tiles_y) {
+    pixgrid_body<NF, false, MODE, true>(a, tiles_x, tiles_y);
+}
+
+template <int NF, March MODE>
+int launch_ns(const so_render_args &a, hipStream_t st) {
+    if (a.ray_mode == SO_RAYS_EXPLICIT) {
+        hipLaunchKernelGGL((render_ns_explicit<NF, MODE>), dim3((a.n_rays + 255) / 256), dim3(256), 0, st, a);
+    } else {
+        int tiles_x = (a.nx + 15) / 16, tiles_y = (a.ny + 15) / 16;
+        hipLaunchKernelGGL((render_ns_pixgrid<NF, MODE>), dim3(tiles_x * tiles_y * a.n_cams), dim3(256), 0, st, a, tiles_x, tiles_y);
+    }
+    return so_launch_status();
+}
+
+// the fast march's re-pack of the SDF volume (sdf_brickify_kernel)
+void so_launch_brickify(const so_render_args &a, hipStream_t st, int with_codes) {
+    // threadIdx.x = d (a power of two of them), threadIdx.y = w; blockIdx.x = h
+    const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
+    int qx = 1;
+    while (qx < D && qx < 256) qx *= 2;
+    const int wy = 256 / qx;
+    hipLaunchKernelGGL(sdf_brickify_kernel, dim3(H, min((W + wy - 1) / wy, 65535)), dim3(qx, wy), 0, st, a.sdf_vol, a.sdf_brick,
+                       H, W, D, a, with_codes);
+}
+
+// the routes of dispatch_ps below; SO_FLAG_NO_FACE_SAFE (an A/B switch of the shipped widths) is ignored: the march is face-safe
+template <int NF>
+int dispatch_ns(const so_render_args &a, hipStream_t st) {
+    if (a.weights || a.ts || a.deltas || a.sdf || a.grad) return so_render_ns_samples<NF>(a, st);
+    if (a.map.kind == SO_MAP_UPSCALE) return launch_ns<NF, March::CanonicalUpscale>(a, st);
+    const bool fast = !(a.flags & SO_FLAG_EXACT) && a.jitter_mode == SO_JITTER_NONE &&
+                      a.map.h.size1 == 0.0f && a.map.w.size1 == 0.0f && a.map.d.size1 == 0.0f &&
+                      (long long)a.map.h.tot_len * a.map.w.tot_len < (1 << 24) && a.map.d.tot_len < (1 << 24);   // so_cell_index
+    if (!fast) return launch_ns<NF, March::Canonical>(a, st);
+    if (a.sdf_brick) so_launch_brickify(a, st, 0);
+    return launch_ns<NF, March::FastFaceSafe>(a, st);
+}
+
 template <int NF, bool BF16>
 int dispatch_ps(const so_render_args &a, hipStream_t st) {
     bool per_sample = a.weights || a.ts || a.deltas || a.sdf || a.grad;
@@ -1265,14 +1328,7 @@ int dispatch_ps(const so_render_args &a, hipStream_t st) {
                 (long long)a.map.h.tot_len * a.map.w.tot_len < (1 << 24) && a.map.d.tot_len < (1 << 24);   // so_cell_index
     if (fast) {
         if (a.sdf_brick) {
-            const int with_codes = (NF == 0 && !(a.flags & SO_FLAG_NO_SKIP)) ? 1 : 0;
-            // threadIdx.x = d (a power of two of them), threadIdx.y = w; blockIdx.x = h
-            const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
-            int qx = 1;
-            while (qx < D && qx < 256) qx *= 2;
-            const int wy = 256 / qx;
-            hipLaunchKernelGGL(sdf_brickify_kernel, dim3(H, min((W + wy - 1) / wy, 65535)), dim3(qx, wy), 0, st, a.sdf_vol, a.sdf_brick,
-                               H, W, D, a, with_codes);
+            so_launch_brickify(a, st, (NF == 0 && !(a.flags & SO_FLAG_NO_SKIP)) ? 1 : 0);
         }
         if constexpr (NF == 0) {
             if (a.sdf_brick && !(a.flags & (SO_FLAG_NO_SKIP | SO_FLAG_NO_AHEAD)))
@@ -1404,6 +1460,16 @@ int so_validate_render(const so_render_args &a) {
         SO_REQUIRE(a.feat_stride == ((n_coef + 3) & ~3), "sh_deg = %d reads %d coefficients: feat_stride must be %d (got %d)",
                    (int)a.sh_deg, n_coef, (n_coef + 3) & ~3, (int)a.feat_stride);
     }
+    if (a.n_sem > 0 && !so_sh_launch(a)) {   // rows [r, g, b, logit_0 .. logit_{n_sem - 1}, pad]: n_sem = 2 .. 21
+        const int stride = (3 + a.n_sem + 3) & ~3;
+        SO_REQUIRE(a.n_sem != 1, "n_sem = 1 is not built (built: n_sem 0 and 2 .. 21): one class renders `acc`");
+        SO_REQUIRE(a.n_sem <= 21, "n_sem = %d is not built (built: n_sem 0 and 2 .. 21): the binned backward record and the "
+                   "32-lanes-per-sample brick kernel end at 24 channels", (int)a.n_sem);
+        SO_REQUIRE(a.feat_stride == stride, "n_sem = %d semantic channels: feat_stride must be %d = 3 + n_sem rounded up to 4 (got %d)",
+                   (int)a.n_sem, stride, (int)a.feat_stride);
+        SO_REQUIRE(a.feat_dtype == SO_DTYPE_F32 || a.n_sem == 21, "bfloat16 feature volumes with semantic channels are built for "
+                   "n_sem = 21, feat_stride = 24 only (got n_sem = %d)", (int)a.n_sem);
+    }
     if (a.ray_mode == SO_RAYS_EXPLICIT) {
         SO_REQUIRE(a.n_rays == 0 || (a.origins && a.dirs), "explicit rays need origins and dirs");
     } else if (a.ray_mode == SO_RAYS_PIXEL_GRID) {
@@ -1433,14 +1499,14 @@ extern "C" int selfocc_render_fwd(const so_render_args *args, void *stream) {
         SO_REQUIRE(a.feat_stride == 4, "n_rgb=3, n_sem=0 requires feat_stride == 4");
         return bf ? dispatch_ps<4, true>(a, st) : dispatch_ps<4, false>(a, st);
     }
-    SO_REQUIRE(a.feat_stride == nf, "semantic volumes require feat_stride == n_rgb + n_sem");
-    switch (nf) {
-        case 8:      // (bfloat16 storage is built for the shipped widths 4 and 24 only)
-            SO_REQUIRE(!bf, "bfloat16 feature volumes: n_rgb + n_sem must be 3 or 24 (got 8)");
-            return dispatch_ps<8, false>(a, st);
-        case 24: return bf ? dispatch_ps<24, true>(a, st) : dispatch_ps<24, false>(a, st);
-        default: break;
+    // so_validate_render: n_sem in 2 .. 21, feat_stride = 3 + n_sem rounded up to 4, bfloat16 at 21 classes only
+    if (nf == 8) return dispatch_ps<8, false>(a, st);          // the shipped widths: rows without a pad channel
+    if (nf == 24) return bf ? dispatch_ps<24, true>(a, st) : dispatch_ps<24, false>(a, st);
+    switch (a.feat_stride) {                                   // any other class count: the masked family of its row width
+        case 8: return dispatch_ns<8>(a, st);
+        case 12: return dispatch_ns<12>(a, st);
+        case 16: return dispatch_ns<16>(a, st);
+        case 20: return dispatch_ns<20>(a, st);
+        default: return dispatch_ns<24>(a, st);
     }
-    SO_REQUIRE(false, "unsupported n_rgb + n_sem = %d (built: 3, 8, 24)", nf);
-    return -1;
 }

@@ -69,13 +69,36 @@ SO_DEVFN void so_train_feat(const void *__restrict__ vol, int H, int W, int D, c
 template <int NF, bool BF16, int WPR, int MK = SO_MAP_LINEAR>
 __global__ __launch_bounds__(256) void render_fwd_samples_kernel(so_render_args a) {
     constexpr int NB = NF < 0 ? 1 : 0;   // no spherical harmonics (spelled value-dependent: the NB > 0 branches are never instantiated)
+    constexpr bool MASKED = false;
 #include "render_train_body.h"
 }
 template <int NB, int WPR, int MK>
 __global__ __launch_bounds__(256) void render_sh_samples_kernel(so_render_args a) {
     constexpr int NF = so_sh_stride(NB);
     constexpr bool BF16 = false;
+    constexpr bool MASKED = false;
 #include "render_train_body.h"
+}
+// any class count from 2 to 21: float32 rows of NF = 8, 12, 16, 20, 24 floats that hold a.n_sem in [NF - 6, NF - 3]
+// logits and up to three pad channels, which SO_SEM_ON keeps out of the soft-max
+template <int NF, int WPR, int MK>
+__global__ __launch_bounds__(256) void render_ns_samples_kernel(so_render_args a) {
+    constexpr int NB = NF < 0 ? 1 : 0;
+    constexpr bool BF16 = false;
+    constexpr bool MASKED = true;
+#include "render_train_body.h"
+}
+template <int NF, int WPR, int MK>
+int launch_ns_samples_w(const so_render_args &a, hipStream_t st) {
+    constexpr int RPB = 4 / WPR;
+    hipLaunchKernelGGL((render_ns_samples_kernel<NF, WPR, MK>), dim3((a.n_rays + RPB - 1) / RPB), dim3(256), 0, st, a);
+    return so_launch_status();
+}
+template <int NF, int MK>
+int launch_ns_samples(const so_render_args &a, hipStream_t st) {
+    if (a.n_samples <= 64) return launch_ns_samples_w<NF, 1, MK>(a, st);
+    if (a.n_samples <= 128) return launch_ns_samples_w<NF, 2, MK>(a, st);
+    return launch_ns_samples_w<NF, 4, MK>(a, st);
 }
 
 template <int NB, int WPR, int MK>
@@ -132,3 +155,14 @@ int so_render_sh_samples(const so_render_args &a, hipStream_t st) {
 template int so_render_sh_samples<1>(const so_render_args &, hipStream_t);
 template int so_render_sh_samples<4>(const so_render_args &, hipStream_t);
 template int so_render_sh_samples<9>(const so_render_args &, hipStream_t);
+
+// the masked launches of the training API (called by selfocc_render_fwd)
+template <int NF>
+int so_render_ns_samples(const so_render_args &a, hipStream_t st) {
+    return a.map.kind == SO_MAP_UPSCALE ? launch_ns_samples<NF, SO_MAP_UPSCALE>(a, st) : launch_ns_samples<NF, SO_MAP_LINEAR>(a, st);
+}
+template int so_render_ns_samples<8>(const so_render_args &, hipStream_t);
+template int so_render_ns_samples<12>(const so_render_args &, hipStream_t);
+template int so_render_ns_samples<16>(const so_render_args &, hipStream_t);
+template int so_render_ns_samples<20>(const so_render_args &, hipStream_t);
+template int so_render_ns_samples<24>(const so_render_args &, hipStream_t);

@@ -1,8 +1,9 @@
 // render_train_body.h — the body of the sample-parallel forward kernels of render_train.hip, included once per kernel
 // template (no include guard).  The including kernel provides: `so_render_args a` (its by-value kernel argument) and the
-// compile-time constants NF, BF16, WPR, MK, NB.  Textual sharing instead of a common device function: the shipped kernels
+// compile-time constants NF, BF16, WPR, MK, NB, MASKED (SO_SEM_ON, so_device.h).  Textual sharing instead of a common device function: the shipped kernels
 // must stay the code they are, and a body that takes the arguments by reference compiles to different registers.
     constexpr int NSEM = (NB == 0 && NF > 4) ? NF - 3 : 0;
+    const int nsem = MASKED ? a.n_sem : NSEM;     // the launch's class count (block-uniform); pad channels keep sem[k] = 0
     constexpr int RPB = 4 / WPR;                  // rays per block
     constexpr int NACC = 5 + NSEM;                // acc, dsum, rgb[3], sem[NSEM] partial sums per wave
     __shared__ float s_tot[2][4];                 // wave totals of the step factors, double-buffered over passes
@@ -119,13 +120,16 @@
                 if constexpr (NSEM > 0) {
                     float m = f[3];
 #pragma unroll
-                    for (int k = 1; k < NSEM; ++k) m = fmaxf(m, f[3 + k]);
+                    for (int k = 1; k < NSEM; ++k) if (SO_SEM_ON(k)) m = fmaxf(m, f[3 + k]);
                     float e[NSEM], den = 0.0f;
 #pragma unroll
-                    for (int k = 0; k < NSEM; ++k) { e[k] = so_expf(f[3 + k] - m); den = den + e[k]; }
+                    for (int k = 0; k < NSEM; ++k) {
+                        if (SO_SEM_ON(k)) { e[k] = so_expf(f[3 + k] - m); den = den + e[k]; }
+                        else e[k] = 0.0f;
+                    }
                     const float wd = w / den;
 #pragma unroll
-                    for (int k = 0; k < NSEM; ++k) sem[k] = fmaf(wd, e[k], sem[k]);
+                    for (int k = 0; k < NSEM; ++k) if (SO_SEM_ON(k)) sem[k] = fmaf(wd, e[k], sem[k]);
                 }
             }
         }
@@ -200,7 +204,7 @@
         if constexpr (NSEM > 0) {
             if (a.sem) {
 #pragma unroll
-                for (int k = 0; k < NSEM; ++k) a.sem[(size_t)ray * NSEM + k] = sem[k];
+                for (int k = 0; k < NSEM; ++k) if (SO_SEM_ON(k)) a.sem[(size_t)ray * nsem + k] = sem[k];
             }
         }
     }

@@ -11,6 +11,12 @@
 
 #define SO_DEVFN __device__ __forceinline__
 
+// Is semantic channel k of a render row a logit (not a pad channel)?  Used inside code that defines the compile-time constants
+// MASKED and NSEM (the row's capacity, NF - 3) and the wave-uniform `nsem` (the launch's class count, >= NSEM - 3).  Unmasked
+// kernels, and the channels every class count of the width has, get the constant `true`; a masked kernel compares its last
+// three channels with a launch argument: a select or a uniform branch, so that a pad value reaches no max, exp or sum.
+#define SO_SEM_ON(k) (!MASKED || (k) < NSEM - 3 || (k) < nsem)
+
 // ---- error plumbing -------------------------------------------------------------------
 void so_set_error(const char *fmt, ...);
 #define SO_REQUIRE(cond, ...)          \

@@ -196,6 +196,10 @@ class SDFField(BaseModule):
             if self.n_sem > 0 and (sh_deg > 0 or sh_act != 'relu'):
                 raise NotImplementedError(f"color_dims={color_dims} with sh_deg={sh_deg}, sh_act={sh_act!r} leaves {self.n_sem} "
                                           "semantic channels: semantic channels are built with sh_deg=0 and sh_act='relu' only")
+            if self.n_sem == 1 or self.n_sem > 21:
+                raise NotImplementedError(f"color_dims={color_dims} leaves n_sem={self.n_sem} semantic channels: the render kernels "
+                                          "are built for n_sem = 0 and 2 .. 21 (one class renders `acc`; the render rows end at "
+                                          "24 channels)")
             if feat_dtype != torch.float32 and (sh_deg > 0 or sh_act != 'relu'):
                 raise NotImplementedError("sh_deg > 0 / sh_act='sigmoid' are built for a float32 feature volume (got "
                                           f"{feat_dtype})")

@@ -21,7 +21,7 @@ class SDFVolume:
 
     sdf  : (H, W, D) float32
     feat : (H, W, D, F) float32 / bfloat16 or None; channels = raw colour (3) then
-           semantic logits (n_sem); F == 4 when n_sem == 0 (one pad channel).
+           semantic logits (n_sem = 2 .. 21), then pad: F == 3 + n_sem rounded up to a multiple of 4.
     sh_deg / sh_act : view-dependent colour (selfocc_amd/sh.py).  With sh_deg > 0 the colour channels are the
            3 * (sh_deg + 1)^2 spherical-harmonics coefficients, colour-major, F = 12 / 28 for degree 1 / 2 (float32,
            n_sem == 0); n_rgb stays 3, the number of colour outputs.
@@ -43,7 +43,9 @@ class SDFVolume:
         if sh_deg > 0:
             assert n_rgb == 3 and n_sem == 0, "sh_deg > 0 is built without semantic channels"
             return sh.feat_stride(sh_deg)
-        return 4 if n_sem == 0 else n_rgb + n_sem
+        # rows are [r, g, b, logit_0 .. logit_{n_sem - 1}, pad]: 3 + n_sem rounded up to 4 floats (4 without semantics; 8 / 24 for
+        # 5 / 21 classes have no pad).  The render kernels never read a pad channel and leave its gradient zero.
+        return (n_rgb + n_sem + 3) & ~3
 
     @property
     def n_colour(self):
