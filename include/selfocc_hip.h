@@ -159,7 +159,7 @@ enum { SO_SH_RELU = 0, SO_SH_SIGMOID = 1 };
  * up to a multiple of 4: 8 (2 - 5 classes), 12 (6 - 9), 16 (10 - 13), 20 (14 - 17) or 24 (18 - 21).  The up to three pad
  * channels may hold anything: they are never read into a result, and a backward never writes their gradient (it stays what
  * the caller put there: zero).  sem and g_sem are (n_rays, n_sem), without a pad.  5 and 21 classes (rows without a pad) run
- * the kernels they always ran; the other class counts run the render_ns_* kernels of the row width, which compare the last
+ * the kernels they always ran; the other class counts run the render kernels on the masked row of their width, which compare the last
  * three channels with n_sem.  Those march face-safe: SO_FLAG_NO_FACE_SAFE is ignored for them.
  * Refused on the host, by name in selfocc_last_error(): n_sem == 1 (one class renders `acc`), n_sem >= 22 (the binned backward
  * record and the 32-lanes-per-sample brick kernel end at 24 channels), any other feat_stride, a bfloat16 feat_vol at a class

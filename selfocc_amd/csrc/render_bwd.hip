@@ -14,11 +14,9 @@
 // division by the tiny f_i that a "suffix sum / f_i" formulation would need).
 // d L / d alpha_i = T_i (Gw_i - E_i), Gw_i = total derivative of the loss wrt weight i.
 // The volume gradient is a scatter of 8 (+ 8 * n_feat) hardware float atomics per sample.
-#include "so_device.h"
-#include "sh_device.h"
+#include "render_row.h"
 #include "ray_device.h"
 #include <stdlib.h>
-#include <type_traits>
 
 namespace {
 
@@ -72,8 +70,9 @@ SO_DEVFN int rb_shard(long long sample) { return (int)(sample >> 8) & (kShards -
 
 // NB > 0 (spherical harmonics): the record's feature part is {g_raw[3], dx, dy, dz, 0, 0} at every degree, and a sample is
 // served by 32 lanes of the brick kernel (3 * NB <= 27 coefficient channels)
-template <int NF, int NB = 0>
+template <class ROW>
 struct RbRec {
+    static constexpr int NF = ROW::NF, NB = ROW::NB;
     static constexpr int NCH = NB > 0 ? 3 * NB : (NF == 4 ? 3 : NF);                 // feature channels with a gradient
     static constexpr int RECF = NB > 0 ? 16 : (NF >= 12 ? 32 : (NF >= 4 ? 16 : 8));  // floats per record (>= NF + 8)
     static constexpr int LPG = NB > 0 ? 32 : RECF;                                    // lanes per sample in rb_brick_kernel
@@ -135,28 +134,493 @@ SO_DEVFN int rb_run(int key, int lane, int &head_lane) {
 // NB > 0: spherical-harmonics colour with NB basis functions (sh_device.h), NF = the row stride of the coefficients.
 // d L / d f[c * NB + k] = g_raw_c * Y_k is rank one per sample: the atomic scatter expands it into the row it parks in LDS,
 // the binned scatter stores g_raw[3] and the ray's unit direction in a 64-byte record and leaves the expansion to the brick kernel.
-template <int NF, bool BF16, int M, int WPR, bool BIN, int MK = SO_MAP_LINEAR>
+// MASKED rows: d L / d feature stays an exact 0 in a pad channel (SO_SEM_ON), and neither scatter adds a zero.
+// The body stays IN the kernel: as a device function that takes the arguments by reference it compiles to different registers.
+template <class ROW, int M, int WPR, bool BIN, int MK>
 __global__ __launch_bounds__(256) void render_bwd_kernel(so_render_bwd_args ba, RbBin bin) {
-    constexpr int NB = NF < 0 ? 1 : 0;   // no spherical harmonics (spelled value-dependent: the NB > 0 branches are never instantiated)
-    constexpr bool MASKED = false;
-#include "render_bwd_body.h"
-}
-template <int NB, int M, int WPR, bool BIN, int MK>
-__global__ __launch_bounds__(256) void render_bwd_sh_kernel(so_render_bwd_args ba, RbBin bin) {
-    constexpr int NF = so_sh_stride(NB);
-    constexpr bool BF16 = false;
-    constexpr bool MASKED = false;
-#include "render_bwd_body.h"
-}
-// any class count from 2 to 21: float32 rows of NF = 8, 12, 16, 20, 24 floats with a.n_sem in [NF - 6, NF - 3] logits
-// and up to three pad channels.  The binned scatter shares rb_brick_kernel<NF> with the unmasked widths: a pad channel's
-// record entry is an exact 0, which the brick kernel does not add.
-template <int NF, int M, int WPR, bool BIN, int MK>
-__global__ __launch_bounds__(256) void render_ns_bwd_kernel(so_render_bwd_args ba, RbBin bin) {
-    constexpr int NB = NF < 0 ? 1 : 0;
-    constexpr bool BF16 = false;
-    constexpr bool MASKED = true;
-#include "render_bwd_body.h"
+    constexpr int NF = ROW::NF, NB = ROW::NB, NSEM = ROW::NSEM;
+    constexpr bool BF16 = ROW::BF16, MASKED = ROW::MASKED;
+    static_assert(WPR == 1 || WPR == 4, "waves per ray");
+    constexpr int RECF = RbRec<ROW>::RECF, NCH = RbRec<ROW>::NCH;
+    const so_render_args &a = ba.fwd;
+    const int nsem = MASKED ? a.n_sem : NSEM;   // the launch's class count (uniform)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ray = WPR == 1 ? blockIdx.x * 4 + wave : blockIdx.x;
+    const int wstep = WPR == 1 ? 0 : wave;   // position of this wave inside a step group
+    __shared__ float xch[4][8];
+    // sum of v[0..N) over the waves that share the ray (block-uniform control flow when WPR == 4)
+    auto ray_sum = [&](auto &v, auto nconst) {
+        constexpr int N = decltype(nconst)::value;
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = so_wave_sum_32to1(v[k]);
+        if constexpr (WPR > 1) {
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < N; ++k) xch[wave][k] = v[k];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < N; ++k) v[k] = (xch[0][k] + xch[1][k]) + (xch[2][k] + xch[3][k]);
+            __syncthreads();
+        }
+    };
+    // per-wave transpose buffer of the feature-gradient scatter (phase B); odd record stride
+    __shared__ __attribute__((aligned(16))) float lds_rec[BIN ? 4 : 4 * 64 * (NF > 0 ? (NF + 9 + (((NF + 9) & 1) ? 0 : 1)) : 9)];
+    if (ray >= a.n_rays) return;  // wave-uniform (block-uniform when the waves share a ray)
+    const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
+    const int S = a.n_samples;
+    const RayGeom g = so_ray_of(a, ray);
+    float Y[NB > 0 ? NB : 1];
+    if constexpr (NB > 0) so_sh_basis<NB>(g.dx, g.dy, g.dz, Y);
+
+    float tn, tf;
+    so_collide(a, g, tn, tf);
+
+    // ---- phase A: per-sample forward state -------------------------------------------------
+    so_cell cell[M];
+    float alpha[M], fj[M], tmid[M], delta[M], Pc[M], Nc[M], sdfv[M], halfv[M];
+    bool live[M], cneg[M], unclipped[M];
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        const int i = (j * WPR + wstep) * 64 + lane;   // a step covers 64 CONSECUTIVE samples (one per lane)
+        live[j] = i < S;
+        const int ic = live[j] ? i : S - 1;
+        const float t0 = so_edge(a, ray, ic, tn, tf), t1 = so_edge(a, ray, ic + 1, tn, tf);
+        delta[j] = t1 - t0;
+        tmid[j] = (t0 + t1) / 2.0f;
+        cell[j] = sample_cell<MK>(a, g, t0, t1);
+        float v[8], wk[8];
+        so_gather_sdf(a.sdf_vol, H, W, D, cell[j], v);
+        sdfv[j] = so_trilerp_sdf(cell[j], v, wk);
+        float gx, gy, gz;
+        so_trilerp_grad(cell[j], v, gx, gy, gz);
+        const float cosv = (g.dx * gx + g.dy * gy) + g.dz * gz;
+        cneg[j] = cosv < 0.0f;
+        halfv[j] = (fminf(cosv, 0.0f) * delta[j]) * 0.5f;
+        Pc[j] = so_sigmoid((sdfv[j] - halfv[j]) * so_inv_s(a));
+        Nc[j] = so_sigmoid((sdfv[j] + halfv[j]) * so_inv_s(a));
+        const float araw = ((Pc[j] - Nc[j]) + 1e-5f) / (Pc[j] + 1e-5f);
+        unclipped[j] = (araw > 0.0f) && (araw < 1.0f);
+        alpha[j] = live[j] ? fminf(fmaxf(araw, 0.0f), 1.0f) : 0.0f;
+        fj[j] = live[j] ? (1.0f - alpha[j]) + 1e-7f : 1.0f;
+    }
+    // BIN: the slots of this wave's samples in the brick-ordered record array: one returning atomic per run of lanes
+    // with one (brick, shard) counter, issued here so that its latency hides behind phase B's gathers
+    int slot_base[M], slot_head[M];
+    if constexpr (BIN) {
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            int key = -1;
+            if (live[j]) key = rb_key(bin, cell[j], H, W, D) * kShards + rb_shard((long long)ray * S + ((j * WPR + wstep) * 64 + lane));
+            const int run = rb_run(key, lane, slot_head[j]);
+            slot_base[j] = 0;
+            if (run > 0 && key >= 0) slot_base[j] = atomicAdd(bin.cursor + key, run);
+        }
+    }
+    // transmittance: exclusive prefix product over the samples in ray order = per step an exclusive scan
+    // over the lanes (Hillis-Steele on shuffles) times the product of all earlier steps
+    float T[M], w[M];
+    float acc_l = 0.0f, dsum_l = 0.0f, carry = 1.0f;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        float incl = fj[j];
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const float o = __shfl_up(incl, d, 64);
+            if (lane >= d) incl *= o;
+        }
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 1.0f;
+        const float tot = __shfl(incl, 63, 64);
+        float before = carry;                     // product over all earlier steps
+        if constexpr (WPR > 1) {
+            if (lane == 0) xch[wave][0] = tot;
+            __syncthreads();
+#pragma unroll
+            for (int ww = 0; ww < WPR; ++ww) {
+                if (ww < wave) before *= xch[ww][0];
+                carry *= xch[ww][0];
+            }
+            __syncthreads();
+        } else {
+            carry *= tot;
+        }
+        T[j] = before * excl;
+        w[j] = alpha[j] * T[j];
+        acc_l += w[j];
+        dsum_l = fmaf(w[j], tmid[j], dsum_l);
+    }
+    float ad[2] = {acc_l, dsum_l};
+    ray_sum(ad, std::integral_constant<int, 2>{});
+    const float acc = ad[0], dsum = ad[1];
+    const float inv_ae = 1.0f / (acc + 1e-10f);
+    const float depth_raw = dsum * inv_ae;
+    const float ddn = (a.flags & SO_FLAG_DEPTH_DIV_NORM) ? 1.0f / g.dn : 1.0f;
+
+    // upstream per-ray gradients (wave-uniform)
+    const float g_depth = ba.g_depth ? ba.g_depth[ray] * ddn : 0.0f;
+    float g_accum = ba.g_acc ? ba.g_acc[ray] : 0.0f;
+    float g_rgb[3] = {0.0f, 0.0f, 0.0f};
+    if constexpr (NF > 0) {
+        if (ba.g_rgb) {
+            // rgb_k = clamp(sum_i w_i col_ik + bg_k (1 - acc)): the clamp and the background need the
+            // forward value; recompute sum_i w_i col_ik below, so first pass: gather colours
+        }
+    }
+
+    // ---- phase B: colour / semantics: Gw contributions + feature-volume scatter ---------------
+    float Gw[M];
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        const size_t so = (size_t)ray * S + ((j * WPR + wstep) * 64 + lane);
+        Gw[j] = (ba.g_weights && live[j]) ? ba.g_weights[so] : 0.0f;
+        Gw[j] += g_depth * (tmid[j] - depth_raw) * inv_ae;
+    }
+    if constexpr (NF > 0) {
+        float col[M][3];
+        float rgb_l[3] = {0.0f, 0.0f, 0.0f};
+        // pass 1: ONE gather of the 8 corners' feature rows per sample (round 6: the colours used to be gathered here and the whole
+        // rows again in pass 2 — the corner gathers are 475 of the ray kernel's 994 us, profiles/r6_c_render_bwd_gather_bound.txt):
+        // interpolated colour (kept: forward rgb for the clamp mask) and, with semantics, the sample's softmax probabilities (kept)
+        // (the probabilities wait in lane-private LDS columns [j][k][thread], not in 21 registers: kept live across the ray
+        // reduction they pushed the 24-channel kernel from 213 to 256 + 24 registers — one wave per SIMD — or into scratch)
+        __shared__ float pk_s[(NSEM > 0 ? NSEM : 1) * M * 256];
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            float f3[3] = {0.0f, 0.0f, 0.0f};
+            float lg[NSEM > 0 ? NSEM : 1];
+#pragma unroll
+            for (int k = 0; k < (NSEM > 0 ? NSEM : 1); ++k) lg[k] = 0.0f;
+            const float fd[2] = {cell[j].fd0, cell[j].fd1}, fw[2] = {cell[j].fw0, cell[j].fw1}, fh[2] = {cell[j].fh0, cell[j].fh1};
+            if constexpr (NB > 0) {   // the forward's fold: f3 = the raw (pre-activation) colour
+                float wk[8];
+#pragma unroll
+                for (int kk = 0; kk < 8; ++kk) wk[kk] = (fd[kk & 1] * fw[(kk >> 1) & 1]) * fh[kk >> 2];
+                so_sh_gather<NB>(a.feat_vol, H, W, D, cell[j], wk, Y, f3);
+            }
+#pragma unroll
+            for (int kk = 0; kk < (NB > 0 ? 0 : 8); ++kk) {
+                const int h = cell[j].h0 + (kk >> 2), ww = cell[j].w0 + ((kk >> 1) & 1), d = cell[j].d0 + (kk & 1);
+                const bool in = (h >= 0) && (h < H) && (ww >= 0) && (ww < W) && (d >= 0) && (d < D);
+                const int hc = min(max(h, 0), H - 1), wc = min(max(ww, 0), W - 1), dc = min(max(d, 0), D - 1);
+                const float wgt = in ? (fd[kk & 1] * fw[(kk >> 1) & 1]) * fh[kk >> 2] : 0.0f;
+                const size_t vox = ((size_t)hc * W + wc) * D + dc;
+                if constexpr (NSEM > 0) {
+                    float f[NF];
+#ifdef SO_RB_NO_GATHER      // A/B build (scripts/build_variant.sh nogather render_bwd.hip -DSO_RB_NO_GATHER; timing only): no corner gathers —
+#pragma unroll              // the bound of "keep the forward's interpolated features".  (As a RUN-TIME switch the branch cost the shipped
+                    for (int k = 0; k < NF; ++k) f[k] = 0.01f * k;      // kernel 45 %: 1 040 -> 1 502 us.)
+#else
+                    load_feat<NF, BF16>(a.feat_vol, vox, f);
+#endif
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) f3[k] = fmaf(f[k], wgt, f3[k]);
+#pragma unroll
+                    for (int k = 0; k < NSEM; ++k) lg[k] = fmaf(f[3 + k], wgt, lg[k]);
+                } else {
+                    float c3[3];
+#ifdef SO_RB_NO_GATHER
+                    c3[0] = 0.1f; c3[1] = 0.2f; c3[2] = 0.3f;
+#else
+                    if constexpr (!BF16) {
+                        const float *p = (const float *)a.feat_vol + vox * NF;
+                        c3[0] = p[0]; c3[1] = p[1]; c3[2] = p[2];
+                    } else {
+                        const uint16_t *p = (const uint16_t *)a.feat_vol + vox * NF;
+                        c3[0] = so_bf16_to_f32(p[0]); c3[1] = so_bf16_to_f32(p[1]); c3[2] = so_bf16_to_f32(p[2]);
+                    }
+#endif
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) f3[k] = fmaf(c3[k], wgt, f3[k]);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if constexpr (NB > 0) {
+                    col[j][k] = f3[k];                                // pre-activation
+                    rgb_l[k] = fmaf(w[j], so_sh_act(col[j][k], a.sh_act), rgb_l[k]);
+                } else {
+                    col[j][k] = 0.28209479177387814f * f3[k] + 0.5f;  // pre-relu
+                    rgb_l[k] = fmaf(w[j], fmaxf(col[j][k], 0.0f), rgb_l[k]);
+                }
+            }
+            if constexpr (NSEM > 0) {
+                float mx = lg[0];
+#pragma unroll
+                for (int k = 1; k < NSEM; ++k) if (SO_SEM_ON(k)) mx = fmaxf(mx, lg[k]);
+                float den = 0.0f;
+#pragma unroll
+                for (int k = 0; k < NSEM; ++k) {
+                    if (SO_SEM_ON(k)) { lg[k] = so_expf(lg[k] - mx); den += lg[k]; }
+                    else lg[k] = 0.0f;
+                }
+                const float iden = 1.0f / den;
+#pragma unroll
+                for (int k = 0; k < NSEM; ++k) pk_s[(j * NSEM + k) * 256 + threadIdx.x] = lg[k] * iden;
+            }
+        }
+        float bgk[3] = {0.0f, 0.0f, 0.0f};
+        ray_sum(rgb_l, std::integral_constant<int, 3>{});
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (a.bkgd_mode == SO_BKGD_CONST) bgk[k] = a.bkgd[k];
+            else if (a.bkgd_mode == SO_BKGD_PER_RAY) bgk[k] = a.bkgd_rays[3 * (size_t)ray + k];
+            float r = rgb_l[k];
+            if (a.bkgd_mode != SO_BKGD_NONE) r = r + bgk[k] * (1.0f - acc);
+            float gk = ba.g_rgb ? ba.g_rgb[3 * (size_t)ray + k] : 0.0f;
+            if ((a.flags & SO_FLAG_CLAMP_RGB) && (r < 0.0f || r > 1.0f)) gk = 0.0f;
+            g_rgb[k] = gk;
+            if (a.bkgd_mode != SO_BKGD_NONE) g_accum -= gk * bgk[k];
+        }
+        float g_semr[NSEM > 0 ? NSEM : 1];
+        if constexpr (NSEM > 0) {
+#pragma unroll
+            for (int k = 0; k < NSEM; ++k) g_semr[k] = (ba.g_sem && SO_SEM_ON(k)) ? ba.g_sem[(size_t)ray * nsem + k] : 0.0f;
+        }
+        // pass 2: full feature vector per sample: Gw += g_rgb . col + g_sem . p; scatter d L / d feat.
+        // The scatter is TRANSPOSED through LDS: each lane parks {cell, 8 corner weights, d L / d f[NF]}
+        // of its sample, then GS = 2^ceil(log2 NF) consecutive lanes own the NF contiguous channels of one
+        // sample's corner, so an atomic instruction touches 64 / GS segments of NF * 4 bytes instead of 64
+        // scattered dwords (the lane-per-sample form cost 112 ms per nuscenes_occ iteration).
+        constexpr int GS = NF <= 4 ? 4 : (NF <= 8 ? 8 : 32);       // lanes per sample in the scatter
+        constexpr int REC = NF + 9 + (((NF + 9) & 1) ? 0 : 1);     // odd stride: conflict-free columns
+        float *rec = lds_rec + wave * (64 * REC);
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            float df[NF];  // d L / d interpolated feature
+#pragma unroll
+            for (int k = 0; k < NF; ++k) df[k] = 0.0f;
+            const float fd[2] = {cell[j].fd0, cell[j].fd1}, fw[2] = {cell[j].fw0, cell[j].fw1}, fh[2] = {cell[j].fh0, cell[j].fh1};
+            float g_raw[3] = {0.0f, 0.0f, 0.0f};   // NB > 0: d L / d raw colour
+            if (live[j]) {
+                if constexpr (NB > 0) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        Gw[j] = fmaf(g_rgb[k], so_sh_act(col[j][k], a.sh_act), Gw[j]);
+                        g_raw[k] = (g_rgb[k] * w[j]) * so_sh_dact(col[j][k], a.sh_act);
+                    }
+                    if constexpr (!BIN) {
+#pragma unroll
+                        for (int k = 0; k < 3 * NB; ++k) df[k] = g_raw[k / NB] * Y[k % NB];
+                    }
+                } else {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    Gw[j] = fmaf(g_rgb[k], fmaxf(col[j][k], 0.0f), Gw[j]);
+                    df[k] = (col[j][k] > 0.0f) ? g_rgb[k] * w[j] * 0.28209479177387814f : 0.0f;
+                }
+                }
+                if constexpr (NSEM > 0) {
+                    float pk[NSEM];
+#pragma unroll
+                    for (int k = 0; k < NSEM; ++k) pk[k] = pk_s[(j * NSEM + k) * 256 + threadIdx.x];
+                    float gp = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < NSEM; ++k) if (SO_SEM_ON(k)) gp = fmaf(g_semr[k], pk[k], gp);
+                    Gw[j] += gp;
+#pragma unroll
+                    for (int k = 0; k < NSEM; ++k) if (SO_SEM_ON(k)) df[3 + k] = w[j] * pk[k] * (g_semr[k] - gp);  // softmax backward
+                }
+            }
+            if constexpr (BIN) {
+                const int slot = __shfl(slot_base[j], slot_head[j], 64) + (lane - slot_head[j]);
+                if constexpr (NB > 0) {
+                    if (live[j]) {
+                        float4 *dst = (float4 *)(bin.rec + (size_t)slot * RECF);
+                        dst[0] = make_float4(g_raw[0], g_raw[1], g_raw[2], g.dx);
+                        dst[1] = make_float4(g.dy, g.dz, 0.0f, 0.0f);
+                    }
+                } else
+                if (live[j] && !(bin.dbg & 8)) {   // the feature part of the sample's record, 16 bytes at a time
+                    float4 *dst = (float4 *)(bin.rec + (size_t)slot * RECF);
+#pragma unroll
+                    for (int q = 0; q < (RECF - 8) / 4; ++q) {
+                        float4 t;
+                        t.x = (4 * q < NCH) ? df[(4 * q < NCH) ? 4 * q : 0] : 0.0f;
+                        t.y = (4 * q + 1 < NCH) ? df[(4 * q + 1 < NCH) ? 4 * q + 1 : 0] : 0.0f;
+                        t.z = (4 * q + 2 < NCH) ? df[(4 * q + 2 < NCH) ? 4 * q + 2 : 0] : 0.0f;
+                        t.w = (4 * q + 3 < NCH) ? df[(4 * q + 3 < NCH) ? 4 * q + 3 : 0] : 0.0f;
+                        dst[q] = t;
+                    }
+                }
+            } else if (ba.g_feat_vol) {   // wave-uniform
+                float *mine = rec + lane * REC;
+                mine[0] = __int_as_float((cell[j].h0 * W + cell[j].w0) * D + cell[j].d0);
+#pragma unroll
+                for (int kk = 0; kk < 8; ++kk) {
+                    const int h = cell[j].h0 + (kk >> 2), ww = cell[j].w0 + ((kk >> 1) & 1), d = cell[j].d0 + (kk & 1);
+                    const bool in = live[j] && (h >= 0) && (h < H) && (ww >= 0) && (ww < W) && (d >= 0) && (d < D);
+                    mine[1 + kk] = in ? (fd[kk & 1] * fw[(kk >> 1) & 1]) * fh[kk >> 2] : 0.0f;
+                }
+#pragma unroll
+                for (int k = 0; k < NF; ++k) mine[9 + k] = (NF == 4 && k == 3) ? 0.0f : df[k];
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const int sub = lane % GS, grp = lane / GS;
+                // Row grp serves the samples of lanes grp * GS .. + GS - 1, which are CONSECUTIVE on the ray; a
+                // run of samples inside one voxel (about two at the shipped step / voxel ratio) shares its 8
+                // corners, so the row sums the run's contributions and issues one set of atomics for it.
+                // (The rows of one instruction are GS samples apart: different voxels, no shared L2 line.)
+                for (int t = 0; t < GS; ++t) {
+                    const float *r = rec + (grp * GS + t) * REC;
+                    const int base = __float_as_int(r[0]);
+                    if (t > 0 && __float_as_int(r[-REC]) == base) continue;   // inside a run: already added
+                    float val[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                    int tt = t;
+                    const float *rr = r;
+                    do {
+                        const float dfc = (sub < NF) ? rr[9 + sub] : 0.0f;
+#pragma unroll
+                        for (int kk = 0; kk < 8; ++kk) val[kk] = fmaf(rr[1 + kk], dfc, val[kk]);
+                        ++tt;
+                        rr += REC;
+                    } while (tt < GS && __float_as_int(rr[0]) == base);
+                    if (sub < NF) {
+#pragma unroll
+                        for (int kk = 0; kk < 8; ++kk) {
+                            if (val[kk] != 0.0f) {
+                                const int vox = base + ((kk >> 2) * W + ((kk >> 1) & 1)) * D + (kk & 1);
+                                unsafeAtomicAdd(ba.g_feat_vol + (size_t)vox * NF + sub, val[kk]);
+                            }
+                        }
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < M; ++j) Gw[j] += g_accum;
+
+    // ---- phase C: reverse affine scan  E_i = Gw_{i+1} alpha_{i+1} + f_{i+1} E_{i+1} -----------
+    // Each sample is the affine map x -> Gw_i alpha_i + f_i x; E_i is the composition of the maps of all
+    // later samples applied to 0.  Per step (last step first): inclusive suffix composition over the lanes,
+    // then E of lane l = (maps of lanes l+1 .. 63 of this step)(E after the step).
+    float Ev[M];
+    float E_end = 0.0f;   // E after the last sample of the current step
+#pragma unroll
+    for (int j = M - 1; j >= 0; --j) {
+        float SA = Gw[j] * alpha[j], SB = fj[j];
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const float oa = __shfl_down(SA, d, 64), ob = __shfl_down(SB, d, 64);
+            if (lane + d < 64) { SA = fmaf(SB, oa, SA); SB = SB * ob; }
+        }
+        const float na = __shfl_down(SA, 1, 64), nb = __shfl_down(SB, 1, 64);
+        const float wa = __shfl(SA, 0, 64), wb = __shfl(SB, 0, 64);   // the whole step as one map
+        float E_mine = E_end;                     // E after the last sample of THIS wave's step
+        if constexpr (WPR > 1) {
+            if (lane == 0) { xch[wave][0] = wa; xch[wave][1] = wb; }
+            __syncthreads();
+#pragma unroll
+            for (int ww = WPR - 1; ww >= 0; --ww) {   // later steps are applied first
+                if (ww > wave) E_mine = fmaf(xch[ww][1], E_mine, xch[ww][0]);
+                E_end = fmaf(xch[ww][1], E_end, xch[ww][0]);
+            }
+            __syncthreads();
+        } else {
+            E_end = fmaf(wb, E_end, wa);
+        }
+        Ev[j] = (lane == 63) ? E_mine : fmaf(nb, E_mine, na);
+    }
+
+    float dinv_s_l = 0.0f;
+    // SDF-volume records: {cell, 8 corner coefficients} per lane, in this wave's own slab of lds_rec (the same
+    // slab as its feature records: with one wave per ray the waves of a block are not in step)
+    float *srec = lds_rec + wave * (64 * (NF > 0 ? (NF + 9 + (((NF + 9) & 1) ? 0 : 1)) : 9));
+#pragma unroll
+    for (int j = M - 1; j >= 0; --j) {
+        float dalpha = T[j] * (Gw[j] - Ev[j]);
+        float coefs[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        float r_ds = 0.0f, r_qx = 0.0f, r_qy = 0.0f, r_qz = 0.0f;   // BIN: the record's sdf coefficients
+        if (live[j]) {
+            if (!unclipped[j]) dalpha = 0.0f;
+            const float pe = Pc[j] + 1e-5f;
+            const float dP = dalpha * (Nc[j] / (pe * pe));
+            const float dN = -dalpha / pe;
+            const float da = dP * Pc[j] * (1.0f - Pc[j]);
+            const float db = dN * Nc[j] * (1.0f - Nc[j]);
+            const size_t so = (size_t)ray * S + ((j * WPR + wstep) * 64 + lane);
+            float ds = (da + db) * so_inv_s(a);
+            const float dh = (db - da) * so_inv_s(a);
+            dinv_s_l += da * (sdfv[j] - halfv[j]) + db * (sdfv[j] + halfv[j]);
+            const float dc = cneg[j] ? dh * (delta[j] * 0.5f) : 0.0f;
+            float dgx = dc * g.dx, dgy = dc * g.dy, dgz = dc * g.dz;
+            if (ba.g_sdf) ds += ba.g_sdf[so];
+            if (ba.g_grad) { dgx += ba.g_grad[3 * so]; dgy += ba.g_grad[3 * so + 1]; dgz += ba.g_grad[3 * so + 2]; }
+            if (BIN && ba.g_sdf_vol) {
+                r_ds = ds; r_qx = dgx * cell[j].sw; r_qy = dgy * cell[j].sh; r_qz = dgz * cell[j].sd;
+            }
+            if (!BIN && ba.g_sdf_vol) {
+                // sdf = sum_k W_k v_k ; grad_axis = slope_axis * sum_k dW_k/d axis * v_k
+                const so_cell &c = cell[j];
+                const float fd[2] = {c.fd0, c.fd1}, fw[2] = {c.fw0, c.fw1}, fh[2] = {c.fh0, c.fh1};
+                const float qx = dgx * c.sw, qy = dgy * c.sh, qz = dgz * c.sd;  // metre x<->w, y<->h, z<->d
+#pragma unroll
+                for (int kk = 0; kk < 8; ++kk) {
+                    const int kd = kk & 1, kw = (kk >> 1) & 1, kh = kk >> 2;
+                    const int h = c.h0 + kh, ww = c.w0 + kw, d = c.d0 + kd;
+                    const bool in = (h >= 0) && (h < H) && (ww >= 0) && (ww < W) && (d >= 0) && (d < D);
+                    const float Wk = (fd[kd] * fw[kw]) * fh[kh];
+                    const float dWd = (kd ? 1.0f : -1.0f) * (fw[kw] * fh[kh]);
+                    const float dWw = (kw ? 1.0f : -1.0f) * (fd[kd] * fh[kh]);
+                    const float dWh = (kh ? 1.0f : -1.0f) * (fd[kd] * fw[kw]);
+                    coefs[kk] = in ? fmaf(Wk, ds, fmaf(dWd, qz, fmaf(dWw, qx, dWh * qy))) : 0.0f;
+                }
+            }
+        }
+        if constexpr (BIN) {
+            const so_cell &c = cell[j];
+            const int slot = __shfl(slot_base[j], slot_head[j], 64) + (lane - slot_head[j]);
+            if (live[j]) {
+                // so_locate does not clamp: a sample outside the box (a ray that misses it, near_plane past the exit, an
+                // aabb larger than the mapping) has h0 <= -2 or h0 >= H.  The clamp keeps such an index OUTSIDE the volume
+                // (-2 and 1021 >= tot_len fail every corner test of rb_brick_kernel), as the atomic path's `in` test does.
+                const int pack = ((min(max(c.h0, -2), 1021) + 2) << 20) | ((min(max(c.w0, -2), 1021) + 2) << 10) |
+                                 (min(max(c.d0, -2), 1021) + 2);
+                float4 *dst = (float4 *)(bin.rec + (size_t)slot * RECF + (RECF - 8));
+                dst[0] = make_float4(r_ds, __int_as_float(pack), c.fh1, c.fw1);
+                dst[1] = make_float4(c.fd1, r_qx, r_qy, r_qz);
+            }
+        } else if (ba.g_sdf_vol) {   // wave-uniform
+            // Scalar per-lane atomics would be one 64-byte fabric write each (8 per sample: as much traffic as
+            // the whole feature scatter).  Instead 8-lane rows (one corner per lane) walk the samples in ray
+            // order and add the coefficients of a run of samples inside one voxel before one atomic per corner.
+            float *mine = srec + lane * 9;
+            mine[0] = __int_as_float((cell[j].h0 * W + cell[j].w0) * D + cell[j].d0);
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk) mine[1 + kk] = coefs[kk];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const int sub = lane & 7, grp = lane >> 3;
+            const int voff = ((sub >> 2) * W + ((sub >> 1) & 1)) * D + (sub & 1);
+            for (int t = 0; t < 8; ++t) {
+                const float *r = srec + (grp * 8 + t) * 9;
+                const int base = __float_as_int(r[0]);
+                if (t > 0 && __float_as_int(r[-9]) == base) continue;   // inside a run: already added
+                float val = 0.0f;
+                int tt = t;
+                const float *rr = r;
+                do {
+                    val += rr[1 + sub];
+                    ++tt;
+                    rr += 9;
+                } while (tt < 8 && __float_as_int(rr[0]) == base);
+                // a coefficient is non-zero only for a corner inside the volume, so base + voff is a valid voxel
+                if (val != 0.0f) unsafeAtomicAdd(ba.g_sdf_vol + (base + voff), val);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    if (ba.g_inv_s) {
+        const float t = so_wave_sum_32to1(dinv_s_l);
+        // BIN: kInvsSlots partial sums (rb_brick_kernel's first block adds them up) instead of one atomic per wave on ONE word
+        if (lane == 0) unsafeAtomicAdd(BIN ? bin.invs_part + (blockIdx.x & (kInvsSlots - 1)) : ba.g_inv_s, t);
+    }
 }
 
 // ---- the binned scatter's own kernels ---------------------------------------------------------------------
@@ -290,20 +754,151 @@ SO_DEVFN float rb_sh_one(int k, float x, float y, float z) {
     }
 }
 
-// NB > 0: spherical-harmonics records (RbRec<NF, NB>): 32 lanes per sample, lane `sub` < 3 * NB owns coefficient channel sub and
+// NB > 0: spherical-harmonics records (RbRec<ROW>): 32 lanes per sample, lane `sub` < 3 * NB owns coefficient channel sub and
 // expands g_raw[sub / NB] * Y_(sub % NB)(direction) itself; the last 8 lanes of the 32 ALSO own one sdf corner each.
-template <int NF, int NT>
+// ROW: float32 and unmasked (rb_brick_row): the records hold floats whatever the volume does, and a pad channel's record entry
+// is an exact 0, which this kernel does not add.
+template <class ROW, int NT>
 __global__ __launch_bounds__(NT) void rb_brick_kernel(RbBin b, float *__restrict__ g_sdf_vol, float *__restrict__ g_feat_vol,
                                                       float *__restrict__ g_inv_s, int H, int W, int D) {
-    constexpr int NB = NF < 0 ? 1 : 0;   // no spherical harmonics
-#include "render_bwd_brick_body.h"
+    constexpr int NF = ROW::NF, NB = ROW::NB;
+    constexpr int RECF = RbRec<ROW>::RECF, NCH = RbRec<ROW>::NCH, RW = RbRec<ROW>::RW, LPG = RbRec<ROW>::LPG;
+    constexpr int NG = NT / LPG, U = 4;
+    extern __shared__ double tile[];   // [kTileVox][RW]
+    if (blockIdx.x == 0 && g_inv_s) {   // the ray kernel's partial sums of d L / d inv_s: one atomic per wave of this block
+        float t = 0.0f;
+        for (int k = threadIdx.x; k < kInvsSlots; k += NT) t += b.invs_part[k];
+        t = so_wave_sum_32to1(t);
+        if ((threadIdx.x & 63) == 0) unsafeAtomicAdd(g_inv_s, t);
+    }
+    if ((int)blockIdx.x >= b.n_items[0]) return;
+    const int4 it = b.items[blockIdx.x];
+    const int bd = it.x % b.nbd, bw = (it.x / b.nbd) % b.nbw, bh = it.x / (b.nbd * b.nbw);
+    const int oh = bh * kBH, ow = bw * kBW, od = bd * kBD;
+    for (int k = threadIdx.x; k < kTileVox * RW; k += NT) tile[k] = 0.0;
+    __syncthreads();
+    const int grp = threadIdx.x / LPG, sub = threadIdx.x % LPG;
+    // lanes [0, NCH) of a group: one feature channel each, all 8 corners; lanes [RECF - 8, RECF): ONE corner each of the
+    // sdf column (its coefficient has four terms: spreading the corners over the 8 otherwise idle tail lanes keeps the
+    // per-corner loop of the feature lanes at one multiply)
+    const bool sdf_lane = sub >= LPG - 8;
+    const int mk = sub - (LPG - 8), mkd = mk & 1, mkw = (mk >> 1) & 1, mkh = (mk >> 2) & 1;
+    const int moff = ((mkh * kTW + mkw) * kTD + mkd) * RW + NCH;
+    // Group g walks the CONTIGUOUS slice [y + g * per, ...) of the item, U records at a time.  The records of an item are
+    // in ray order (a run of consecutive samples of one ray takes consecutive slots), and consecutive samples of a ray share
+    // their cell 2 - 6 times at the shipped step / voxel ratio: the group sums such a run in registers and issues its LDS
+    // atomics once per run (the kernel sits on the ds_add_f64 issue rate: ~15 clocks per instruction, 35 M of them per launch
+    // before this).  SELFOCC_RB_DBG & 4: no merging (every sample flushes).
+    const int per = (it.z - it.y + NG - 1) / NG;
+    const int gb = it.y + grp * per, ge = min(it.z, gb + per);
+    const bool merge = !(b.dbg & 4);
+    int cur = -1;                 // packed cell of the open run
+    float acc[8];                 // feature lanes: the run's sum per corner; sdf lanes: acc[0] = the own corner's sum
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0.0f;
+    float sacc_sh = 0.0f;         // NB > 0: a lane can own a channel AND an sdf corner, so the sdf sum has its own register
+    float &sacc = *[&]() { if constexpr (NB > 0) return &sacc_sh; else return &acc[0]; }();
+    auto flush = [&]() {
+        const int h0 = (cur >> 20) - 2, w0 = ((cur >> 10) & 1023) - 2, d0 = (cur & 1023) - 2;
+        const int lh = h0 - oh, lw = w0 - ow, ld = d0 - od;
+        // a corner counts when it is inside the volume AND inside this brick's tile (the second never fails: the
+        // counting pass and the ray kernel derive the cell with the same code; it only keeps a mismatch inside the tile)
+        const bool okh[2] = {((unsigned)h0 < (unsigned)H) && ((unsigned)lh < (unsigned)kTH),
+                             ((unsigned)(h0 + 1) < (unsigned)H) && ((unsigned)(lh + 1) < (unsigned)kTH)};
+        const bool okw[2] = {((unsigned)w0 < (unsigned)W) && ((unsigned)lw < (unsigned)kTW),
+                             ((unsigned)(w0 + 1) < (unsigned)W) && ((unsigned)(lw + 1) < (unsigned)kTW)};
+        const bool okd[2] = {((unsigned)d0 < (unsigned)D) && ((unsigned)ld < (unsigned)kTD),
+                             ((unsigned)(d0 + 1) < (unsigned)D) && ((unsigned)(ld + 1) < (unsigned)kTD)};
+        double *t0 = tile + ((lh * kTW + lw) * kTD + ld) * RW;
+        if constexpr (NCH > 0) {
+            if (sub < NCH) {
+#pragma unroll
+                for (int kk = 0; kk < 8; ++kk) {
+                    const int kd = kk & 1, kw = (kk >> 1) & 1, kh = kk >> 2;
+                    if (okd[kd] && okw[kw] && okh[kh] && acc[kk] != 0.0f)
+                        __hip_atomic_fetch_add(t0 + ((kh * kTW + kw) * kTD + kd) * RW + sub, (double)acc[kk], __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        }
+        if (sdf_lane && okd[mkd] && okw[mkw] && okh[mkh] && sacc != 0.0f)
+            __hip_atomic_fetch_add(t0 + moff, (double)sacc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] = 0.0f;
+        sacc = 0.0f;
+    };
+    for (int i0 = gb; i0 < ge; i0 += U) {
+        bool ok[U];
+        float v[U];
+        float4 ta[U], tb[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = i0 + u;
+            ok[u] = i < ge;
+            if (ok[u]) {
+                const float *r = b.rec + (size_t)i * RECF;
+                if constexpr (NB > 0) v[u] = (sub < NCH) ? r[sub / NB] * rb_sh_one(sub % NB, r[3], r[4], r[5]) : 0.0f;
+                else v[u] = (b.dbg & 16) ? 0.0f : r[sub];
+                ta[u] = *(const float4 *)(r + (RECF - 8));
+                tb[u] = *(const float4 *)(r + (RECF - 4));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (!ok[u] || (b.dbg & 1)) continue;
+            const int pack = __float_as_int(ta[u].y);
+            if (pack != cur || !merge) {
+                if (cur >= 0) flush();
+                cur = pack;
+            }
+            const float fh[2] = {1.0f - ta[u].z, ta[u].z}, fw[2] = {1.0f - ta[u].w, ta[u].w}, fd[2] = {1.0f - tb[u].x, tb[u].x};
+            if constexpr (NCH > 0) {
+                if (sub < NCH) {
+                    const float fdfw[2][2] = {{fd[0] * fw[0], fd[0] * fw[1]}, {fd[1] * fw[0], fd[1] * fw[1]}};
+#pragma unroll
+                    for (int kk = 0; kk < 8; ++kk) acc[kk] = fmaf(fdfw[kk & 1][(kk >> 1) & 1] * fh[kk >> 2], v[u], acc[kk]);
+                }
+            }
+            if (sdf_lane) {
+                // d L / d sdf corner = ds W_k + qz dW_k/dd + qx dW_k/dw + qy dW_k/dh
+                const float fds = fd[mkd], fws = fw[mkw], fhs = fh[mkh];
+                const float Wk = (fds * fws) * fhs;
+                const float dWd = (mkd ? 1.0f : -1.0f) * (fws * fhs);
+                const float dWw = (mkw ? 1.0f : -1.0f) * (fds * fhs);
+                const float dWh = (mkh ? 1.0f : -1.0f) * (fds * fws);
+                sacc += fmaf(Wk, ta[u].x, fmaf(dWd, tb[u].w, fmaf(dWw, tb[u].y, dWh * tb[u].z)));
+            }
+        }
+    }
+    if (cur >= 0) flush();
+    __syncthreads();
+    if (b.dbg & 2) return;
+    // flush.  Feature rows: RECF lanes per voxel row, consecutive groups = consecutive d (contiguous rows in HBM).
+    if constexpr (NCH > 0) {
+        if (g_feat_vol) {
+            for (int r = grp; r < kTileVox; r += NG) {
+                const int rd = r % kTD, rw = (r / kTD) % kTW, rh = r / (kTD * kTW);
+                const int h = oh + rh, w = ow + rw, d = od + rd;
+                if (h < H && w < W && d < D && sub < NCH) {
+                    const float val = (float)tile[r * RW + sub];
+                    if (val != 0.0f) unsafeAtomicAdd(g_feat_vol + ((size_t)(h * W + w) * D + d) * NF + sub, val);
+                }
+            }
+        }
+    }
+    if (g_sdf_vol) {   // the sdf column: consecutive lanes = consecutive d
+        for (int r = threadIdx.x; r < kTileVox; r += NT) {
+            const int rd = r % kTD, rw = (r / kTD) % kTW, rh = r / (kTD * kTW);
+            const int h = oh + rh, w = ow + rw, d = od + rd;
+            if (h < H && w < W && d < D) {
+                const float val = (float)tile[r * RW + NCH];
+                if (val != 0.0f) unsafeAtomicAdd(g_sdf_vol + (size_t)(h * W + w) * D + d, val);
+            }
+        }
+    }
 }
-template <int NB, int NT>
-__global__ __launch_bounds__(NT) void rb_brick_sh_kernel(RbBin b, float *__restrict__ g_sdf_vol, float *__restrict__ g_feat_vol,
-                                                         float *__restrict__ g_inv_s, int H, int W, int D) {
-    constexpr int NF = so_sh_stride(NB);
-#include "render_bwd_brick_body.h"
-}
+template <class ROW>
+using rb_brick_row = so_row<ROW::NF, false, ROW::NB>;
 
 inline size_t rb_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -315,7 +910,7 @@ inline size_t rb_bricks(const so_render_args &a, RbBin *b) {
 }
 
 // workspace carve-up; returns the total size (base may be NULL to size only)
-template <int NF, int NB = 0>
+template <class ROW>
 size_t rb_layout(const so_render_args &a, int chunk, char *base, RbBin *out, int *max_items) {
     RbBin b;
     const size_t nb = rb_bricks(a, &b);
@@ -331,7 +926,7 @@ size_t rb_layout(const so_render_args &a, int chunk, char *base, RbBin *out, int
     b.cursor = (int *)(base + off); off = rb_align(off + nb * kShards * 4);
     b.blk_tot = (int2 *)(base + off); off = rb_align(off + ((nb + 1023) / 1024) * 8);
     b.items = (int4 *)(base + off); off = rb_align(off + mi * 16);
-    b.rec = (float *)(base + off); off = rb_align(off + total * RbRec<NF, NB>::RECF * 4);
+    b.rec = (float *)(base + off); off = rb_align(off + total * RbRec<ROW>::RECF * 4);
     if (out) *out = b;
     if (max_items) *max_items = (int)mi;
     return off;
@@ -350,44 +945,31 @@ inline bool rb_in_range(const so_render_args &a) {
            (size_t)a.n_rays * a.n_samples < ((size_t)1 << 31);
 }
 
-template <int NF, bool BF16, bool BIN, int MK, int NB = 0, bool MASKED = false>
+template <class ROW, int M, int WPR, bool BIN, int MK>
+void launch_ray_kernel(const so_render_bwd_args &ba, const RbBin &bin, hipStream_t st) {
+    const int blocks = WPR == 4 ? ba.fwd.n_rays : (ba.fwd.n_rays + 3) / 4;
+    hipLaunchKernelGGL((render_bwd_kernel<ROW, M, WPR, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin);
+}
+
+template <class ROW, bool BIN, int MK>
 int launch_ray(const so_render_bwd_args &ba, const RbBin &bin, hipStream_t st) {
-    const int S = ba.fwd.n_samples;
-    const int m = (S + 63) / 64;
-    if (m >= 3) {   // four waves per ray: M = ceil(m / 4) steps per wave
-        const int blocks = ba.fwd.n_rays;
-#define SO_L(MM)                                                                                                        \
-    do {                                                                                                                \
-        if constexpr (MASKED) hipLaunchKernelGGL((render_ns_bwd_kernel<NF, MM, 4, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin); \
-        else if constexpr (NB > 0) hipLaunchKernelGGL((render_bwd_sh_kernel<NB, MM, 4, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin); \
-        else hipLaunchKernelGGL((render_bwd_kernel<NF, BF16, MM, 4, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin);  \
-    } while (0)
-        if (m <= 4) SO_L(1);
-        else SO_L(2);
-#undef SO_L
-    } else {
-        const int blocks = (ba.fwd.n_rays + 3) / 4;
-#define SO_L(MM)                                                                                                        \
-    do {                                                                                                                \
-        if constexpr (MASKED) hipLaunchKernelGGL((render_ns_bwd_kernel<NF, MM, 1, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin); \
-        else if constexpr (NB > 0) hipLaunchKernelGGL((render_bwd_sh_kernel<NB, MM, 1, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin); \
-        else hipLaunchKernelGGL((render_bwd_kernel<NF, BF16, MM, 1, BIN, MK>), dim3(blocks), dim3(256), 0, st, ba, bin);  \
-    } while (0)
-        if (m <= 1) SO_L(1);
-        else SO_L(2);
-#undef SO_L
-    }
+    const int m = (ba.fwd.n_samples + 63) / 64;
+    if (m <= 1) launch_ray_kernel<ROW, 1, 1, BIN, MK>(ba, bin, st);
+    else if (m == 2) launch_ray_kernel<ROW, 2, 1, BIN, MK>(ba, bin, st);
+    else if (m <= 4) launch_ray_kernel<ROW, 1, 4, BIN, MK>(ba, bin, st);   // four waves per ray: ceil(m / 4) steps per wave
+    else launch_ray_kernel<ROW, 2, 4, BIN, MK>(ba, bin, st);
     return so_launch_status();
 }
 
-template <int NF, bool BF16, int MK, int NB = 0, bool MASKED = false>
-int launch_mk(const so_render_bwd_args &ba, hipStream_t st) {
+// the mapping kind picks the instances of the counting pass, of the cell (sample_cell) and nothing else
+template <class ROW, int MK>
+int launch_bwd(const so_render_bwd_args &ba, hipStream_t st) {
     const so_render_args &a = ba.fwd;
     const bool binned = ba.scatter_ws != nullptr && rb_in_range(a) && (ba.g_sdf_vol || ba.g_feat_vol);
-    if (!binned) return launch_ray<NF, BF16, false, MK, NB, MASKED>(ba, RbBin{}, st);
+    if (!binned) return launch_ray<ROW, false, MK>(ba, RbBin{}, st);
     RbBin bin;
     int max_items = 0;
-    const size_t need = rb_layout<NF, NB>(a, rb_chunk(), (char *)ba.scatter_ws, &bin, &max_items);
+    const size_t need = rb_layout<ROW>(a, rb_chunk(), (char *)ba.scatter_ws, &bin, &max_items);
     bin.dbg = rb_env_int("SELFOCC_RB_DBG", 0);
     SO_REQUIRE(ba.scatter_ws_bytes >= need, "render_bwd: scatter_ws holds %llu bytes, selfocc_render_bwd_ws_bytes() asks for %llu",
                (unsigned long long)ba.scatter_ws_bytes, (unsigned long long)need);
@@ -399,49 +981,15 @@ int launch_mk(const so_render_bwd_args &ba, hipStream_t st) {
                        dim3(kCountWaves * 64), 0, st, a, bin);
     hipLaunchKernelGGL(rb_scan1_kernel, dim3(sblocks), dim3(1024), 0, st, bin);
     hipLaunchKernelGGL(rb_scan2_kernel, dim3(sblocks), dim3(1024), 0, st, bin);
-    if (int rc = launch_ray<NF, BF16, true, MK, NB, MASKED>(ba, bin, st)) return rc;
+    if (int rc = launch_ray<ROW, true, MK>(ba, bin, st)) return rc;
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
-    const size_t lds = (size_t)kTileVox * RbRec<NF, NB>::RW * 8;
-    if constexpr (NB > 0) {
-        static const hipError_t attr_sh = hipFuncSetAttribute((const void *)rb_brick_sh_kernel<NB, 512>,
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)attr_sh;
-        hipLaunchKernelGGL((rb_brick_sh_kernel<NB, 512>), dim3(max_items), dim3(512), lds, st, bin, ba.g_sdf_vol, ba.g_feat_vol,
-                           ba.g_inv_s, H, W, D);
-    } else {
-        // 512 threads per item (SELFOCC_RB_THREADS chose among 256 / 512 / 1024 while the kernel was tuned: 512 won at every shape)
-        static const hipError_t attr = hipFuncSetAttribute((const void *)rb_brick_kernel<NF, 512>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)attr;
-        hipLaunchKernelGGL((rb_brick_kernel<NF, 512>), dim3(max_items), dim3(512), lds, st, bin, ba.g_sdf_vol, ba.g_feat_vol,
-                           ba.g_inv_s, H, W, D);
-    }
+    const size_t lds = (size_t)kTileVox * RbRec<ROW>::RW * 8;
+    // 512 threads per item (SELFOCC_RB_THREADS chose among 256 / 512 / 1024 while the kernel was tuned: 512 won at every shape)
+    const auto brick = rb_brick_kernel<rb_brick_row<ROW>, 512>;
+    static const hipError_t attr = hipFuncSetAttribute((const void *)brick, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)attr;
+    hipLaunchKernelGGL(brick, dim3(max_items), dim3(512), lds, st, bin, ba.g_sdf_vol, ba.g_feat_vol, ba.g_inv_s, H, W, D);
     return so_launch_status();
-}
-
-// the mapping kind picks the instances ('linear_upscale' is built for the widths of the forward's upscale route)
-template <int NF, bool BF16>
-int launch_m(const so_render_bwd_args &ba, hipStream_t st) {
-    if (ba.fwd.map.kind == SO_MAP_UPSCALE) {
-        if constexpr (NF == 24 && BF16) {
-            SO_REQUIRE(false, "the 'linear_upscale' mapping is built for n_rgb + n_sem = 0, 3, 8 and float32 24 (got bfloat16 24)");
-        } else {
-            return launch_mk<NF, BF16, SO_MAP_UPSCALE>(ba, st);
-        }
-    }
-    return launch_mk<NF, BF16, SO_MAP_LINEAR>(ba, st);
-}
-
-template <int NF>
-int launch_ns(const so_render_bwd_args &ba, hipStream_t st) {
-    if (ba.fwd.map.kind == SO_MAP_UPSCALE) return launch_mk<NF, false, SO_MAP_UPSCALE, 0, true>(ba, st);
-    return launch_mk<NF, false, SO_MAP_LINEAR, 0, true>(ba, st);
-}
-
-template <int NB>
-int launch_sh(const so_render_bwd_args &ba, hipStream_t st) {
-    if (ba.fwd.map.kind == SO_MAP_UPSCALE) return launch_mk<so_sh_stride(NB), false, SO_MAP_UPSCALE, NB>(ba, st);
-    return launch_mk<so_sh_stride(NB), false, SO_MAP_LINEAR, NB>(ba, st);
 }
 
 }  // namespace
@@ -452,19 +1000,9 @@ extern "C" size_t selfocc_render_bwd_ws_bytes(const so_render_bwd_args *args) {
     if (!args) return 0;
     const so_render_args &a = args->fwd;
     if (!rb_in_range(a) || a.n_rays <= 0 || a.n_samples <= 0) return 0;
-    if (so_sh_launch(a)) {   // the 64-byte record at every degree
-        if (a.n_sem != 0 || a.sh_deg < 0 || a.sh_deg > 2) return 0;
-        return a.sh_deg == 0 ? rb_layout<4, 1>(a, rb_chunk(), nullptr, nullptr, nullptr)
-                             : (a.sh_deg == 1 ? rb_layout<12, 4>(a, rb_chunk(), nullptr, nullptr, nullptr)
-                                              : rb_layout<28, 9>(a, rb_chunk(), nullptr, nullptr, nullptr));
-    }
-    if (a.n_sem == 1 || a.n_sem > 21 || a.n_sem < 0) return 0;   // not built (so_validate_render)
-    switch (a.n_rgb + a.n_sem == 0 ? 0 : (3 + a.n_sem + 3) & ~3) {   // the row width: 64-byte records up to 8 floats, 128-byte above
-        case 0: return rb_layout<0>(a, rb_chunk(), nullptr, nullptr, nullptr);
-        case 4: return rb_layout<4>(a, rb_chunk(), nullptr, nullptr, nullptr);
-        case 8: return rb_layout<8>(a, rb_chunk(), nullptr, nullptr, nullptr);
-        default: return rb_layout<24>(a, rb_chunk(), nullptr, nullptr, nullptr);
-    }
+    if (so_sh_launch(a) ? (a.n_sem != 0 || a.sh_deg < 0 || a.sh_deg > 2) : (a.n_sem == 1 || a.n_sem > 21 || a.n_sem < 0))
+        return 0;   // not built (so_validate_render)
+    return so_with_row(a, [&](auto row) { return rb_layout<decltype(row)>(a, rb_chunk(), nullptr, nullptr, nullptr); });
 }
 
 extern "C" int selfocc_render_bwd(const so_render_bwd_args *args, void *stream) {
@@ -475,22 +1013,5 @@ extern "C" int selfocc_render_bwd(const so_render_bwd_args *args, void *stream) 
     SO_REQUIRE(a.n_samples <= 64 * kMaxM, "render_bwd: n_samples must be <= %d", 64 * kMaxM);
     if (a.n_rays == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const int nf = a.n_rgb + a.n_sem;
-    const bool bf = a.feat_dtype == SO_DTYPE_BF16;
-    if (nf == 0) return launch_m<0, false>(ba, st);
-    if (so_sh_launch(a)) return a.sh_deg == 0 ? launch_sh<1>(ba, st) : (a.sh_deg == 1 ? launch_sh<4>(ba, st) : launch_sh<9>(ba, st));
-    if (nf == 3) {
-        SO_REQUIRE(a.feat_stride == 4, "n_rgb=3, n_sem=0 requires feat_stride == 4");
-        return bf ? launch_m<4, true>(ba, st) : launch_m<4, false>(ba, st);
-    }
-    // so_validate_render: n_sem in 2 .. 21, feat_stride = 3 + n_sem rounded up to 4, bfloat16 at 21 classes only
-    if (nf == 8) return launch_m<8, false>(ba, st);            // the shipped widths: rows without a pad channel
-    if (nf == 24) return bf ? launch_m<24, true>(ba, st) : launch_m<24, false>(ba, st);
-    switch (a.feat_stride) {                                   // any other class count: the masked family of its row width
-        case 8: return launch_ns<8>(ba, st);
-        case 12: return launch_ns<12>(ba, st);
-        case 16: return launch_ns<16>(ba, st);
-        case 20: return launch_ns<20>(ba, st);
-        default: return launch_ns<24>(ba, st);
-    }
+    return so_with_row_and_map(ba.fwd, [&](auto row, auto mk) { return launch_bwd<decltype(row), decltype(mk)::value>(ba, st); });
 }

@@ -6,7 +6,7 @@
 //   lookup of the SDF / colour / semantic volume (+ analytic gradient) -> NeuS alpha ->
 //   transmittance -> weights -> depth / acc / rgb / sem / max-depth.
 // No per-sample tensor touches HBM: launches that ask for the per-sample training outputs go to the sample-parallel
-// kernels of render_train.hip (dispatch_ps / dispatch_sh below).  Ray construction, the box collider and the bin edges are
+// kernels of render_train.hip (dispatch below).  Ray construction, the box collider and the bin edges are
 // those of ray_device.h, shared with render_train.hip and render_bwd.hip; the marches a kernel can run are `enum class March`.
 //
 // Mapping to the hardware: one ray per lane; in pixel-grid mode a 64-lane wavefront owns
@@ -15,17 +15,11 @@
 // The transmittance recurrence is then a per-lane scalar chain — no cross-lane scan is
 // needed on this path (render_bwd.hip, which must reverse the recurrence, is the kernel
 // that scans across lanes).
-#include "so_device.h"
-#include "sh_device.h"
+#include "render_row.h"
 #include "ray_device.h"
 
 // render_train.hip
-template <int NF, bool BF16>
 int so_render_fwd_samples(const so_render_args &a, hipStream_t st);
-template <int NB>
-int so_render_sh_samples(const so_render_args &a, hipStream_t st);
-template <int NF>
-int so_render_ns_samples(const so_render_args &a, hipStream_t st);
 
 namespace {
 
@@ -147,13 +141,11 @@ SO_DEVFN void so_gather_feat_interior(__amdgpu_buffer_rsrc_t rf, int W, int D, u
     }
 }
 
-// MK: the mapping kind (SO_MAP_LINEAR / SO_MAP_UPSCALE), a compile-time choice of so_locate_k
-// NB > 0: spherical-harmonics colour with NB basis functions (sh_device.h); NF is then the row stride of the coefficients
-// MASKED (the render_ns_* kernels): the row holds a.n_sem <= NF - 3 logits and up to three pad channels; SO_SEM_ON
-// (so_device.h) keeps a pad channel out of the soft-max and the outputs.  Unmasked it is the constant `true`.
-template <int NF, bool BF16, int MK = SO_MAP_LINEAR, int NB = 0, bool MASKED = false>
+// ROW: the feature row (render_row.h).  MK: the mapping kind (SO_MAP_LINEAR / SO_MAP_UPSCALE), a compile-time choice of so_locate_k
+template <class ROW, int MK>
 SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g) {
-    constexpr int NSEM = (NB == 0 && NF > 4) ? NF - 3 : 0;  // NF = 3 rgb (+1 pad) or 3 rgb + n_sem
+    constexpr int NF = ROW::NF, NB = ROW::NB, NSEM = ROW::NSEM;
+    constexpr bool BF16 = ROW::BF16, MASKED = ROW::MASKED;
     const int nsem = MASKED ? a.n_sem : NSEM;                // wave-uniform
     float Y[NB > 0 ? NB : 1];                   // the ray's basis: once, before the march
     if constexpr (NB > 0) so_sh_basis<NB>(g.dx, g.dy, g.dz, Y);
@@ -508,10 +500,12 @@ struct FastStep {
 
 // `geom()` returns the lane's ray; it is called once up front and again inside the (rare) canonical cell
 // fallback, so that origin / direction / far need not stay in registers across the march loop.
-template <int NF, bool BF16, bool STAGED = false, bool FACE_SAFE = false, bool MASKED = false, class GeomFn>
+template <class ROW, bool STAGED, bool FACE_SAFE, class GeomFn>
 SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool store = true,
                              float *lds = nullptr, int lane = 0, float *sem_lds = nullptr) {
-    constexpr int NSEM = NF > 4 ? NF - 3 : 0;
+    static_assert(ROW::NB == 0, "the fast march renders degree-0 relu colour");
+    constexpr int NF = ROW::NF, NSEM = ROW::NSEM;
+    constexpr bool BF16 = ROW::BF16, MASKED = ROW::MASKED;
     const int nsem = MASKED ? a.n_sem : NSEM;   // wave-uniform (see so_march_exact)
     // The staged 24-channel float32 kernel keeps its 21 semantic accumulators in LDS (sem_lds[k * 256 + thread];
     // read-modify-write of a lane-private slot; ds_add_f32 measured 5 x slower) instead of registers: at 2 waves / SIMD the 256-VGPR budget was 14 - 19 registers short and the spills
@@ -1108,20 +1102,21 @@ constexpr bool so_is_fast(March m) { return m == March::Fast || m == March::Fast
 constexpr bool so_is_skip(March m) { return m == March::Skip || m == March::SkipFaceSafe; }
 constexpr bool so_face_safe(March m) { return m == March::FastFaceSafe || m == March::SkipFaceSafe; }
 // the fast march with the wave's voxel neighbourhood staged in LDS (so_gather_feat_staged): pixel-grid launches only
-template <int NF, bool BF16>
-constexpr bool so_is_staged(March m) { return so_is_fast(m) && !BF16 && NF >= 4; }
+template <class ROW>
+constexpr bool so_is_staged(March m) { return so_is_fast(m) && !ROW::BF16 && ROW::NF >= 4; }
 
-template <int NF, bool BF16, March MODE, bool MASKED = false, class GeomFn>
+// a spherical-harmonics row has the canonical marches only
+template <class ROW, March MODE, class GeomFn>
 SO_DEVFN void so_march(const so_render_args &a, int ray, GeomFn geom) {
     if constexpr (MODE == March::CanonicalUpscale) {
-        so_march_exact<NF, BF16, SO_MAP_UPSCALE, 0, MASKED>(a, ray, geom(a));
+        so_march_exact<ROW, SO_MAP_UPSCALE>(a, ray, geom(a));
     } else if constexpr (so_is_skip(MODE)) {
-        static_assert(NF == 0, "skip marcher: SDF-only launches");
+        static_assert(ROW::NF == 0, "skip marcher: SDF-only launches");
         so_march_fast_ahead<so_face_safe(MODE)>(a, ray, geom);
     } else if constexpr (so_is_fast(MODE)) {
-        so_march_fast<NF, BF16, false, so_face_safe(MODE), MASKED>(a, ray, geom);
+        so_march_fast<ROW, false, so_face_safe(MODE)>(a, ray, geom);
     } else {
-        so_march_exact<NF, BF16, SO_MAP_LINEAR, 0, MASKED>(a, ray, geom(a));
+        so_march_exact<ROW, SO_MAP_LINEAR>(a, ray, geom(a));
     }
 }
 
@@ -1192,23 +1187,28 @@ SO_DEVFN TilePixel so_tile_pixel(int tiles_x, int tiles_y) {
     return {cam, tx * 16 + (wave & 1) * 8 + (lane & 7), ty * 16 + (wave >> 1) * 8 + (lane >> 3), wave, lane};
 }
 
-// explicit rays: one ray per thread, linear order.  The feature-carrying kernels ask for 2 waves / SIMD.
-template <int NF, bool BF16, March MODE>
-__global__ __launch_bounds__(256, (NF >= 8 ? 2 : 1)) void render_fwd_explicit(so_render_args a) {
+// The feature-carrying kernels of the degree-0 rows ask for 2 waves / SIMD.
+template <class ROW>
+constexpr int so_min_blocks() { return (ROW::NB == 0 && ROW::NF >= 8) ? 2 : 1; }
+
+// explicit rays: one ray per thread, linear order
+template <class ROW, March MODE>
+__global__ __launch_bounds__(256, so_min_blocks<ROW>()) void render_fwd_explicit(so_render_args a) {
     int ray = blockIdx.x * blockDim.x + threadIdx.x;
     if (ray >= a.n_rays) return;
     auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_explicit_ray(a, ray); };
-    so_march<NF, BF16, MODE>(a, ray, geom);
+    so_march<ROW, MODE>(a, ray, geom);
 }
 
-template <int NF, bool BF16, March MODE, bool MASKED = false>
+template <class ROW, March MODE>
 SO_DEVFN void pixgrid_body(const so_render_args &a, int tiles_x, int tiles_y) {
     const TilePixel p = so_tile_pixel(tiles_x, tiles_y);
     const int cam = p.cam, wave = p.wave, lane = p.lane;
     int ix = p.ix, iy = p.iy;
-    if constexpr (so_is_staged<NF, BF16>(MODE)) {
+    if constexpr (so_is_staged<ROW>(MODE)) {
         // every lane keeps marching (the LDS staging is a whole-wave operation): lanes beyond the
         // lattice edge shadow the nearest real pixel and only skip the final store
+        constexpr int NF = ROW::NF;
         __shared__ __attribute__((aligned(16))) float s_stage[4 * StageGeom<NF>::kWaveDwords];
         const bool real = (ix < a.nx) && (iy < a.ny);
         ix = min(ix, a.nx - 1); iy = min(iy, a.ny - 1);
@@ -1216,69 +1216,59 @@ SO_DEVFN void pixgrid_body(const so_render_args &a, int tiles_x, int tiles_y) {
         auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_pixel_ray(a, cam, ix, iy); };
         constexpr int NSEM_LDS = NF - 3 >= 16 ? NF - 3 : 0;          // so_march_fast::SEM_LDS
         __shared__ float s_sem[NSEM_LDS > 0 ? NSEM_LDS * 256 : 1];
-        so_march_fast<NF, BF16, true, so_face_safe(MODE), MASKED>(a, ray, geom, real, s_stage + wave * StageGeom<NF>::kWaveDwords, lane,
-                                                          s_sem + threadIdx.x);
+        so_march_fast<ROW, true, so_face_safe(MODE)>(a, ray, geom, real, s_stage + wave * StageGeom<NF>::kWaveDwords, lane,
+                                                     s_sem + threadIdx.x);
     } else {
         if (ix >= a.nx || iy >= a.ny) return;
         int ray = (cam * a.ny + iy) * a.nx + ix;
         auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_pixel_ray(a, cam, ix, iy); };
-        so_march<NF, BF16, MODE, MASKED>(a, ray, geom);
+        so_march<ROW, MODE>(a, ray, geom);
     }
 }
 
-template <int NF, bool BF16, March MODE>
-__global__ __launch_bounds__(256, (NF >= 8 ? 2 : 1)) void render_fwd_pixgrid(so_render_args a, int tiles_x, int tiles_y) {
-    pixgrid_body<NF, BF16, MODE>(a, tiles_x, tiles_y);
+template <class ROW, March MODE>
+__global__ __launch_bounds__(256, so_min_blocks<ROW>()) void render_fwd_pixgrid(so_render_args a, int tiles_x, int tiles_y) {
+    if constexpr (ROW::NB > 0) {
+        // A spherical-harmonics row keeps the spelling its kernels shipped with: the pixel map written out and the ray passed
+        // by value.  Through pixgrid_body the compiler commutes the operands of one scalar multiply and one add in these six
+        // kernels (the same instructions in another order); this way all of them stay the code they were.
+        const int b = blockIdx.x;
+        const int cam = b / (tiles_x * tiles_y);
+        const int tb = b - cam * tiles_x * tiles_y;
+        const int ty = tb / tiles_x, tx = tb - ty * tiles_x;
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        const int ix = tx * 16 + (wave & 1) * 8 + (lane & 7);
+        const int iy = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
+        if (ix >= a.nx || iy >= a.ny) return;
+        const int ray = (cam * a.ny + iy) * a.nx + ix;
+        so_march_exact<ROW, MODE == March::CanonicalUpscale ? SO_MAP_UPSCALE : SO_MAP_LINEAR>(a, ray, so_pixel_ray(a, cam, ix, iy));
+    } else {
+        pixgrid_body<ROW, MODE>(a, tiles_x, tiles_y);
+    }
 }
 // The skip marchers (bench.py's kernel) at 8 waves / SIMD need <= 64 VGPRs AND <= 80 SGPRs: a CU admits
 // floor(800 / (ceil(sgpr / 16) * 16 + 16)) blocks of 256 threads, 7 at 82 - 96 SGPRs although the compiler's occupancy says 8.
 // Left alone the allocator spends 84 (constants the rare canonical branch needs, hoisted); capped it fits in 80 without spilling.
 template <>
-__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<0, false, March::Skip>(
+__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<so_row<0, false>, March::Skip>(
     so_render_args a, int tiles_x, int tiles_y) {
-    pixgrid_body<0, false, March::Skip>(a, tiles_x, tiles_y);
+    pixgrid_body<so_row<0, false>, March::Skip>(a, tiles_x, tiles_y);
 }
 template <>
-__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<0, false, March::SkipFaceSafe>(
+__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<so_row<0, false>, March::SkipFaceSafe>(
     so_render_args a, int tiles_x, int tiles_y) {
-    pixgrid_body<0, false, March::SkipFaceSafe>(a, tiles_x, tiles_y);
+    pixgrid_body<so_row<0, false>, March::SkipFaceSafe>(a, tiles_x, tiles_y);
 }
 
-template <int NF, bool BF16, March MODE>
+template <class ROW, March MODE>
 int launch_fwd(const so_render_args &a, hipStream_t st) {
     if (a.ray_mode == SO_RAYS_EXPLICIT) {
         int blocks = (a.n_rays + 255) / 256;
-        hipLaunchKernelGGL((render_fwd_explicit<NF, BF16, MODE>), dim3(blocks), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((render_fwd_explicit<ROW, MODE>), dim3(blocks), dim3(256), 0, st, a);
     } else {
         int tiles_x = (a.nx + 15) / 16, tiles_y = (a.ny + 15) / 16;
         int blocks = tiles_x * tiles_y * a.n_cams;
-        hipLaunchKernelGGL((render_fwd_pixgrid<NF, BF16, MODE>), dim3(blocks), dim3(256), 0, st, a, tiles_x, tiles_y);
-    }
-    return so_launch_status();
-}
-
-// ---- any class count from 2 to 21: the marches above with MASKED = true, one family per row width --------------
-// NF = the row width (8, 12, 16, 20, 24), float32 rows; the class count a.n_sem in [NF - 6, NF - 3] is a launch argument.
-// Launches with 5 or 21 classes keep the kernels above.
-template <int NF, March MODE>
-__global__ __launch_bounds__(256, 2) void render_ns_explicit(so_render_args a) {
-    int ray = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ray >= a.n_rays) return;
-    auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_explicit_ray(a, ray); };
-    so_march<NF, false, MODE, true>(a, ray, geom);
-}
-template <int NF, March MODE>
-__global__ __launch_bounds__(256, 2) void render_ns_pixgrid(so_render_args a, int tiles_x, int tiles_y) {
-    pixgrid_body<NF, false, MODE, true>(a, tiles_x, tiles_y);
-}
-
-template <int NF, March MODE>
-int launch_ns(const so_render_args &a, hipStream_t st) {
-    if (a.ray_mode == SO_RAYS_EXPLICIT) {
-        hipLaunchKernelGGL((render_ns_explicit<NF, MODE>), dim3((a.n_rays + 255) / 256), dim3(256), 0, st, a);
-    } else {
-        int tiles_x = (a.nx + 15) / 16, tiles_y = (a.ny + 15) / 16;
-        hipLaunchKernelGGL((render_ns_pixgrid<NF, MODE>), dim3(tiles_x * tiles_y * a.n_cams), dim3(256), 0, st, a, tiles_x, tiles_y);
+        hipLaunchKernelGGL((render_fwd_pixgrid<ROW, MODE>), dim3(blocks), dim3(256), 0, st, a, tiles_x, tiles_y);
     }
     return so_launch_status();
 }
@@ -1294,91 +1284,37 @@ void so_launch_brickify(const so_render_args &a, hipStream_t st, int with_codes)
                        H, W, D, a, with_codes);
 }
 
-// the routes of dispatch_ps below; SO_FLAG_NO_FACE_SAFE (an A/B switch of the shipped widths) is ignored: the march is face-safe
-template <int NF>
-int dispatch_ns(const so_render_args &a, hipStream_t st) {
-    if (a.weights || a.ts || a.deltas || a.sdf || a.grad) return so_render_ns_samples<NF>(a, st);
-    if (a.map.kind == SO_MAP_UPSCALE) return launch_ns<NF, March::CanonicalUpscale>(a, st);
-    const bool fast = !(a.flags & SO_FLAG_EXACT) && a.jitter_mode == SO_JITTER_NONE &&
-                      a.map.h.size1 == 0.0f && a.map.w.size1 == 0.0f && a.map.d.size1 == 0.0f &&
-                      (long long)a.map.h.tot_len * a.map.w.tot_len < (1 << 24) && a.map.d.tot_len < (1 << 24);   // so_cell_index
-    if (!fast) return launch_ns<NF, March::Canonical>(a, st);
-    if (a.sdf_brick) so_launch_brickify(a, st, 0);
-    return launch_ns<NF, March::FastFaceSafe>(a, st);
+// the fast march needs g(t) affine in t (no jitter, single-segment axes, the linear mapping kind) and so_cell_index's 24 bits
+bool so_fast_eligible(const so_render_args &a) {
+    return !(a.flags & SO_FLAG_EXACT) && a.jitter_mode == SO_JITTER_NONE && a.map.kind == SO_MAP_LINEAR &&
+           a.map.h.size1 == 0.0f && a.map.w.size1 == 0.0f && a.map.d.size1 == 0.0f &&
+           (long long)a.map.h.tot_len * a.map.w.tot_len < (1 << 24) && a.map.d.tot_len < (1 << 24);
 }
 
-template <int NF, bool BF16>
-int dispatch_ps(const so_render_args &a, hipStream_t st) {
-    bool per_sample = a.weights || a.ts || a.deltas || a.sdf || a.grad;
-    // training API: the sample-parallel kernel of render_train.hip (a lane per sample, canonical arithmetic)
-    // (SO_FLAG_RAY_PER_LANE, the A/B route of rounds 2 - 4 through ray-per-lane per-sample kernels, is accepted and ignored
-    // since ABI v30: 48 instantiations nobody shipped)
-    if (per_sample) return so_render_fwd_samples<NF, BF16>(a, st);
+// the march of a launch without per-sample outputs.  Built per row: the degree-0 unmasked rows have every march, the masked
+// rows are always face-safe (SO_FLAG_NO_FACE_SAFE, an A/B switch of the shipped widths, is ignored), the spherical-harmonics
+// rows march canonically.
+// (SO_FLAG_RAY_PER_LANE, the A/B route of rounds 2 - 4 through ray-per-lane per-sample kernels, is accepted and ignored
+// since ABI v30: 48 instantiations nobody shipped)
+template <class ROW, int MK>
+int dispatch(const so_render_args &a, hipStream_t st) {
     // 'linear_upscale': the canonical march with the upscale mapping (no brick re-pack, no skip codes)
-    if (a.map.kind == SO_MAP_UPSCALE) {
-        if constexpr (NF == 24 && BF16) {
-            SO_REQUIRE(false, "the 'linear_upscale' mapping is built for n_rgb + n_sem = 0, 3, 8 and float32 24 (got bfloat16 24)");
-        } else {
-            return launch_fwd<NF, BF16, March::CanonicalUpscale>(a, st);
-        }
-    }
-    // the fast path needs g(t) affine in t: no jitter, single-segment axes, the linear mapping kind
-    bool fast = !(a.flags & SO_FLAG_EXACT) && a.jitter_mode == SO_JITTER_NONE && a.map.kind == SO_MAP_LINEAR &&
-                a.map.h.size1 == 0.0f && a.map.w.size1 == 0.0f && a.map.d.size1 == 0.0f &&
-                (long long)a.map.h.tot_len * a.map.w.tot_len < (1 << 24) && a.map.d.tot_len < (1 << 24);   // so_cell_index
-    if (fast) {
-        if (a.sdf_brick) {
-            so_launch_brickify(a, st, (NF == 0 && !(a.flags & SO_FLAG_NO_SKIP)) ? 1 : 0);
-        }
-        if constexpr (NF == 0) {
+    if constexpr (MK == SO_MAP_UPSCALE) return launch_fwd<ROW, March::CanonicalUpscale>(a, st);
+    else if constexpr (ROW::NB > 0) return launch_fwd<ROW, March::Canonical>(a, st);
+    else {
+        if (!so_fast_eligible(a)) return launch_fwd<ROW, March::Canonical>(a, st);
+        constexpr bool CAN_SKIP = ROW::NF == 0;
+        if (a.sdf_brick) so_launch_brickify(a, st, (CAN_SKIP && !(a.flags & SO_FLAG_NO_SKIP)) ? 1 : 0);
+        const bool face_safe = ROW::MASKED || !(a.flags & SO_FLAG_NO_FACE_SAFE);
+        if constexpr (CAN_SKIP) {
             if (a.sdf_brick && !(a.flags & (SO_FLAG_NO_SKIP | SO_FLAG_NO_AHEAD)))
-                return (a.flags & SO_FLAG_NO_FACE_SAFE) ? launch_fwd<0, false, March::Skip>(a, st) : launch_fwd<0, false, March::SkipFaceSafe>(a, st);
+                return face_safe ? launch_fwd<ROW, March::SkipFaceSafe>(a, st) : launch_fwd<ROW, March::Skip>(a, st);
         }
-        if (!(a.flags & SO_FLAG_NO_FACE_SAFE)) return launch_fwd<NF, BF16, March::FastFaceSafe>(a, st);
-        return launch_fwd<NF, BF16, March::Fast>(a, st);
+        if constexpr (!ROW::MASKED) {
+            if (!face_safe) return launch_fwd<ROW, March::Fast>(a, st);
+        }
+        return launch_fwd<ROW, March::FastFaceSafe>(a, st);
     }
-    return launch_fwd<NF, BF16, March::Canonical>(a, st);
-}
-
-// ---- spherical-harmonics colour (sh_deg > 0 or sh_act != relu): ray per lane, canonical march -------------------------------
-// The same thread <-> ray maps as render_fwd_explicit / render_fwd_pixgrid (an 8 x 8 pixel tile per wave).
-template <int NB, int MK>
-__global__ __launch_bounds__(256) void render_sh_explicit(so_render_args a) {
-    const int ray = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ray >= a.n_rays) return;
-    so_march_exact<so_sh_stride(NB), false, MK, NB>(a, ray, so_explicit_ray(a, ray));
-}
-
-template <int NB, int MK>
-__global__ __launch_bounds__(256) void render_sh_pixgrid(so_render_args a, int tiles_x, int tiles_y) {
-    // (written out: through so_tile_pixel the compiler commutes the operands of one scalar multiply and one add)
-    const int b = blockIdx.x;
-    const int cam = b / (tiles_x * tiles_y);
-    const int tb = b - cam * tiles_x * tiles_y;
-    const int ty = tb / tiles_x, tx = tb - ty * tiles_x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int ix = tx * 16 + (wave & 1) * 8 + (lane & 7);
-    const int iy = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (ix >= a.nx || iy >= a.ny) return;
-    const int ray = (cam * a.ny + iy) * a.nx + ix;
-    so_march_exact<so_sh_stride(NB), false, MK, NB>(a, ray, so_pixel_ray(a, cam, ix, iy));
-}
-
-template <int NB, int MK>
-int launch_sh(const so_render_args &a, hipStream_t st) {
-    if (a.ray_mode == SO_RAYS_EXPLICIT) {
-        hipLaunchKernelGGL((render_sh_explicit<NB, MK>), dim3((a.n_rays + 255) / 256), dim3(256), 0, st, a);
-    } else {
-        const int tiles_x = (a.nx + 15) / 16, tiles_y = (a.ny + 15) / 16;
-        hipLaunchKernelGGL((render_sh_pixgrid<NB, MK>), dim3(tiles_x * tiles_y * a.n_cams), dim3(256), 0, st, a, tiles_x, tiles_y);
-    }
-    return so_launch_status();
-}
-
-template <int NB>
-int dispatch_sh(const so_render_args &a, hipStream_t st) {
-    if (a.weights || a.ts || a.deltas || a.sdf || a.grad) return so_render_sh_samples<NB>(a, st);   // training API
-    return a.map.kind == SO_MAP_UPSCALE ? launch_sh<NB, SO_MAP_UPSCALE>(a, st) : launch_sh<NB, SO_MAP_LINEAR>(a, st);
 }
 
 }  // namespace
@@ -1457,11 +1393,11 @@ int so_validate_render(const so_render_args &a) {
         SO_REQUIRE(a.n_sem == 0, "sh_deg > 0 / sh_act = sigmoid with n_sem = %d semantic channels is not built (built: n_sem = 0)",
                    (int)a.n_sem);
         SO_REQUIRE(a.feat_dtype == SO_DTYPE_F32, "sh_deg > 0 / sh_act = sigmoid with a bfloat16 feature volume is not built (built: float32)");
-        SO_REQUIRE(a.feat_stride == ((n_coef + 3) & ~3), "sh_deg = %d reads %d coefficients: feat_stride must be %d (got %d)",
-                   (int)a.sh_deg, n_coef, (n_coef + 3) & ~3, (int)a.feat_stride);
+        SO_REQUIRE(a.feat_stride == so_sh_stride(n_coef / 3), "sh_deg = %d reads %d coefficients: feat_stride must be %d (got %d)",
+                   (int)a.sh_deg, n_coef, so_sh_stride(n_coef / 3), (int)a.feat_stride);
     }
     if (a.n_sem > 0 && !so_sh_launch(a)) {   // rows [r, g, b, logit_0 .. logit_{n_sem - 1}, pad]: n_sem = 2 .. 21
-        const int stride = (3 + a.n_sem + 3) & ~3;
+        const int stride = so_row_width(a.n_sem);
         SO_REQUIRE(a.n_sem != 1, "n_sem = 1 is not built (built: n_sem 0 and 2 .. 21): one class renders `acc`");
         SO_REQUIRE(a.n_sem <= 21, "n_sem = %d is not built (built: n_sem 0 and 2 .. 21): the binned backward record and the "
                    "32-lanes-per-sample brick kernel end at 24 channels", (int)a.n_sem);
@@ -1491,22 +1427,7 @@ extern "C" int selfocc_render_fwd(const so_render_args *args, void *stream) {
     if (so_validate_render(a)) return -1;
     if (a.n_rays == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    int nf = a.n_rgb + a.n_sem;
-    bool bf = a.feat_dtype == SO_DTYPE_BF16;
-    if (nf == 0) return dispatch_ps<0, false>(a, st);
-    if (so_sh_launch(a)) return a.sh_deg == 0 ? dispatch_sh<1>(a, st) : (a.sh_deg == 1 ? dispatch_sh<4>(a, st) : dispatch_sh<9>(a, st));
-    if (nf == 3) {
-        SO_REQUIRE(a.feat_stride == 4, "n_rgb=3, n_sem=0 requires feat_stride == 4");
-        return bf ? dispatch_ps<4, true>(a, st) : dispatch_ps<4, false>(a, st);
-    }
-    // so_validate_render: n_sem in 2 .. 21, feat_stride = 3 + n_sem rounded up to 4, bfloat16 at 21 classes only
-    if (nf == 8) return dispatch_ps<8, false>(a, st);          // the shipped widths: rows without a pad channel
-    if (nf == 24) return bf ? dispatch_ps<24, true>(a, st) : dispatch_ps<24, false>(a, st);
-    switch (a.feat_stride) {                                   // any other class count: the masked family of its row width
-        case 8: return dispatch_ns<8>(a, st);
-        case 12: return dispatch_ns<12>(a, st);
-        case 16: return dispatch_ns<16>(a, st);
-        case 20: return dispatch_ns<20>(a, st);
-        default: return dispatch_ns<24>(a, st);
-    }
+    // training API: the sample-parallel kernels of render_train.hip (a lane per sample, canonical arithmetic)
+    if (a.weights || a.ts || a.deltas || a.sdf || a.grad) return so_render_fwd_samples(a, st);
+    return so_with_row_and_map(a, [&](auto row, auto mk) { return dispatch<decltype(row), decltype(mk)::value>(a, st); });
 }

@@ -161,6 +161,8 @@ def test_render_forward_vs_float64_port(hip, n_rgb, n_sem, feat_dtype):
     parity_report(got, ref, label=f"upscale explicit C={1 + n_rgb + n_sem} {feat_dtype}")
     gp = render_rays(v, RaySet(img2lidar=pix.img2lidar.to(D0), nx=pix.nx, ny=pix.ny, sx=pix.sx, sy=pix.sy), cfg)
     parity_report({k: t[idx.to(D0)] for k, t in gp.items()}, ref, label=f"upscale pixel grid C={1 + n_rgb + n_sem} {feat_dtype}")
+    gt = render_rays(v, _dev(ex), cfg, per_sample=True)      # the sample-parallel kernel of the same row
+    parity_report({k: gt[k] for k in got}, ref, label=f"upscale per-sample launch C={1 + n_rgb + n_sem} {feat_dtype}")
     assert len(rmod._BRICK_WS) == n_ws                       # no brick re-pack for the upscale route
 
 

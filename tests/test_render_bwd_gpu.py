@@ -243,16 +243,27 @@ def test_render_backward_binned_vs_atomic_at_training_shape(hip, n_rgb, n_sem):
     assert abs(b[2].item() - a[2].item()) <= 1e-3 * abs(a[2].item()) + 1e-6
 
 
-@pytest.mark.parametrize("n_sem,S", [(0, 32), (21, 100), (21, 300)])
-def test_render_backward_binned_vs_atomic_bf16_features(hip, n_sem, S):
+@pytest.mark.parametrize("n_sem,S,mapping", [(0, 32, 'linear'), (21, 100, 'linear'), (21, 300, 'linear'), (0, 48, 'linear_upscale')],
+                         ids=["0-32", "21-100", "21-300", "0-48-linear_upscale"])
+def test_render_backward_binned_vs_atomic_bf16_features(hip, n_sem, S, mapping):
     """bfloat16 STORAGE of the feature volume (gradients stay float32): the brick-binned scatter and the per-sample atomics
-    agree at every instantiation the bf16 launch table holds (4 / 24 channels; one and four waves per ray, M = 1 / 2)."""
-    vol = sy.make_volume("cfg1", n_rgb=3, n_sem=n_sem, feat_dtype=torch.bfloat16, seed=5, noise=0.02).to(D0)
-    ex = sy.explicit_rays(sy.make_rays("cfg1", seed=5))
+    agree at every instantiation the bf16 launch table holds (4 / 24 channels; one and four waves per ray, M = 1 / 2; the
+    4-channel row under 'linear_upscale' too, on the scene of tests/test_mapping_upscale_gpu.py — bfloat16 24 has no such kernels)."""
+    if mapping == 'linear_upscale':
+        import test_mapping_upscale_gpu as up
+        from selfocc_amd.mapping import GridMeterMapping
+        from selfocc_amd.render import RenderConfig
+        vol = up._volume(GridMeterMapping(**up.HEAD_UPSCALE), 3, n_sem, torch.bfloat16, seed=5).to(D0)
+        ex = up._candidate_rays(500, seed=5)
+        make_cfg = lambda: RenderConfig(aabb=up.AABB, n_samples=S, inv_s=12.0)
+    else:
+        vol = sy.make_volume("cfg1", n_rgb=3, n_sem=n_sem, feat_dtype=torch.bfloat16, seed=5, noise=0.02).to(D0)
+        ex = sy.explicit_rays(sy.make_rays("cfg1", seed=5))
+        make_cfg = lambda: sy.make_render_config("cfg1", inv_s=12.0)
     rg = RaySet(origins=ex.origins.to(D0), dirs=ex.dirs.to(D0), dir_norm=ex.dir_norm.to(D0))
     res = {}
     for mode in ("atomic", "binned"):
-        cfg = sy.make_render_config("cfg1", inv_s=12.0)
+        cfg = make_cfg()
         cfg.n_samples, cfg.bwd_scatter = S, mode
         inv_s = torch.tensor([12.0], device=D0, requires_grad=True)
         sdf = vol.sdf.detach().clone().requires_grad_(True)

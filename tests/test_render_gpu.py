@@ -152,6 +152,13 @@ def test_cfg1_pixel_grid_vs_oracle(hip, n_rgb, n_sem, feat_dtype, sample_pos, ex
         from dataclasses import replace
         got_l = render_rays(vol.to(d), rg, replace(cfg, ray_per_lane=True), per_sample=True, want_grad_samples=True)
         assert torch.equal(got_l['weights'], got['weights']) and torch.equal(got_l['sdf'], got['sdf'])
+    # and the same rays given explicitly: the one-ray-per-thread kernel of the row and mode (direct gathers, no LDS staging)
+    ex = sy.explicit_rays(rays)
+    got_x = render_rays(vol.to(d), RaySet(origins=ex.origins.to(d), dirs=ex.dirs.to(d), dir_norm=ex.dir_norm.to(d)), cfg)
+    if exact is True:
+        _cmp(got_x, ref, keys=[k for k in per_ray if k in got_x])
+    else:
+        parity_report(got_x, ref, label=f"cfg1 eval launch {exact}, explicit rays", strict=(exact is False), **loose)
 
 
 def test_explicit_rays_and_jitter(hip):

@@ -1,7 +1,6 @@
 """CPU: any semantic class count from 2 to 21 — the row-width table, the host-only accept / refuse list of the
 C boundary, the backward workspace size, the construction rules of SDFField, the compiler's scratch report of the new
 forward kernels, and the oracle's indifference to what the pad channels hold."""
-import os
 import shutil
 
 import pytest
@@ -11,7 +10,8 @@ import oracle
 from selfocc_amd import abi, synthetic as sy
 from selfocc_amd.render import SDFVolume
 from nsem_cases import CLASS_COUNTS, CONTROLS, stride, volume
-from test_sh_cpu import HIPCC, ROOT, SMALL_MAPPING, _args, _resources
+from kernel_report import HIPCC, kernels_of
+from test_sh_cpu import SMALL_MAPPING, _args
 
 
 def test_feat_width_is_the_row_rounded_up_to_four_floats():
@@ -143,14 +143,17 @@ def test_the_oracle_ignores_the_pad_channels(n_sem):
 
 # ---- compiler report: the new forward kernels keep nothing in scratch -----------------------------------------------------------
 @pytest.mark.skipif(not shutil.which(HIPCC), reason="hipcc not present")
-@pytest.mark.parametrize("src,name,count", [("render_fwd.hip", "render_ns_explicit", 15), ("render_fwd.hip", "render_ns_pixgrid", 15),
-                                            ("render_train.hip", "render_ns_samples_kernel", 30)])
-def test_masked_forward_kernels_use_no_scratch(src, name, count):
+@pytest.mark.parametrize("src,base,count", [("render_fwd.hip", "render_fwd_explicit", 15), ("render_fwd.hip", "render_fwd_pixgrid", 15),
+                                            ("render_train.hip", "render_fwd_samples_kernel", 30)],
+                         # the ids these cases have always had: the names of the kernels before they became instances of `base`
+                         ids=["render_fwd.hip-render_ns_explicit-15", "render_fwd.hip-render_ns_pixgrid-15",
+                              "render_train.hip-render_ns_samples_kernel-30"])
+def test_masked_forward_kernels_use_no_scratch(src, base, count):
     """eval forward: 5 row widths x (canonical, canonical under 'linear_upscale', fast face-safe), explicit rays and pixel grid;
     training forward: 5 row widths x 3 waves-per-ray forms x 2 mapping kinds"""
-    table = _resources(os.path.join(ROOT, "selfocc_amd", "csrc", src))
-    hits = {k: v for k, v in table.items() if name in k}
-    assert len(hits) == count, sorted(table)
-    for k, r in hits.items():
-        assert r["ScratchSize"] == 0, (k, r)
-        assert r["VGPRs"] + r.get("AGPRs", 0) <= 256, (k, r)
+    hits = kernels_of(src, base, lambda r: r.masked)
+    assert len(hits) == count, [k.name for k in hits]
+    assert sorted({k.row.nf for k in hits}) == [8, 12, 16, 20, 24] and not any(k.row.bf16 or k.row.nb for k in hits)
+    for k in hits:
+        assert k.res["ScratchSize"] == 0, k
+        assert k.res["VGPRs"] + k.res.get("AGPRs", 0) <= 256, k

@@ -4,22 +4,24 @@ Every volume here has 64.0 in its pad channels (nsem_cases.volume); the logits a
 soft-max, a sum or a gradient row would take it over.  Class counts 2, 4, 6, 11, 16, 17, 20 cover pad sizes 0 - 3 and both ends
 of every row width (8, 12, 16, 20, 24 floats); 5 and 21 are the controls that run the kernels of every earlier version.
 
-Which case reaches which built route (NF = the row width):
-  render_ns_pixgrid / render_ns_explicit <NF, Canonical>         test_exact_launches_vs_oracle (every class count),
+Which case reaches which built route.  The kernels are the render templates instantiated on a masked row, R = so_row<NF, false,
+0, true> of csrc/render_row.h (NF = the row width):
+  render_fwd_pixgrid / render_fwd_explicit <R, Canonical>        test_exact_launches_vs_oracle (every class count),
                                                                  test_single_jitter_..., test_two_segment_mapping_...,
                                                                  test_rays_entering_from_outside_the_box[exact]
-  render_ns_pixgrid / render_ns_explicit <NF, CanonicalUpscale>  test_linear_upscale_mapping_vs_float64_port
-  render_ns_explicit <NF, FastFaceSafe> (direct gathers)         test_default_flags_vs_oracle (explicit launch)
-  render_ns_pixgrid <NF, FastFaceSafe> (LDS-staged block,        test_default_flags_vs_oracle (pixel grid), test_sample_at_mid_...,
+  render_fwd_pixgrid / render_fwd_explicit <R, CanonicalUpscale> test_linear_upscale_mapping_vs_float64_port, ..._at_every_row_width
+  render_fwd_explicit <R, FastFaceSafe> (direct gathers)         test_default_flags_vs_oracle (explicit launch)
+  render_fwd_pixgrid <R, FastFaceSafe> (LDS-staged block,        test_default_flags_vs_oracle (pixel grid), test_sample_at_mid_...,
       semantic sums in LDS at NF >= 20)                          test_rays_entering_...[fast] (clamped / zero-padded gathers),
                                                                  test_launch_large_enough_for_the_brick_repack (with the brick)
-  render_ns_samples_kernel <NF, 1 / 2 / 4 waves per ray, linear> test_training_forward_... (S = 32 / 100 / 256)
-  render_ns_samples_kernel <NF, ., upscale>                      test_linear_upscale_mapping_vs_float64_port (per-sample launch)
-  render_ns_bwd_kernel <NF, M, WPR, atomic / binned, linear>     test_backward_vs_float64_autograd (S = 32: M 1, WPR 1; S = 100: M 2,
+  render_fwd_samples_kernel <R, 1 / 2 / 4 waves per ray, linear> test_training_forward_... (S = 32 / 100 / 256)
+  render_fwd_samples_kernel <R, ., upscale>                      test_linear_upscale_mapping_vs_float64_port (per-sample launch)
+  render_bwd_kernel <R, M, WPR, atomic / binned, linear>         test_backward_vs_float64_autograd (S = 32: M 1, WPR 1; S = 100: M 2,
                                                                  WPR 1), test_backward_binned_vs_atomic_at_the_auto_threshold
                                                                  (S = 256: M 1, WPR 4)
-  render_ns_bwd_kernel <NF, ., ., ., upscale>                    test_linear_upscale_mapping_vs_float64_port (binned against atomic)
-  rb_brick_kernel <12 / 16 / 20> (new widths; 8 / 24 shared)     every binned case above
+  render_bwd_kernel <R, ., ., ., upscale>                        test_linear_upscale_mapping_vs_float64_port (binned against atomic)
+  rb_brick_kernel <so_row<12 / 16 / 20, false>> (the unmasked    every binned case above
+      row of the width; 8 / 24 shared with 5 / 21 classes)
   SDFField / NeuSHead with 20 (and 6) classes                    test_head_with_20_classes_*, test_fused_and_op_by_op_field_routes_agree
 """
 import os
@@ -142,7 +144,7 @@ def test_two_segment_mapping_takes_the_canonical_route(hip):
     rays = RaySet(origins=o.contiguous(), dirs=dirs.contiguous(), dir_norm=torch.ones(500))
     cfg = RenderConfig(aabb=(-15.0, -15.0, -1.0, 15.0, 15.0, 7.0), n_samples=48, inv_s=5.0)
     ref = oracle.render_fwd(vol, rays, cfg, per_sample=True, want_grad_samples=True)
-    got = render_rays(vol.to(D0), _dev(rays), cfg)                          # eval launch: render_ns_explicit<20, Canonical>
+    got = render_rays(vol.to(D0), _dev(rays), cfg)                          # eval launch: render_fwd_explicit<so_row<20, false, 0, true>, Canonical>
     _cmp(got, ref, keys=list(got))
     _sem_sums_to_acc(ref, got, n_sem)
     got_t = render_rays(vol.to(D0), _dev(rays), cfg, per_sample=True, want_grad_samples=True)
@@ -192,15 +194,14 @@ def test_launch_large_enough_for_the_brick_repack(hip, n_sem):
     _sem_sums_to_acc(ref, got, n_sem)
 
 
-def test_linear_upscale_mapping_vs_float64_port(hip):
+def _upscale_vs_float64_port(n_sem):
     """scene, rays and the off-face ray rule of tests/test_mapping_upscale_gpu.py (the C oracle has no upscale mapping: the
     reference is the float64 port); eval launch on explicit rays and pixel grid, the per-sample launch, binned against atomic"""
     import test_mapping_upscale_gpu as up
     from selfocc_amd.mapping import GridMeterMapping
-    n_sem = 6
     m = GridMeterMapping(**up.HEAD_UPSCALE)
     vol = fill_pad(up._volume(m, 3, n_sem))
-    assert vol.feat.shape[-1] == 12
+    assert vol.feat.shape[-1] == stride(n_sem)
     cfg = RenderConfig(aabb=up.AABB, n_samples=64, inv_s=20.0, sample_pos=abi.SAMPLE_AT_START)
     pix = up._pixel_rays()
     ex, idx = up._off_faces(m, sy.explicit_rays(pix), cfg, 1e-3)
@@ -211,12 +212,12 @@ def test_linear_upscale_mapping_vs_float64_port(hip):
     ref = {k: v.float() for k, v in ref.items()}
     v = vol.to(D0)
     got = render_rays(v, _dev(ex), cfg)
-    parity_report(got, ref, label="upscale explicit n_sem=6")
+    parity_report(got, ref, label=f"upscale explicit n_sem={n_sem}")
     _sem_sums_to_acc(ref, got, n_sem)
     gp = render_rays(v, _dev(pix), cfg)
-    parity_report({k: t[idx.to(D0)] for k, t in gp.items()}, ref, label="upscale pixel grid n_sem=6")
+    parity_report({k: t[idx.to(D0)] for k, t in gp.items()}, ref, label=f"upscale pixel grid n_sem={n_sem}")
     gt = render_rays(v, _dev(ex), cfg, per_sample=True)
-    parity_report({k: gt[k] for k in got}, ref, label="upscale per-sample launch n_sem=6")
+    parity_report({k: gt[k] for k in got}, ref, label=f"upscale per-sample launch n_sem={n_sem}")
     res = {}
     for mode in ("atomic", "binned"):
         cfg.bwd_scatter = mode
@@ -225,9 +226,22 @@ def test_linear_upscale_mapping_vs_float64_port(hip):
         out = render_rays_autograd(SDFVolume(m, sdf, feat, 3, n_sem), inv_s, _dev(ex), cfg)
         (out['depth'].mean() + out['rgb'].mean() + out['sem'].square().mean() + out['sdf'].abs().mean()).backward()
         res[mode] = (sdf.grad, feat.grad)
-        assert feat.grad[..., 3 + n_sem:].abs().max() == 0 and feat.grad[..., 3:3 + n_sem].abs().max() > 0
+        assert feat.grad[..., 3:3 + n_sem].abs().max() > 0
+        if stride(n_sem) > 3 + n_sem:
+            assert feat.grad[..., 3 + n_sem:].abs().max() == 0
     for a, b in zip(res["atomic"], res["binned"]):
         assert _rel_l2(b.double(), a.double()) < 1e-5 and (b - a).abs().max() <= 1e-4 * a.abs().max()
+
+
+def test_linear_upscale_mapping_vs_float64_port(hip):
+    """6 classes: the 12-float masked row"""
+    _upscale_vs_float64_port(6)
+
+
+@pytest.mark.parametrize("n_sem", [4, 11, 17, 20, 5])
+def test_linear_upscale_mapping_at_every_row_width(hip, n_sem):
+    """one class count for each other masked row width (8, 16, 20, 24 floats) and the 5-class control (the unmasked 8-float row)"""
+    _upscale_vs_float64_port(n_sem)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

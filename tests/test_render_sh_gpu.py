@@ -241,17 +241,22 @@ def test_sh_render_backward_vs_float64_autograd(hip, deg, act, jitter, sample_po
     assert e_s < 5e-2, f"d/d inv_s rel {e_s:.3e} ({inv_s.grad.item()} vs {inv_s64.grad.item()})"
 
 
-@pytest.mark.parametrize("scatter", ["atomic", "binned"])
-def test_sh_render_backward_under_the_upscale_mapping(hip, scatter):
-    vol, ex, cfg, t_rand, bk, G, out, sdf_p, feat_p, inv_s = _backward_case(2, 'relu', abi.JITTER_NONE, 0, 100, scatter, upscale=True)
+# (the degree-2 cases keep the ids they had while they were the only ones)
+@pytest.mark.parametrize("deg,act,scatter", [(2, 'relu', "atomic"), (2, 'relu', "binned"), (1, 'relu', "atomic"), (1, 'relu', "binned"),
+                                             (0, 'sigmoid', "atomic"), (0, 'sigmoid', "binned")],
+                         ids=["atomic", "binned", "1-relu-atomic", "1-relu-binned", "0-sigmoid-atomic", "0-sigmoid-binned"])
+def test_sh_render_backward_under_the_upscale_mapping(hip, deg, act, scatter):
+    vol, ex, cfg, t_rand, bk, G, out, sdf_p, feat_p, inv_s = _backward_case(deg, act, abi.JITTER_NONE, 0, 100, scatter, upscale=True)
     dd = torch.float64
     sdf64, feat64 = vol.sdf.to(dd).requires_grad_(True), vol.feat.to(dd).requires_grad_(True)
     inv_s64 = torch.tensor(cfg.inv_s, dtype=dd, requires_grad=True)
-    ref = compose64(vol.mapping, sdf64, feat64, 2, 'relu', ex, cfg, inv_s64, t_rand, bk)
+    ref = compose64(vol.mapping, sdf64, feat64, deg, act, ex, cfg, inv_s64, t_rand, bk)
     sum((ref[k] * G[k].to(dd)).sum() for k in G).backward()
     assert _rel_l2(sdf_p.grad.cpu().double(), sdf64.grad) < 2e-3
     assert _rel_l2(feat_p.grad.cpu().double(), feat64.grad) < 2e-3
-    assert feat_p.grad[..., 27].abs().max() == 0
+    assert feat64.grad.abs().max() > 0
+    if feat_p.shape[-1] > sh.n_coef(deg):
+        assert feat_p.grad[..., sh.n_coef(deg):].abs().max() == 0          # the pad channel (27 at degree 2, 3 at degree 0)
 
 
 @pytest.mark.parametrize("scatter", ["atomic", "binned"])

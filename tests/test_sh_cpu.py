@@ -2,9 +2,7 @@
 REAL reference (tests/golden/make_golden_sh.py -> sh.npz), the host-only argument checks of the C boundary, and the
 construction rules of SDFVolume / SDFField / NeuSHead."""
 import ctypes as C
-import functools
 import os
-import re
 import shutil
 import subprocess
 
@@ -12,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_report import HIPCC, kernels_of
 from selfocc_amd import abi, sh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -231,36 +230,18 @@ def test_marshalling_carries_sh_fields():
 
 
 # ---- compiler report: the new forward kernels keep nothing in scratch ---------------------------------------------------------
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
-         "-fno-vectorize", "--cuda-device-only", "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]   # csrc/build.sh
-
-
-@functools.lru_cache(maxsize=None)
-def _resources(src):
-    out = subprocess.run([HIPCC, *FLAGS, src], check=True, capture_output=True, text=True).stderr
-    table, name = {}, None
-    for line in out.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            table[name] = {}
-            continue
-        m = re.search(r"remark: +(VGPRs|AGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and name:
-            table[name][m.group(1).split()[0]] = int(m.group(2))
-    return table
-
-
 @pytest.mark.skipif(not shutil.which(HIPCC), reason="hipcc not present")
-@pytest.mark.parametrize("src,prefix,count", [("render_fwd.hip", "render_sh_explicit", 6), ("render_fwd.hip", "render_sh_pixgrid", 6),
-                                               ("render_train.hip", "render_sh_samples_kernel", 18)])
-def test_sh_forward_kernels_use_no_scratch(src, prefix, count):
+@pytest.mark.parametrize("src,base,count", [("render_fwd.hip", "render_fwd_explicit", 6), ("render_fwd.hip", "render_fwd_pixgrid", 6),
+                                             ("render_train.hip", "render_fwd_samples_kernel", 18)],
+                         # the ids these cases have always had: the names of the kernels before they became instances of `base`
+                         ids=["render_fwd.hip-render_sh_explicit-6", "render_fwd.hip-render_sh_pixgrid-6",
+                              "render_train.hip-render_sh_samples_kernel-18"])
+def test_sh_forward_kernels_use_no_scratch(src, base, count):
     """eval forward (explicit / pixel grid x 3 basis sizes x 2 mapping kinds) and training forward (x 3 waves-per-ray forms):
     the folded gather keeps three sums, so nothing of width n_coef can spill"""
-    table = _resources(os.path.join(ROOT, "selfocc_amd", "csrc", src))
-    hits = {k: v for k, v in table.items() if prefix in k}
-    assert len(hits) == count, sorted(table)
-    for k, r in hits.items():
-        assert r["ScratchSize"] == 0, (k, r)
-        assert r["VGPRs"] + r.get("AGPRs", 0) <= 256, (k, r)
+    hits = kernels_of(src, base, lambda r: r.nb > 0)
+    assert len(hits) == count, [k.name for k in hits]
+    assert sorted({(k.row.nb, k.row.nf) for k in hits}) == [(1, 4), (4, 12), (9, 28)]
+    for k in hits:
+        assert k.res["ScratchSize"] == 0, k
+        assert k.res["VGPRs"] + k.res.get("AGPRs", 0) <= 256, k
