@@ -11,6 +11,7 @@ i=0; rm -rf $R/gpurun_out/pmc_$TAG
 for pass in "${passes[@]}"; do
   i=$((i+1))
   timeout 200 rocprofv3 --pmc $pass --output-format csv -d $R/gpurun_out/pmc_$TAG/p$i -o p -- python $R/scripts/prof_render.py $C 3 > /dev/null 2>&1
+  rc=$?; [ $rc -eq 0 ] || { echo "pass $i ($pass) failed: rc=$rc"; exit 1; }     # nothing more on the GPU after a pass that failed
 done
 python - <<PY | tee $R/gpurun_out/${TAG}_pmc.txt
 import sys, os; sys.path.insert(0, "$R"); import bench

@@ -852,6 +852,9 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
 //     at steps lo and hi is interior at every step between; [i_lo, i_hi] is found once per wave with the test itself;
 //   * the best-weight compare: T does not grow inside a run, so w = kAlphaFree * T does not exceed the run's first w;
 //   * the exit test: see kRunExitFreeSteps.
+// The same range splits the march into three phases: the steps before i_lo and from i_hi on run the general step, the steps
+// between a copy of it compiled without the interior test, the all_interior flags and the range compares (the wave-uniform
+// scalar work and branches of a step whose outcome is known there).
 // What a lane computes at a step, and every wave-wide decision, is what the step-by-step form computes: same outputs, bit for bit.
 // ---------------------------------------------------------------------------------------
 // A run of n free steps multiplies T by ((1 - kAlphaFree) + 1e-7f) n times, each product rounded: by more than
@@ -864,7 +867,7 @@ struct AheadStep {
     float gh, gw, gd, fi;         // grid coordinates (the fractions are taken only by the steps that interpolate)
     int h0, w0, d0;
     unsigned cell, code;
-    bool all_interior;            // wave-uniform
+    bool all_interior;            // wave-uniform; not kept by the steps inside the sure range
 };
 
 template <bool FACE_SAFE, class GeomFn>
@@ -929,14 +932,18 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
         }
         if (i_hi < 0) i_lo = S;
     }
-    auto sure = [&](const int i) __attribute__((always_inline)) { return i >= i_lo && i <= i_hi; };
-
-    auto locate = [&](const int i, AheadStep &st) __attribute__((always_inline)) {
+    // Locate step i.  In the sure range (IN_SURE) the wave is interior without a test: the code load is unconditional and
+    // st.all_interior is neither written nor read.  Outside it the interior test runs at every step (at i_lo and i_hi it is
+    // the evaluation that found the range, so it is true there).
+    auto locate = [&](const int i, AheadStep &st, auto in_sure) __attribute__((always_inline)) {
         place(i, st);
-        st.all_interior = true;
-        if (!sure(i)) st.all_interior = interior(st);
-        st.code = 0u;
-        if (st.all_interior) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 16u, 0);
+        if constexpr (decltype(in_sure)::value) {
+            st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 16u, 0);
+        } else {
+            st.all_interior = interior(st);
+            st.code = 0u;
+            if (st.all_interior) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 16u, 0);
+        }
     };
     auto near_face = [&](float fh, float fw, float fd) __attribute__((always_inline)) {
         return fmaxf(fmaxf(fabsf(fh - 0.5f), fabsf(fw - 0.5f)), fabsf(fd - 0.5f)) > 0.5f - face_m;
@@ -974,10 +981,17 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
         return so_cell_of(gh, gw, gd);
     };
 
-    // returns whether the step skipped (wave-uniform)
-    auto step = [&](const int i, AheadStep &cur, AheadStep &nxt) __attribute__((always_inline)) {
-        const bool skip = cur.all_interior && so_all((int)cur.code >= rcode);
-        if (i + 1 < S) locate(i + 1, nxt);
+    // Returns whether the step skipped (wave-uniform).  IN_SURE: steps i and i + 1 both lie in the sure range.
+    auto step = [&](const int i, AheadStep &cur, AheadStep &nxt, auto in_sure) __attribute__((always_inline)) {
+        constexpr bool IN_SURE = decltype(in_sure)::value;
+        bool skip;
+        if constexpr (IN_SURE) {
+            skip = so_all((int)cur.code >= rcode);
+            locate(i + 1, nxt, in_sure);
+        } else {
+            skip = cur.all_interior && so_all((int)cur.code >= rcode);
+            if (i + 1 < S) locate(i + 1, nxt, in_sure);
+        }
         float w;
         if (skip) {
             w = kAlphaFree * T;
@@ -1010,7 +1024,7 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
                 }
             }
             if (!loaded) {
-                if (cur.all_interior) {
+                if (IN_SURE || cur.all_interior) {
                     {   // the records of cells (h, w, d) and (h, w + 1, d) = the four corner pairs, in the register order
                         // so_trilerp_fast_pk takes them
                         // (issuing these loads before locate() above, to run it under them, measured 9 % SLOWER)
@@ -1035,17 +1049,15 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
         return skip;
     };
 
-    // The run loop.  On entry step i - 1 skipped and passed the exit test, and `st` holds step i, located.  It composites
-    // steps i, i + 1, ... while they skip and the step after them is inside the sure range (so that `st`, re-located in
-    // place after each decision, needs no interior test), then hands `st` = the located step i back to the general step.
-    // Returns true when the march is over.
+    // The run loop, entered from the sure loop only.  On entry step i - 1 skipped and passed the exit test, `st` holds step
+    // i, located, and i_lo <= i <= i_hi.  It composites steps i, i + 1, ... while they skip and the step after them is inside
+    // the sure range (so that `st`, re-located in place after each decision, needs no interior test), then hands `st` = the
+    // located step i back to the caller.  Returns true when the march is over.
     auto run = [&](int &i, AheadStep &st) __attribute__((always_inline)) {
-        if (i < i_lo || i >= i_hi) return false;
         auto free_step = [&]() __attribute__((always_inline)) {
             const float t_mid = fmaf(st.fi, dt, tnear + hdt);
             ++i;
             place(i, st);
-            st.all_interior = true;
             st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 16u, 0);
             const float w = kAlphaFree * T;
             T = T * ((1.0f - kAlphaFree) + 1e-7f);
@@ -1063,18 +1075,41 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
         return false;
     };
 
+    // Three phases.  Head, steps [0, i_lo), and tail, steps [i_hi, S): the general step, which tests the interior at every
+    // step; at most kSureScan steps each, so they run as a rolled loop that moves the located step back (A = B) instead of
+    // ping-ponging.  A wave without a sure range has i_lo = S and marches in the head loop alone.  Between them the sure loop,
+    // steps i with i_lo <= i and i + 1 <= i_hi: no interior test, no all_interior flag, no range compare, the record loads
+    // on the brick path; the located steps ping-pong between A and B, and skipped steps continue in the run loop.  Whichever
+    // loop composites a step, the lane computes what the general step computes.
+    // (Head and tail as ONE loop around the sure loop, 15.0 KB instead of 19.0 KB of code, needs 71 VGPRs instead of 63: what
+    // either loop keeps in registers is then live across both.  DESIGN 3.1, round 10.)
     {
+        constexpr std::false_type general{};
+        constexpr std::true_type in_sure{};
         AheadStep A, B;
-        locate(0, A);
-        for (int i = 0;;) {
-            const bool sa = step(i, A, B);
-            if (++i >= S) break;
-            if (so_all(T < 1e-10f)) break;
-            if (sa && run(i, B)) break;
-            const bool sb = step(i, B, A);
-            if (++i >= S) break;
-            if (so_all(T < 1e-10f)) break;
-            if (sb && run(i, A)) break;
+        locate(0, A, general);
+        int i = 0;
+        bool over = false;
+        auto gen = [&](int end) __attribute__((always_inline)) {
+#pragma nounroll
+            while (i < end) {
+                step(i, A, B, general);
+                if (++i >= S || so_all(T < 1e-10f)) { over = true; break; }
+                A = B;
+            }
+        };
+        gen(i_lo);
+        if (!over) {
+            while (i < i_hi) {
+                const bool sa = step(i, A, B, in_sure);
+                ++i;
+                if (so_all(T < 1e-10f) || (sa && run(i, B))) { over = true; break; }
+                if (i >= i_hi) { A = B; break; }        // the tail takes its located step from A
+                const bool sb = step(i, B, A, in_sure);
+                ++i;
+                if (so_all(T < 1e-10f) || (sb && run(i, A))) { over = true; break; }
+            }
+            if (!over) { A.all_interior = true; gen(S); }
         }
     }
 
