@@ -272,6 +272,25 @@ int selfocc_render_bwd(const so_render_bwd_args *args, void *stream);
  * ray's unit direction (3 floats) in place of a d L / d feature row, and the brick kernel expands Y_k from the direction. */
 size_t selfocc_render_bwd_ws_bytes(const so_render_bwd_args *args);
 
+/* Median depth of the march: upstream nerfstudio's DepthRenderer(method="median"), the `ms_depths_median` eval_depth.py reads
+ * (eval_depth.py:178-218).  Per ray, with w_i / ts_i the per-sample `weights` / `ts` selfocc_render_fwd writes for the same
+ * inputs (the same bits):
+ *     c_0 = w_0,  c_i = c_{i-1} + w_i                  float32, in sample order
+ *     j   = the smallest i with c_i >= 0.5f;  n_samples - 1 when there is none (a NaN sum never reaches 0.5)
+ *     median_depth = ts_j        median_index = j
+ * One launch of a kernel of its own (csrc/render_median.hip): one ray per lane, canonical arithmetic whatever SO_FLAG_EXACT
+ * says, and a ray stops marching at its j.  It reads the SDF volume only: of `fwd`, the mapping, sdf_vol, the ray fields,
+ * the sampling fields (aabb, near_plane, n_samples, sample_pos, jitter_mode, t_rand), inv_s and inv_s_dev are used;
+ * feat_vol, feat_dtype, feat_stride, n_rgb, n_sem, sh_deg, sh_act, bkgd_*, flags, sdf_brick and every output pointer of `fwd`
+ * are ignored.  Refused by name: both outputs NULL, n_samples < 1, n_rays < 0, and what selfocc_render_fwd refuses among
+ * the fields that are read.  n_rays == 0 succeeds without a launch.  A new entry point: SELFOCC_ABI_VERSION is unchanged. */
+typedef struct so_render_median_args {
+    so_render_args fwd;        /* inputs as for selfocc_render_fwd; outputs and feature fields ignored */
+    float   *median_depth;     /* (n_rays) or NULL */
+    int32_t *median_index;     /* (n_rays) or NULL */
+} so_render_median_args;
+int selfocc_render_median(const so_render_median_args *args, void *stream);
+
 /* ------------------------------------------------------------------------------------
  * Multi-scale deformable attention.  Replaces mmcv==2.0.1
  * MultiScaleDeformableAttnFunction.apply(value, spatial_shapes, level_start_index,

@@ -74,6 +74,10 @@ class SoRenderBwdArgs(C.Structure):
     ]
 
 
+class SoRenderMedianArgs(C.Structure):
+    _fields_ = [("fwd", SoRenderArgs), ("median_depth", _p), ("median_index", _p)]
+
+
 class SoMsdaArgs(C.Structure):
     _fields_ = [
         ("form", _i), ("bs", _i), ("nv", _i), ("nq", _i), ("heads", _i), ("d", _i), ("L", _i), ("P", _i),
@@ -159,6 +163,7 @@ SYMBOLS = {
     "selfocc_render_fwd": (C.c_int, [C.POINTER(SoRenderArgs), _p]),
     "selfocc_render_bwd": (C.c_int, [C.POINTER(SoRenderBwdArgs), _p]),
     "selfocc_render_bwd_ws_bytes": (C.c_size_t, [C.POINTER(SoRenderBwdArgs)]),
+    "selfocc_render_median": (C.c_int, [C.POINTER(SoRenderMedianArgs), _p]),
     "selfocc_msda_fwd": (C.c_int, [C.POINTER(SoMsdaArgs), _p]),
     "selfocc_msda_bwd": (C.c_int, [C.POINTER(SoMsdaArgs), _p]),
     "selfocc_msda_ws_bytes": (C.c_size_t, [C.POINTER(SoMsdaArgs)]),

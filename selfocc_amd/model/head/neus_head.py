@@ -14,6 +14,7 @@ declared deviation risks): field evaluated at frustum START positions, single ji
 ray in training, ``inv_s = exp(10 * variance)``, eik_grad = metre gradient at every sample,
 second_grad = compact second differences of the SDF volume.
 """
+import dataclasses
 import math
 import os
 
@@ -28,7 +29,7 @@ from ...mapping import GridMeterMapping
 from ...occ import field_query, field_query_autograd, uniform_lattice
 from ...field import field_volume, field_volume_supported, field_volume_train_supported, FieldVolumeFunction
 from ...registry import HEADS
-from ...render import SDFVolume, RaySet, RenderConfig, render_rays, render_rays_autograd
+from ...render import SDFVolume, RaySet, RenderConfig, render_rays, render_rays_autograd, render_median_depth
 from ..bricks import BaseModule, _TallLinear
 
 
@@ -355,7 +356,7 @@ class NeuSHead(BaseModule):
                  embed_dims=128, color_dims=0, density_layers=2, sh_deg=2, sh_act="relu", init_cfg=None,
                  print_freq=50, two_split=True, tpv=False, using_2d_img_feats=False,
                  sample_pos='start', single_jitter=True, feat_dtype=torch.float32, exact_render=False,
-                 ray_shard=False, render_normal=False, **kwargs):
+                 ray_shard=False, render_normal=False, return_median_depth=False, **kwargs):
         super().__init__(init_cfg)
         for name, on in dict(num_samples_importance=num_samples_importance > 0, num_up_sample_steps=num_up_sample_steps > 0,
                              use_numerical_gradients=use_numerical_gradients, estimate_flow=estimate_flow,
@@ -390,6 +391,9 @@ class NeuSHead(BaseModule):
         # vis_* scripts only) from a chunked per-sample pass; off by default (zeros): eval_depth.py never reads it and
         # the pass costs ~25 x the depth render
         self.render_normal = render_normal
+        # render() / forward(): add `ms_depths_median` (nerfstudio's DepthRenderer(method="median"), the third depth target of
+        # eval_depth.py) from one extra SDF-only launch (render_median_depth); off by default: no key, no launch
+        self.return_median_depth = return_median_depth
         self.last_inv_s = None
         self._register_load_state_dict_pre_hook(self._report_foreign_field_keys, with_module=True)
 
@@ -546,9 +550,11 @@ class NeuSHead(BaseModule):
         return {'sdf': sdf, 'rep': representation, 'xyz': xyz}
 
     @torch.no_grad()
-    def render(self, metas=None, batch=0, **kwargs):
+    def render(self, metas=None, batch=0, median_depth=None, **kwargs):
         """Full-lattice render in ONE launch: ``batch`` (the reference's memory-driven chunk size,
-        neus_head.py:329-385) is accepted and ignored — no per-sample tensor is materialised."""
+        neus_head.py:329-385) is accepted and ignored — no per-sample tensor is materialised.
+        ``median_depth`` (None: the head's ``return_median_depth``) adds ``ms_depths_median`` from one more launch."""
+        want_median = self.return_median_depth if median_depth is None else bool(median_depth)
         vol = self.model.field.volume
         assert vol is not None, "call prepare() (or forward) before render()"
         device = vol.sdf.device
@@ -568,10 +574,14 @@ class NeuSHead(BaseModule):
             rays = sdist.shard_rays(full)
             bk = torch.rand(rays.n_rays, 3, device=device) if cfg.bkgd_mode == abi.BKGD_PER_RAY else None
             loc = render_rays(vol, rays, cfg, bkgd_rays=bk)
+            if want_median:
+                loc['median_depth'] = render_median_depth(vol, rays, cfg)['median_depth']
             out = {k: sdist.gather_rays(v, full).reshape(-1, *v.shape[1:]) for k, v in loc.items()}
         else:
             bk = torch.rand(rays.n_rays, 3, device=device) if cfg.bkgd_mode == abi.BKGD_PER_RAY else None
             out = render_rays(vol, rays, cfg, bkgd_rays=bk)
+            if want_median:
+                out['median_depth'] = render_median_depth(vol, rays, cfg)['median_depth']
         shp = (1, num_cams, num_rays)
         rgb = out['rgb'].reshape(*shp, 3) if 'rgb' in out else torch.empty(*shp, 0, device=device)
         if kwargs.get('vis_normal', self.render_normal) and not self._sharding(rays):
@@ -583,6 +593,8 @@ class NeuSHead(BaseModule):
                    'ms_rays': pix}
         if self.return_max_depth:
             outputs['ms_max_depths'] = [out['max_depth'].reshape(shp)]
+        if want_median:
+            outputs['ms_depths_median'] = [out['median_depth'].reshape(shp)]
         if self.return_sem and 'sem' in out:
             outputs['sem'] = [out['sem'].reshape(*shp, -1)]
         return outputs
@@ -641,6 +653,13 @@ class NeuSHead(BaseModule):
             inv_s = sdist.replicate_grad_sum(inv_s)       # d/d(variance) is a sum over all rays as well
         out = render_rays_autograd(vol, inv_s, rays, cfg, want_grad_samples=True, t_rand=t_rand, bkgd_rays=bk)
         self.last_inv_s = inv_s.detach()          # device tensor (the reference logs output['inv_s'], neus_head.py:631-633)
+        median = None
+        if self.return_median_depth:
+            # the same rays, jitter and inv_s as the render above; detached (an index into ts carries no gradient)
+            mcfg = dataclasses.replace(cfg, inv_s_dev=inv_s.detach().reshape(1).float().contiguous())
+            median = render_median_depth(vol.detached(), rays, mcfg, t_rand=t_rand)['median_depth']
+            if full_rays is not None:
+                median = sdist.gather_rays(median, full_rays)
         shard = None
         if full_rays is not None:
             # per-ray tensors are gathered into full-frame maps (5 - 30 floats per ray); the per-sample tensors stay on the
@@ -683,6 +702,8 @@ class NeuSHead(BaseModule):
             outputs['uniform_sdf'] = self.get_uniform_sdf(self.aabb, self.resolution, device, True)[0]
         if self.return_max_depth:
             outputs['ms_max_depths'] = [out['max_depth'].reshape(shp)]
+        if median is not None:
+            outputs['ms_depths_median'] = [median.reshape(shp)]
         if self.return_second_grad:
             outputs['second_grad'] = field.second_grad()
         if self.return_sample_sdf:
@@ -691,7 +712,7 @@ class NeuSHead(BaseModule):
             outputs['sem'] = [out['sem'].reshape(*shp, -1)]
         if self.two_split and self.img2lidar.two_split:
             h = num_cams // 2
-            for k in ('ms_depths', 'ms_accs', 'ms_fars', 'ms_max_depths'):
+            for k in ('ms_depths', 'ms_accs', 'ms_fars', 'ms_max_depths', 'ms_depths_median'):
                 if k in outputs:
                     outputs[k] = [outputs[k][0][:, :h]]
             outputs['ms_colors'] = [rgb[:, h:]]

@@ -154,10 +154,11 @@ def _c(t, dtype=torch.float32):
 
 
 def marshal_render_args(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, per_sample=False,
-                        want_grad_samples=False, t_rand=None, bkgd_rays=None, outputs=None):
+                        want_grad_samples=False, t_rand=None, bkgd_rays=None, outputs=None, inputs_only=False):
     """Fill an ``so_render_args`` for tensors living on ONE device (CUDA for the HIP
     library; the test oracle feeds CPU tensors through the same marshalling).
-    Returns (args, outputs_dict, keepalive)."""
+    Returns (args, outputs_dict, keepalive).  ``inputs_only``: allocate no output (the callers whose entry point
+    ignores the outputs of the struct: render_median_depth)."""
     dev = vol.sdf.device
     a = abi.SoRenderArgs()
     a.map = vol.mapping.to_abi()
@@ -214,6 +215,8 @@ def marshal_render_args(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, per_
 
     f32 = dict(dtype=torch.float32, device=dev)
     out = outputs if outputs is not None else {}
+    if inputs_only:
+        return a, out, keep
     def alloc(name, *shape):
         if name not in out:
             out[name] = torch.empty(*shape, **f32)
@@ -247,6 +250,56 @@ def render_rays(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, per_sample=F
         a.sdf_brick = ptr(_brick_workspace(vol.sdf))
     check(lib().selfocc_render_fwd(a, current_stream(vol.sdf.device)), "selfocc_render_fwd")
     return out
+
+
+def render_median_depth(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, t_rand=None, want_index=False):
+    """Median depth of every ray in ONE launch (selfocc_render_median, csrc/render_median.hip): nerfstudio's
+    DepthRenderer(method="median"), the ``ms_depths_median`` of eval_depth.py.  Equal, bit for bit, to
+    ``median_depth_reference`` applied to the ``weights`` / ``ts`` of ``render_rays(vol, rays, cfg, per_sample=True)``,
+    without materialising them: a ray stops marching at the first sample whose running weight sum reaches 0.5.
+    Reads the SDF volume only (``vol.feat`` is not looked at) and marches in the canonical order whatever ``cfg.exact``.
+    Returns {'median_depth': (N,) float32[, 'median_index': (N,) int32]}."""
+    if not vol.sdf.is_cuda:
+        raise RuntimeError("selfocc_amd.render_median_depth needs CUDA(HIP) tensors: there is no CPU fallback")
+    # geometry only: the sampling fields and inv_s of `cfg`; its background, colour and march switches do not apply
+    geo = RenderConfig(aabb=cfg.aabb, n_samples=cfg.n_samples, inv_s=cfg.inv_s, inv_s_dev=cfg.inv_s_dev, near_plane=cfg.near_plane,
+                       sample_pos=cfg.sample_pos, jitter_mode=cfg.jitter_mode)
+    a, _out, _keep = marshal_render_args(SDFVolume(vol.mapping, vol.sdf), rays, geo, t_rand=t_rand, inputs_only=True)
+    ma = abi.SoRenderMedianArgs()
+    ma.fwd = a
+    N, dev = rays.n_rays, vol.sdf.device
+    out = {'median_depth': torch.empty(N, dtype=torch.float32, device=dev)}
+    if want_index:
+        out['median_index'] = torch.empty(N, dtype=torch.int32, device=dev)
+    if N == 0:          # nothing to launch (and an empty tensor has no address to pass)
+        return out
+    ma.median_depth = ptr(out['median_depth'])
+    if want_index:
+        ma.median_index = ptr(out['median_index'])
+    check(lib().selfocc_render_median(ma, current_stream(dev)), "selfocc_render_median")
+    return out
+
+
+def median_depth_reference(weights, ts):
+    """The definition of the median depth, on CPU tensors or arrays of shape (..., S):
+        c_0 = w_0, c_i = c_{i-1} + w_i  in float32, in sample order;   j = the first i with c_i >= 0.5, S - 1 if none
+    Returns (median_depth = ts[..., j] float32, median_index = j int32), as tensors when ``weights`` is one.
+    Sequential float32 on purpose: torch.cumsum on the CPU accumulates float32 in double."""
+    import numpy as np
+    as_tensor = isinstance(weights, torch.Tensor)
+    host = lambda t: (t.detach().numpy() if isinstance(t, torch.Tensor) else np.asarray(t))
+    if as_tensor and weights.is_cuda:
+        raise RuntimeError("median_depth_reference is the CPU definition: pass CPU tensors or arrays")
+    w, t = host(weights).astype(np.float32, copy=False), host(ts).astype(np.float32, copy=False)
+    assert w.shape == t.shape and w.ndim >= 1 and w.shape[-1] >= 1, f"weights {w.shape} / ts {t.shape}: need equal (..., S >= 1)"
+    S = w.shape[-1]
+    c = np.add.accumulate(w, axis=-1, dtype=np.float32)
+    hit = c >= np.float32(0.5)                                  # a NaN sum never compares true
+    j = np.where(hit.any(-1), hit.argmax(-1), S - 1).astype(np.int32)
+    depth = np.take_along_axis(t, j[..., None].astype(np.int64), -1)[..., 0]
+    if as_tensor:
+        return torch.from_numpy(np.ascontiguousarray(depth)), torch.from_numpy(np.ascontiguousarray(j))
+    return depth, j
 
 
 _BRICK_WS = {}

@@ -37,6 +37,12 @@ CONFIGS = {
                               d_range=[-1.0, 5.4, 5.4]),
                  aabb=(-40.0, -40.0, -1.0, 40.0, 40.0, 5.4), n_cams=6, img=(768, 1600), rays=(48, 100),
                  n_samples=256, focal=1266.0, cam_z=1.5, cam_xy=(0.0, 0.0)),
+    # cfg6: shipped nuscenes_depth shapes: 257x257x31, SDF only, the 450x800 evaluation lattice on 900x1600 images, 256 samples
+    "cfg6": dict(mapping=dict(nonlinear_mode='linear', h_size=[128, 0], h_range=[51.2, 0], h_half=False,
+                              w_size=[128, 0], w_range=[51.2, 0], w_half=False, d_size=[30, 0],
+                              d_range=[-4.0, 5.0, 5.0]),
+                 aabb=(-51.2, -51.2, -4.0, 51.2, 51.2, 5.0), n_cams=6, img=(900, 1600), rays=(450, 800),
+                 n_samples=256, focal=1266.0, cam_z=1.5, cam_xy=(0.0, 0.0)),
 }
 
 
