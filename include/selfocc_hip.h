@@ -665,6 +665,36 @@ int selfocc_reproj_bwd(const so_reproj_args *args, const float *g_l1,
                        const float *g_rgb_combine, float *g_weights, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Per ray and temporal frame, the sample with the largest warped-photometric weight, and a per-sample value read
+ * there: the sdf_loss term of ReprojLossMonoMultiNew (loss/reproj_loss_mono_multi_new.py:265-270).  One launch per
+ * camera serves both frames; no image is read.
+ *   weights, ts, values (R, S); deltas (R, S) or NULL; pix (R, 2); T_prev / T_next (4,4) row-major; 1 <= S <= 512.
+ * For frame f (0 = prev, 1 = next) wn_i is bit for bit the `wnorm` selfocc_reproj_fwd writes for the same inputs
+ * when the other frame's transform maps behind the camera (ts > 0), and
+ *   j = 0, best = wn_0;  for i = 1 .. S-1: if (wn_i > best) { best = wn_i; j = i; }
+ * (smallest index among equal maxima; 0 for a fully masked ray; a NaN never wins).
+ *   pick_index[r][f] = j,  pick_value[r][f] = values[r * S + j].
+ * R == 0 succeeds without a launch (after the argument checks).  New entry points: SELFOCC_ABI_VERSION is unchanged.
+ * ---------------------------------------------------------------------------------- */
+typedef struct so_reproj_pick_args {
+    const float *weights, *ts, *deltas; /* deltas may be NULL                           */
+    const float *values;                /* (R, S) what is read at the pick (sample SDF) */
+    const float *pix;
+    const float *T_prev, *T_next;
+    int32_t R, S;
+    float img_h, img_w;
+    int32_t *pick_index;                /* (R, 2)                                       */
+    float *pick_value;                  /* (R, 2)                                       */
+} so_reproj_pick_args;
+
+int selfocc_reproj_pick_fwd(const so_reproj_pick_args *args, void *stream);
+
+/* dense d loss / d values (R, S), every element written: zero, plus g_pick_value[r][f] at pick_index[r][f] (the two
+ * summed where both frames picked the same sample).  No memset, no atomics. */
+int selfocc_reproj_pick_bwd(const int32_t *pick_index, const float *g_pick_value, float *g_values, int32_t R, int32_t S,
+                            void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Depth-evaluation metric tail: DepthMetric._after_step (utils/metric_util.py:247-349) and
  * compute_depth_errors_torch (:424-444) for one frame, in ONE launch (one workgroup per camera).
  *   pred (N, h, w) f32 rendered depth; loc (N, n, 2) f32 normalised (u, v), 8-byte aligned;

@@ -127,6 +127,18 @@ class SoReprojArgs(C.Structure):
     ]
 
 
+class SoReprojPickArgs(C.Structure):
+    _fields_ = [
+        ("weights", _p), ("ts", _p), ("deltas", _p),
+        ("values", _p),
+        ("pix", _p),
+        ("T_prev", _p), ("T_next", _p),
+        ("R", _i), ("S", _i),
+        ("img_h", _f), ("img_w", _f),
+        ("pick_index", _p), ("pick_value", _p),
+    ]
+
+
 class SoDepthMetricArgs(C.Structure):
     _fields_ = [
         ("pred", _p), ("loc", _p), ("gt", _p), ("mask", _p),
@@ -204,6 +216,8 @@ SYMBOLS = {
     "selfocc_ssim_bwd": (C.c_int, [_p] * 4 + [_i] * 4 + [_p, _p, _p, _p]),
     "selfocc_reproj_fwd": (C.c_int, [C.POINTER(SoReprojArgs), _p]),
     "selfocc_reproj_bwd": (C.c_int, [C.POINTER(SoReprojArgs), _p, _p, _p, _p]),
+    "selfocc_reproj_pick_fwd": (C.c_int, [C.POINTER(SoReprojPickArgs), _p]),
+    "selfocc_reproj_pick_bwd": (C.c_int, [_p, _p, _p, _i, _i, _p]),
     "selfocc_depth_metric_ws_bytes": (C.c_size_t, [C.POINTER(SoDepthMetricArgs)]),
     "selfocc_depth_metric": (C.c_int, [C.POINTER(SoDepthMetricArgs), _p]),
     "selfocc_ssc_metric": (C.c_int, [C.POINTER(SoSscMetricArgs), _p]),

@@ -16,6 +16,7 @@
 // wavefront-shuffle reductions; weights / ts are read as contiguous runs.  Nothing
 // per-sample is written in the forward pass; backward recomputes the taps.
 #include "so_device.h"
+#include "reproj_device.h"
 
 namespace {
 
@@ -24,19 +25,6 @@ struct Taps {
     float comb[3];   // (rgb_prev * m_prev + rgb_next * m_next) / max(cnt, 1)
     bool any;        // general_mask: at least one frame valid
 };
-
-SO_DEVFN void project(const float *__restrict__ T, float u, float v, float t, float img_h, float img_w,
-                      float &px, float &py, bool &ok) {
-    // cal_pixel (:118-133): trans @ (u t, v t, t, 1)
-    const float x = u * t, y = v * t;
-    const float p0 = ((T[0] * x + T[1] * y) + T[2] * t) + T[3];
-    const float p1 = ((T[4] * x + T[5] * y) + T[6] * t) + T[7];
-    const float p2 = ((T[8] * x + T[9] * y) + T[10] * t) + T[11];
-    const float den = fmaxf(1e-5f, p2);
-    px = p0 / den;
-    py = p1 / den;
-    ok = (p2 > 0.0f) && (px > 0.0f) && (px < img_w) && (py > 0.0f) && (py < img_h);
-}
 
 // F.grid_sample(bilinear, padding_mode='border', align_corners=True) of a planar (3, Hi, Wi) image
 SO_DEVFN void sample_rgb(const float *__restrict__ img, int Hi, int Wi, float px, float py, float img_h,
@@ -85,26 +73,6 @@ SO_DEVFN Taps sample_taps(const so_reproj_args &a, float u, float v, float t, co
 #pragma unroll
     for (int c = 0; c < 3; ++c) r.comb[c] = ((mp ? rp[c] : 0.0f) + (mn ? rn[c] : 0.0f)) / cnt;
     return r;
-}
-
-SO_DEVFN float wsum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// effective weight of a sample: optional w / delta (:111-116), then general-mask zeroing (:178-179)
-SO_DEVFN float eff_weight(const so_reproj_args &a, size_t o, bool any, float &scale) {
-    float w = a.weights[o];
-    scale = 1.0f;
-    if (a.deltas) {
-        const float eps = 1.1920928955078125e-07f;
-        const float d = a.deltas[o];
-        scale = (d < eps) ? 0.0f : 1.0f / fmaxf(d, eps);
-        w = (d < eps) ? 0.0f : w / fmaxf(d, eps);
-    }
-    if (!any) { w = 0.0f; scale = 0.0f; }
-    return w;
 }
 
 template <int M, bool BWD>

@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 from .._lib import upload
 from ..registry import OPENOCC_LOSS
-from ..reproj import ReprojSampleFunction
+from ..reproj import ReprojSampleFunction, reproj_pick
 from .base import BaseLoss
 
 
@@ -206,12 +206,23 @@ class ReprojLossMonoMultiNewCombine(_ReprojBase):
 @OPENOCC_LOSS.register_module()
 class ReprojLossMonoMultiNew(_ReprojBase):
     """Mono / KITTI variant: the two temporal frames are masked and renormalised separately and
-    enter the minimum as two candidates (reproj_loss_mono_multi_new.py:165-255)."""
+    enter the minimum as two candidates (reproj_loss_mono_multi_new.py:165-255).
+
+    ``sdf_loss=True`` (with ``sdf_loss_weight``, default 0.1) adds the reference's surface term (:265-285): per camera,
+    the SDF of each ray at the sample that carries the most masked, renormalised weight of the previous / of the next
+    frame (``selfocc_reproj_pick_fwd``: one launch for both frames), of which every ray takes the one of the candidate
+    that won its minimum — nothing when an auto-mask candidate won — as ``sum |sdf| / count(rays a temporal frame won)``.
+    ``sample_sdfs`` is read through ``input_dict``; the default dict takes it from the head's ``sample_sdf``
+    (``NeuSHead(return_sample_sdf=True)``).  As in the reference, a camera on which no ray is won by a temporal frame
+    contributes 0 / 0 = NaN: the value is kept, not guarded.  No gradient reaches ``weights`` through the pick (an arg-max
+    has none); ``sample_sdf`` receives one entry per selected ray.  Not available with a ray-sharded head."""
 
     def __init__(self, weight=1.0, input_dict=None, **kwargs):
         super().__init__(weight, input_dict, **kwargs)
-        if kwargs.get('sdf_loss', False):
-            raise NotImplementedError("sdf_loss=True is not used by any shipped config")
+        self.sdf_loss = kwargs.get('sdf_loss', False)
+        self.sdf_loss_weight = kwargs.get('sdf_loss_weight', 0.1)
+        if self.sdf_loss and input_dict is None:
+            self.input_dict['sample_sdfs'] = 'sample_sdf'
 
     def reproj_loss(self, curr_imgs, prev_imgs, next_imgs, ray_indices, weights, ts, metas, ms_rays, deltas=None,
                     sample_sdfs=None):
@@ -224,6 +235,13 @@ class ReprojLossMonoMultiNew(_ReprojBase):
         invalid = _invalid_on(pix.device)
         from ..dist import shard_of
         shard = shard_of(weights)        # ray-sharded head: per-sample inputs are this rank's rows (see the Combine loss)
+        if self.sdf_loss:
+            if sample_sdfs is None:
+                raise ValueError("ReprojLossMonoMultiNew(sdf_loss=True) needs 'sample_sdfs': map it in input_dict to the "
+                                 "head's 'sample_sdf' output (NeuSHead(return_sample_sdf=True))")
+            if shard is not None:
+                raise NotImplementedError("ReprojLossMonoMultiNew(sdf_loss=True) with a ray-sharded head is not supported: "
+                                          "run it with NeuSHead(ray_shard=False)")
         rays_k = num_rays if shard is None else shard.rays_per_cam_local
         pix_k = pix if shard is None else shard.pix_local.float().contiguous()
         tot = 0.
@@ -249,6 +267,14 @@ class ReprojLossMonoMultiNew(_ReprojBase):
             if not self.no_automask:
                 for img in (prev_imgs[0, cam].float(), next_imgs[0, cam].float()):
                     cands.append(self._photometric(self._sample_lattice(pix, img, 'zeros'), target_curr))
-            tot = tot + torch.stack(cands, dim=-1).min(dim=-1)[0].mean()
+            proj, k = torch.stack(cands, dim=-1).min(dim=-1)
+            tot = tot + proj.mean()
+            if self.sdf_loss:
+                # (:265-274) candidates 0 / 1 are the temporal frames, in the reference's order: |sdf| at that frame's pick
+                picked, _ = reproj_pick(sample_sdfs[cam].reshape(rays_k, -1), w2, t2, d2, pix_k, T_prev[cam], T_next[cam],
+                                        self.img_size[0], self.img_size[1])
+                won = k <= 1
+                sdf = picked.gather(1, k.clamp(max=1)[:, None])[:, 0].abs()
+                tot = tot + (torch.where(won, sdf, sdf.new_zeros(())).sum() / won.sum()) * self.sdf_loss_weight
         self.iter_counter += 1
         return tot / num_cams

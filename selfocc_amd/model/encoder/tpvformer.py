@@ -36,6 +36,21 @@ def _normalise(meter, lo0, hi0, lo1, hi1):
     return meter
 
 
+def tpv_plane_grids(H, W, Z):
+    """grid coordinates (h, w, d) of the cells of the three TPV planes: hw (H, W, 3), zh (Z, H, 3), wz (W, Z, 3)"""
+    ar = lambda n: torch.arange(n, dtype=torch.float)
+    hw_grid = torch.stack([ar(H)[:, None].expand(-1, W), ar(W)[None].expand(H, -1), torch.zeros(H, W)], -1)
+    zh_grid = torch.stack([ar(H)[None].expand(Z, -1), torch.zeros(Z, H), ar(Z)[:, None].expand(-1, H)], -1)
+    wz_grid = torch.stack([torch.zeros(W, Z), ar(W)[:, None].expand(-1, Z), ar(Z)[None].expand(W, -1)], -1)
+    return hw_grid, zh_grid, wz_grid
+
+
+def tpv_plane_meters(mapping, grids):
+    """the two in-plane metre coordinates of every cell of the three planes (what the positional encodings take)"""
+    g2m = mapping.grid2meter
+    return [g2m(grids[0])[..., [0, 1]], g2m(grids[1])[..., [1, 2]], g2m(grids[2])[..., [0, 2]]]
+
+
 _PLANE_SHAPES = {}
 
 
@@ -481,13 +496,10 @@ class TPVFormerEncoder(_EncoderBase):
             self.camera_se_net = CameraAwareSE(embed_dims, camera_aware_mid_channels or embed_dims, embed_dims)
         self.mapping = GridMeterMapping(**mapping_args)
         H, W, Z = self.mapping.size_h, self.mapping.size_w, self.mapping.size_d
-        ar = lambda n: torch.arange(n, dtype=torch.float)
-        hw_grid = torch.stack([ar(H)[:, None].expand(-1, W), ar(W)[None].expand(H, -1), torch.zeros(H, W)], -1)
-        zh_grid = torch.stack([ar(H)[None].expand(Z, -1), torch.zeros(Z, H), ar(Z)[:, None].expand(-1, H)], -1)
-        wz_grid = torch.stack([torch.zeros(W, Z), ar(W)[:, None].expand(-1, Z), ar(Z)[None].expand(W, -1)], -1)
+        hw_grid, zh_grid, wz_grid = tpv_plane_grids(H, W, Z)
         g2m = self.mapping.grid2meter
         positional_encoding = dict(positional_encoding)
-        positional_encoding['tpv_meters'] = [g2m(hw_grid)[..., [0, 1]], g2m(zh_grid)[..., [1, 2]], g2m(wz_grid)[..., [0, 2]]]
+        positional_encoding['tpv_meters'] = tpv_plane_meters(self.mapping, (hw_grid, zh_grid, wz_grid))
         self.positional_encoding = build_positional_encoding(positional_encoding)
         self.tpv_size = [H, W, Z]
         self._build_layers(transformerlayers, num_layers)

@@ -1,6 +1,7 @@
 """Host side of the fused reprojection sampling (selfocc_reproj_fwd / _bwd): the
 per-sample part of ReprojLossMonoMultiNewCombine.reproj_loss
-(loss/reproj_loss_mono_multi_new_combine.py:108-201) for one camera."""
+(loss/reproj_loss_mono_multi_new_combine.py:108-201) for one camera, and of the arg-max pick of the mono loss's
+``sdf_loss`` term (selfocc_reproj_pick_fwd / _bwd; loss/reproj_loss_mono_multi_new.py:265-270)."""
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -64,3 +65,54 @@ class ReprojSampleFunction(Function):
         check(lib().selfocc_reproj_bwd(a, ptr(g_l1), ptr(g_comb), ptr(g_w), current_stream(g_w.device)),
               "selfocc_reproj_bwd")
         return (g_w,) + (None,) * 10
+
+
+class ReprojPickFunction(Function):
+    """(values (R,S), weights (R,S), ts (R,S), deltas (R,S)|None, pix (R,2), T_prev (4,4), T_next (4,4), img_h, img_w)
+       -> pick_value (R,2), pick_index (R,2) int32: per ray and frame (0 = prev, 1 = next) the sample with the largest
+    masked, renormalised weight (the smallest index among equal maxima; 0 on a fully masked ray) and ``values`` there.
+    ONE launch serves both frames.  Differentiable wrt ``values`` only: an arg-max hands no gradient to the weights
+    (the reference's ``argmax`` + ``gather`` does not either)."""
+
+    @staticmethod
+    def forward(ctx, values, weights, ts, deltas, pix, T_prev, T_next, img_h, img_w):
+        if not values.is_cuda:
+            raise RuntimeError("ReprojPickFunction needs CUDA(HIP) tensors: selfocc_amd has no CPU fallback")
+        f = lambda t: None if t is None else t.detach().contiguous().float()
+        values, weights, ts, deltas, pix, T_prev, T_next = (f(t) for t in (values, weights, ts, deltas, pix, T_prev, T_next))
+        R, S = weights.shape
+        if values.shape != (R, S) or ts.shape != (R, S) or (deltas is not None and deltas.shape != (R, S)):
+            raise ValueError(f"reproj_pick: values / ts / deltas must have the shape of weights {(R, S)}")
+        if pix.shape != (R, 2) or T_prev.numel() != 16 or T_next.numel() != 16:
+            raise ValueError("reproj_pick: pix must be (R, 2) and the transforms (4, 4)")
+        dev = values.device
+        a = abi.SoReprojPickArgs()
+        a.weights, a.ts, a.deltas, a.values = ptr(weights), ptr(ts), ptr(deltas), ptr(values)
+        a.pix, a.T_prev, a.T_next = ptr(pix), ptr(T_prev), ptr(T_next)
+        a.R, a.S = R, S
+        a.img_h, a.img_w = float(img_h), float(img_w)
+        index = torch.empty(R, 2, device=dev, dtype=torch.int32)
+        value = torch.empty(R, 2, device=dev, dtype=torch.float32)
+        a.pick_index, a.pick_value = ptr(index), ptr(value)
+        if R > 0:       # an empty tensor has no address, and the entry refuses NULL inputs whatever R is
+            check(lib().selfocc_reproj_pick_fwd(a, current_stream(dev)), "selfocc_reproj_pick_fwd")
+        ctx.save_for_backward(index)
+        ctx.S = S
+        ctx.mark_non_differentiable(index)
+        return value, index
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_value, _g_index):
+        index, = ctx.saved_tensors
+        g_value = g_value.contiguous().float()
+        g = torch.empty(index.shape[0], ctx.S, device=index.device, dtype=torch.float32)    # every element is written
+        if index.shape[0] > 0:
+            check(lib().selfocc_reproj_pick_bwd(ptr(index), ptr(g_value), ptr(g), index.shape[0], ctx.S,
+                                                current_stream(g.device)), "selfocc_reproj_pick_bwd")
+        return (g,) + (None,) * 8
+
+
+def reproj_pick(values, weights, ts, deltas, pix, T_prev, T_next, img_h, img_w):
+    """-> (pick_value (R, 2) float32, pick_index (R, 2) int32); see ReprojPickFunction."""
+    return ReprojPickFunction.apply(values, weights, ts, deltas, pix, T_prev, T_next, img_h, img_w)
