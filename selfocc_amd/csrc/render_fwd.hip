@@ -875,6 +875,14 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
     const int S = a.n_samples;
     const RayGeom g = geom(a);
+    // The unit direction, parked for the rare canonical-cell block (canon_cell) in a slot of LDS that only this lane writes
+    // and reads (no barrier: the wave's own LDS operations complete in order).  3 KB per block; the kernel has no other LDS.
+    __shared__ float s_dir[FACE_SAFE ? 3 * 256 : 1];
+    int wave_slot = 0;                       // wave-uniform: the wave's first slot
+    if constexpr (FACE_SAFE) {
+        wave_slot = __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
+        s_dir[threadIdx.x] = g.dx; s_dir[256 + threadIdx.x] = g.dy; s_dir[512 + threadIdx.x] = g.dz;
+    }
     float tnear, tfar;
     so_collide(a, g, tnear, tfar);
     const float dt = (tfar - tnear) / (float)S;
@@ -952,10 +960,20 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
     // and the mapping are re-derived inside this rare branch from launch arguments re-read from the kernarg segment
     // (so_reload_args) — otherwise the direction stays in VGPRs and every mapping / camera constant in SGPRs across the
     // march loop (71 VGPRs / 104 SGPRs: 7 waves / SIMD).  The phases are fenced off from one another so that only one
-    // phase's constants are in SGPRs at a time.  geom() is the code that made the ray up front, and the phases are
-    // so_locate's: the same values, bit for bit.
+    // phase's constants are in SGPRs at a time.  The origin comes from geom(), the code that made the ray up front, and the
+    // unit direction from the lane's LDS slot, where the prelude parked what geom() gave it (re-deriving it here cost the
+    // camera-matrix loads, a sqrt and three divisions); the phases are so_locate's: the same values, bit for bit.
     auto canon_cell = [&](const int i) __attribute__((always_inline)) {
-        const RayGeom gc = geom(so_reload_args());
+        RayGeom gc = geom(so_reload_args());     // the origin only: the direction's arithmetic is dead code
+        {
+            // the lane's slot, rebuilt here (mbcnt) from an operand the optimiser cannot see through, so that neither the lane
+            // index nor an LDS address is computed ahead of the loops and kept in a register across them
+            unsigned ones = ~0u;
+            asm volatile("" : "+s"(ones));
+            const unsigned lane = __builtin_amdgcn_mbcnt_hi(ones, __builtin_amdgcn_mbcnt_lo(ones, 0u));
+            const float *slot = s_dir + (wave_slot + lane);
+            gc.dx = slot[0]; gc.dy = slot[256]; gc.dz = slot[512];
+        }
         __builtin_amdgcn_sched_barrier(0);
         float px, py, pz;
         {
@@ -973,11 +991,14 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
         }
         __builtin_amdgcn_sched_barrier(0);
         float slope;
-        const float gh = so_grid_coord(so_axis_m2g(so_reload_args().map.h, py, slope), so_reload_args().map.h.tot_len);
+        // every launch that reaches this march has single-segment axes (so_fast_eligible: size1 == 0).  Saying so takes
+        // so_axis_m2g's second segment out of the block: a per-lane branch, two divisions and two kernarg dwords per axis
+        auto axis = [](so_axis A) __attribute__((always_inline)) { A.size1 = 0.0f; return A; };
+        const float gh = so_grid_coord(so_axis_m2g(axis(so_reload_args().map.h), py, slope), so_reload_args().map.h.tot_len);
         __builtin_amdgcn_sched_barrier(0);
-        const float gw = so_grid_coord(so_axis_m2g(so_reload_args().map.w, px, slope), so_reload_args().map.w.tot_len);
+        const float gw = so_grid_coord(so_axis_m2g(axis(so_reload_args().map.w), px, slope), so_reload_args().map.w.tot_len);
         __builtin_amdgcn_sched_barrier(0);
-        const float gd = so_grid_coord(so_axis_m2g(so_reload_args().map.d, pz, slope), so_reload_args().map.d.tot_len);
+        const float gd = so_grid_coord(so_axis_m2g(axis(so_reload_args().map.d), pz, slope), so_reload_args().map.d.tot_len);
         return so_cell_of(gh, gw, gd);
     };
 
@@ -1004,26 +1025,27 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
                 so_gather_sdf_buf(rs, H, W, D, h0, w0, d0, v);
                 p0 = so_f32x2{v[0], v[4]}; p1 = so_f32x2{v[1], v[5]}; p2 = so_f32x2{v[2], v[6]}; p3 = so_f32x2{v[3], v[7]};
             };
-            bool loaded = false;                 // wave-uniform
-            if constexpr (FACE_SAFE) {
-                // decided before the corners are loaded, so that no corner is live across the canonical recomputation
-                if (__any(near_face(fh, fw, fd))) {
-                    int h0 = cur.h0, w0 = cur.w0, d0 = cur.d0;
-                    bool moved = false;
-                    if (near_face(fh, fw, fd)) {
-                        const so_cell c = canon_cell(i);
-                        if (c.h0 != h0 || c.w0 != w0 || c.d0 != d0) {   // the canonical order lands next door
-                            h0 = c.h0; w0 = c.w0; d0 = c.d0;
-                            fh = c.fh1; fw = c.fw1; fd = c.fd1;
-                            moved = true;
-                        }
-                    }
-                    // a moved lane reads its new cell from the volume, the wave's other lanes the same corner values
-                    // there as in their brick records
-                    if (__any(moved)) { gather(h0, w0, d0); loaded = true; }
+            // A step with no lane near a face (all but ~2 % of the interpolated wave-steps) falls through both
+            // branches below, from the test to its record loads; the near-face block is marked unlikely and laid out behind the
+            // loop body.  It is decided before any corner is loaded, so that no corner is live across the canonical
+            // recomputation.  (With the record loads written into both arms of an if / else instead of behind the `moved_any`
+            // flag the compiler keeps the flag, adds three register copies and a vmcnt(0) in front of the loads: 3.7 % slower.)
+            bool moved_any = false;              // wave-uniform
+            if (FACE_SAFE && __builtin_expect(__any(near_face(fh, fw, fd)), 0)) {
+                int h0 = cur.h0, w0 = cur.w0, d0 = cur.d0;
+                bool moved = false;
+                if (near_face(fh, fw, fd)) {
+                    const so_cell c = canon_cell(i);
+                    moved = (c.h0 != h0) | (c.w0 != w0) | (c.d0 != d0);   // the canonical order lands next door
+                    h0 = moved ? c.h0 : h0; w0 = moved ? c.w0 : w0; d0 = moved ? c.d0 : d0;
+                    fh = moved ? c.fh1 : fh; fw = moved ? c.fw1 : fw; fd = moved ? c.fd1 : fd;
                 }
+                // a moved lane reads its new cell from the volume, the wave's other lanes the same corner values
+                // there as in their brick records
+                moved_any = __any(moved);
+                if (moved_any) gather(h0, w0, d0);
             }
-            if (!loaded) {
+            if (__builtin_expect(!moved_any, 1)) {
                 if (IN_SURE || cur.all_interior) {
                     {   // the records of cells (h, w, d) and (h, w + 1, d) = the four corner pairs, in the register order
                         // so_trilerp_fast_pk takes them

@@ -139,7 +139,8 @@ class RenderConfig:
     exact: bool = False               # canonical IEEE op order (bit-exact with the oracle), slower
     brick: bool = True                # fast path: re-pack the SDF volume into 16-byte corner records per launch
     skip: bool = True                 # fast path + brick: composite saturated free-space samples without interpolating
-    face_safe: bool = True            # fast path: canonical cell selection within a few ulp of a voxel face (~6 % slower)
+    face_safe: bool = True            # fast path: canonical cell selection within a few ulp of a voxel face (skip marcher on
+                                      # the cfg2 frame, MI355X: 7.2 % slower at inv_s 20, 3.5 % at 200)
     ahead: bool = True                # SDF-only per-ray launches with brick + skip: code-ahead skip marcher (A/B)
     ray_per_lane: bool = False        # ignored since ABI 30 (was: per-sample launches through ray-per-lane kernels, an A/B switch)
     bwd_scatter: str = 'auto'         # backward: 'binned' = brick-binned LDS scatter of the volume gradients (needs a scratch
