@@ -665,6 +665,45 @@ int selfocc_reproj_bwd(const so_reproj_args *args, const float *g_l1,
                        const float *g_rgb_combine, float *g_weights, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The fused temporal reprojection term on images of C channels (the `dims` knob of both reprojection losses, e.g. the
+ * feature-metric loss on (C, Hi, Wi) feature maps): the semantics of selfocc_reproj_fwd / _bwd with 3 replaced by C.
+ *   weights, ts (R, S); deltas (R, S) or NULL; pix (R, 2) pixel (u, v); curr (R, C) = the current image at the ray pixels;
+ *   T_prev / T_next (4,4) row-major; img_prev / img_next CHANNEL-LAST (Hi, Wi, img_stride) float32, base 16-byte aligned,
+ *   img_stride % 4 == 0 and >= C.  Channels C .. img_stride-1 of a pixel are padding: no output depends on them (a NaN
+ *   there reaches none).
+ * Projection, perspective divide (eps 1e-5), in-image masks against (img_h, img_w), w / delta, general-mask zeroing, the
+ * clamped per-ray renormalisation and any_valid read no image: `wnorm` and `any_valid` are bit for bit those of
+ * selfocc_reproj_fwd on the same geometry, at every C.  Per sample and frame f the warped value is
+ * grid_sample(bilinear, border, align_corners=True) of the frame's image at pixel / (img_w, img_h), and
+ *   diff_f = (sum_c |curr_c - warped_c|) / C,   diff = (m_prev diff_prev + m_next diff_next) / max(m_prev + m_next, 1),
+ *   comb_c = (m_prev warped_prev_c + m_next warped_next_c) / max(m_prev + m_next, 1),
+ *   l1 = sum_s w'_s diff_s,   combine_c = sum_s w'_s comb_s,c      (w' = masked, per-ray renormalised weights).
+ * Backward: g_weights_s = sc_s (a_s - abar) / wtot with a_s = g_l1 diff_s + g_combine . comb_s, abar = sum_s w'_s a_s
+ * (0 when the weight sum sits on its clamp), sc_s the sample's 1 / delta (1 without deltas; 0 when masked); the taps are
+ * recomputed, nothing per-sample is stored by the forward.  g_l1 / g_combine may be NULL (taken as zero).
+ * No floating-point atomics: results are run-to-run identical.  l1 / combine / any_valid / wnorm may each be NULL.
+ * Refused on the host, before any HIP call, by name in selfocc_last_error(): C outside 1..512; img_stride < C or not a
+ * multiple of 4; S outside 1..512; a NULL input; an image base that is not 16-byte aligned; a bad image size (Hi, Wi
+ * outside 1..2^24, img_h or img_w <= 0); g_weights NULL in the backward.  R == 0 succeeds without a launch (after the
+ * checks of C, img_stride and S).  New entry points: SELFOCC_ABI_VERSION is unchanged.
+ * ---------------------------------------------------------------------------------- */
+typedef struct so_reproj_c_args {
+    const float *weights, *ts, *deltas;   /* (R, S); deltas may be NULL                                  */
+    const float *pix, *curr;              /* (R, 2) pixel (u, v); (R, C) current image at the ray pixels */
+    const float *T_prev, *T_next;         /* (4, 4) row-major                                            */
+    const float *img_prev, *img_next;     /* CHANNEL-LAST (Hi, Wi, img_stride) float32, 16-byte aligned  */
+    int32_t R, S, Hi, Wi, C, img_stride;  /* 1 <= C <= 512; img_stride % 4 == 0, img_stride >= C         */
+    float img_h, img_w;
+    float *l1, *combine, *any_valid;      /* (R), (R, C), (R)                                            */
+    float *wnorm;                         /* (R, S) or NULL                                              */
+} so_reproj_c_args;
+
+int selfocc_reproj_c_fwd(const so_reproj_c_args *args, void *stream);
+
+int selfocc_reproj_c_bwd(const so_reproj_c_args *args, const float *g_l1, const float *g_combine /* (R, C) */,
+                         float *g_weights /* (R, S) */, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Per ray and temporal frame, the sample with the largest warped-photometric weight, and a per-sample value read
  * there: the sdf_loss term of ReprojLossMonoMultiNew (loss/reproj_loss_mono_multi_new.py:265-270).  One launch per
  * camera serves both frames; no image is read.

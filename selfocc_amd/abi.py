@@ -127,6 +127,19 @@ class SoReprojArgs(C.Structure):
     ]
 
 
+class SoReprojCArgs(C.Structure):
+    _fields_ = [
+        ("weights", _p), ("ts", _p), ("deltas", _p),
+        ("pix", _p), ("curr", _p),
+        ("T_prev", _p), ("T_next", _p),
+        ("img_prev", _p), ("img_next", _p),
+        ("R", _i), ("S", _i), ("Hi", _i), ("Wi", _i), ("C", _i), ("img_stride", _i),
+        ("img_h", _f), ("img_w", _f),
+        ("l1", _p), ("combine", _p), ("any_valid", _p),
+        ("wnorm", _p),
+    ]
+
+
 class SoReprojPickArgs(C.Structure):
     _fields_ = [
         ("weights", _p), ("ts", _p), ("deltas", _p),
@@ -216,6 +229,8 @@ SYMBOLS = {
     "selfocc_ssim_bwd": (C.c_int, [_p] * 4 + [_i] * 4 + [_p, _p, _p, _p]),
     "selfocc_reproj_fwd": (C.c_int, [C.POINTER(SoReprojArgs), _p]),
     "selfocc_reproj_bwd": (C.c_int, [C.POINTER(SoReprojArgs), _p, _p, _p, _p]),
+    "selfocc_reproj_c_fwd": (C.c_int, [C.POINTER(SoReprojCArgs), _p]),
+    "selfocc_reproj_c_bwd": (C.c_int, [C.POINTER(SoReprojCArgs), _p, _p, _p, _p]),
     "selfocc_reproj_pick_fwd": (C.c_int, [C.POINTER(SoReprojPickArgs), _p]),
     "selfocc_reproj_pick_bwd": (C.c_int, [_p, _p, _p, _i, _i, _p]),
     "selfocc_depth_metric_ws_bytes": (C.c_size_t, [C.POINTER(SoDepthMetricArgs)]),

@@ -5,6 +5,12 @@ ReprojLossMonoMultiNew        <- loss/reproj_loss_mono_multi_new.py:41-287
 The per-sample chain (projection, bilinear fetch, masks, per-ray renormalised reductions)
 is ONE fused HIP launch per camera (reproj.py -> csrc/reproj.hip); SSIM, the auto-mask
 minimum and the means stay in torch on the (R, 3) lattice images.
+
+``dims`` (default 3) is the channel count of the images that are warped, as in the reference.  With 3-channel images and
+``dims == 3`` the planar 3-channel kernel runs.  Any other count (``dims=K`` with ``curr_imgs / prev_imgs / next_imgs``
+mapped to K-channel feature maps in ``input_dict``: the feature-metric reprojection loss) goes through the channel-generic
+kernel (csrc/reproj_c.hip) on channel-last copies of the previous / next maps, made once per camera and call; the maps may
+have any resolution, pixels are normalised by ``img_size``.
 """
 import numpy as np
 import torch
@@ -13,7 +19,7 @@ import torch.nn.functional as F
 
 from .._lib import upload
 from ..registry import OPENOCC_LOSS
-from ..reproj import ReprojSampleFunction, reproj_pick
+from ..reproj import ReprojSampleCFunction, ReprojSampleFunction, channel_last, reproj_pick
 from .base import BaseLoss
 
 
@@ -103,6 +109,22 @@ class _ReprojBase(BaseLoss):
             t = torch.stack(vals, dim=0).to(like)
         return t.reshape(-1, num_cams, 4, 4).float()
 
+    def _sampler(self, curr_imgs, prev_imgs, next_imgs, shard):
+        """-> (the per-sample Function, what turns one camera's previous / next image into its image argument).
+        3-channel images with dims == 3: the planar kernel on the images as they are.  Otherwise the images must all have
+        ``dims`` channels, and the channel-generic kernel runs on channel-last copies."""
+        chans = tuple(int(x.shape[2]) for x in (curr_imgs, prev_imgs, next_imgs))
+        if self.dims == 3 and chans == (3, 3, 3):
+            return ReprojSampleFunction, lambda img: img.float()
+        if chans != (self.dims,) * 3:
+            raise ValueError(f"{type(self).__name__}: dims = {self.dims} but curr_imgs / prev_imgs / next_imgs have "
+                             f"{chans[0]} / {chans[1]} / {chans[2]} channels (shapes {tuple(curr_imgs.shape)}, "
+                             f"{tuple(prev_imgs.shape)}, {tuple(next_imgs.shape)}): dims must be the channel count of all three")
+        if shard is not None:
+            raise NotImplementedError(f"{type(self).__name__}(dims={self.dims}) with a ray-sharded head is not supported "
+                                      f"(the per-ray gather packs 3 channels): run dims != 3 with NeuSHead(ray_shard=False)")
+        return ReprojSampleCFunction, channel_last
+
     @staticmethod
     def _local_rows(shard, per_ray_full):
         """rows of a full-lattice per-ray tensor (R, ...) of ONE camera that belong to this rank's block"""
@@ -164,23 +186,24 @@ class ReprojLossMonoMultiNewCombine(_ReprojBase):
         T_prev = self._transforms(metas, 'img2prevImg', ts[0], num_cams)[0]
         T_next = self._transforms(metas, 'img2nextImg', ts[0], num_cams)[0]
         pix = ms_rays.float().contiguous()
+        from ..dist import shard_of
+        shard = shard_of(weights)
+        sample, as_image = self._sampler(curr_imgs, prev_imgs, next_imgs, shard)
         # The reference loops over the cameras in python (reproj_loss_mono_multi_new_combine.py:108-201).  Only
         # the fused sampling kernel is per camera here; the lattice sampling, SSIM, masks and the minimum run
         # batched over the cameras (same per-element arithmetic, ~6x fewer launches of tiny kernels).
         rgb_curr = self._sample_lattice_all(pix, curr_imgs[0].float(), 'border')                   # (N, R, 3)
         # ray-sharded head: weights / ts hold this rank's rows only — the per-sample kernel runs on them, its three
         # per-ray results are gathered into the full lattice (everything below needs whole images: SSIM, minimum)
-        from ..dist import shard_of
-        shard = shard_of(weights)
         rays_k = num_rays if shard is None else shard.rays_per_cam_local
         pix_k = pix if shard is None else shard.pix_local.float().contiguous()
         l1s, combs, valids = [], [], []
         for cam, (weight, t) in enumerate(zip(weights, ts)):
-            l1, comb, any_valid = ReprojSampleFunction.apply(
+            l1, comb, any_valid = sample.apply(
                 weight.reshape(rays_k, -1), t.reshape(rays_k, -1),
                 None if deltas is None else deltas[cam].detach().reshape(rays_k, -1), pix_k,
                 rgb_curr[cam] if shard is None else self._local_rows(shard, rgb_curr[cam]).contiguous(),
-                T_prev[cam], T_next[cam], prev_imgs[0, cam].float(), next_imgs[0, cam].float(),
+                T_prev[cam], T_next[cam], as_image(prev_imgs[0, cam]), as_image(next_imgs[0, cam]),
                 self.img_size[0], self.img_size[1])
             l1s.append(l1); combs.append(comb); valids.append(any_valid)
         l1, comb, any_valid = torch.stack(l1s), torch.stack(combs), torch.stack(valids)             # (N, R[, 3])
@@ -235,6 +258,7 @@ class ReprojLossMonoMultiNew(_ReprojBase):
         invalid = _invalid_on(pix.device)
         from ..dist import shard_of
         shard = shard_of(weights)        # ray-sharded head: per-sample inputs are this rank's rows (see the Combine loss)
+        sample, as_image = self._sampler(curr_imgs, prev_imgs, next_imgs, shard)
         if self.sdf_loss:
             if sample_sdfs is None:
                 raise ValueError("ReprojLossMonoMultiNew(sdf_loss=True) needs 'sample_sdfs': map it in input_dict to the "
@@ -251,9 +275,9 @@ class ReprojLossMonoMultiNew(_ReprojBase):
             w2, t2 = weight.reshape(rays_k, -1), t.reshape(rays_k, -1)
             d2 = None if deltas is None else deltas[cam].detach().reshape(rays_k, -1)
             cands = []
-            for T, img in ((T_prev[cam], prev_imgs[0, cam].float()), (T_next[cam], next_imgs[0, cam].float())):
-                l1, comb, any_valid = ReprojSampleFunction.apply(w2, t2, d2, pix_k, target_k, T, invalid, img, img,
-                                                                 self.img_size[0], self.img_size[1])
+            for T, img in ((T_prev[cam], as_image(prev_imgs[0, cam])), (T_next[cam], as_image(next_imgs[0, cam]))):
+                l1, comb, any_valid = sample.apply(w2, t2, d2, pix_k, target_k, T, invalid, img, img,
+                                                   self.img_size[0], self.img_size[1])
                 if shard is not None:      # one camera's rows: gather as a 1-camera lattice
                     from ..render import RaySet
                     one = RaySet(img2lidar=shard.full.img2lidar[:1], nx=shard.full.nx, ny=shard.full.ny)
