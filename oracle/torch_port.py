@@ -227,14 +227,25 @@ def mean_iou_counts_port(outputs, targets, class_indices, empty_label, mask=None
 # trilinear (value identical to F.grid_sample(align_corners=True): tested) whose analytic
 # metre gradient is itself differentiable wrt the volume.  Run in float64.
 # ---------------------------------------------------------------------------------------
-def trilinear_explicit(mapping, vol_chw, xyz):
-    """vol_chw (C, H, W, D); xyz (n, 3) -> values (n, C), d value[:, 0] / d xyz (n, 3)."""
+def trilinear_explicit(mapping, vol_chw, xyz, slope_eps=None, slope_f64=False, drop_corner=None):
+    """vol_chw (C, H, W, D); xyz (n, 3) -> values (n, C), d value[:, 0] / d xyz (n, 3).
+
+    The mapping slope d grid / d metre is a forward difference.  Default: over 1e-3 m in the working dtype (in float32 that
+    alone costs 4e-4 .. 9e-4 of the metre gradient).  ``slope_eps``: another step in metres; ``slope_f64``: take the
+    difference in float64 whatever the working dtype.  Both mappings are linear per cell, so the difference is exact (to
+    float64 rounding) for every point whose cell also holds ``xyz + slope_eps``.
+    ``drop_corner`` (n,) long, -1 or a corner number 4 kh + 2 kw + kd: that corner of that point keeps its value and loses its
+    gradient wrt ``vol_chw`` (a deliberately defective scatter: the negative controls of tests/render_bwd_cases.py)."""
     C, H, W, D = vol_chw.shape
     g = mapping.meter2grid(xyz)                       # (n, 3) h, w, d (un-normalised)
     with torch.no_grad():
-        eps = 1e-3
-        gp = mapping.meter2grid(xyz + eps)
-        slope = (gp - g) / eps                         # piece-wise constant d grid / d metre (y->h, x->w, z->d)
+        eps = 1e-3 if slope_eps is None else slope_eps
+        if slope_f64:
+            x64 = xyz.double()
+            slope = ((mapping.meter2grid(x64 + eps) - mapping.meter2grid(x64)) / eps).to(xyz.dtype)
+        else:
+            gp = mapping.meter2grid(xyz + eps)
+            slope = (gp - g) / eps                     # piece-wise constant d grid / d metre (y->h, x->w, z->d)
         slope = torch.stack([slope[:, 1], slope[:, 0], slope[:, 2]], -1)   # metre order x, y, z
     g0 = torch.floor(g)
     fr = g - g0
@@ -247,6 +258,8 @@ def trilinear_explicit(mapping, vol_chw, xyz):
                 h, w, d = i0[:, 0] + kh, i0[:, 1] + kw, i0[:, 2] + kd
                 inb = (h >= 0) & (h < H) & (w >= 0) & (w < W) & (d >= 0) & (d < D)
                 v = vol_chw[:, h.clamp(0, H - 1), w.clamp(0, W - 1), d.clamp(0, D - 1)].T * inb[:, None]
+                if drop_corner is not None:
+                    v = torch.where((drop_corner == 4 * kh + 2 * kw + kd)[:, None], v.detach(), v)
                 fh = fr[:, 0] if kh else 1 - fr[:, 0]
                 fw = fr[:, 1] if kw else 1 - fr[:, 1]
                 fd = fr[:, 2] if kd else 1 - fr[:, 2]
@@ -259,8 +272,10 @@ def trilinear_explicit(mapping, vol_chw, xyz):
     return vals, grad
 
 
-def render_port_differentiable(mapping, vol_chw, n_rgb, n_sem, o, d, dn, cfg, inv_s, t_rand=None, bkgd_rays=None):
-    """Same algorithm as _render_chunk, every op differentiable wrt vol_chw and inv_s."""
+def render_port_differentiable(mapping, vol_chw, n_rgb, n_sem, o, d, dn, cfg, inv_s, t_rand=None, bkgd_rays=None,
+                               slope_eps=None, slope_f64=False, drop_corner=None):
+    """Same algorithm as _render_chunk, every op differentiable wrt vol_chw and inv_s.  ``slope_eps`` / ``slope_f64`` /
+    ``drop_corner`` (n_rays * S,): see trilinear_explicit."""
     S = cfg.n_samples
     nears, fars = aabb_collider(o, d, cfg.aabb, cfg.near_plane)
     bins = torch.linspace(0.0, 1.0, S + 1, dtype=o.dtype)[None, :]
@@ -275,7 +290,7 @@ def render_port_differentiable(mapping, vol_chw, n_rgb, n_sem, o, d, dn, cfg, in
     deltas = ends - starts
     mids = (starts + ends) / 2
     pos = o[:, None, :] + d[:, None, :] * (starts if cfg.sample_pos == 0 else mids)[..., None]
-    h, grad = trilinear_explicit(mapping, vol_chw, pos.reshape(-1, 3))
+    h, grad = trilinear_explicit(mapping, vol_chw, pos.reshape(-1, 3), slope_eps, slope_f64, drop_corner)
     sdf = h[:, 0].reshape(-1, S)
     grad = grad.reshape(-1, S, 3)
     true_cos = (d[:, None, :] * grad).sum(-1)
@@ -293,6 +308,7 @@ def render_port_differentiable(mapping, vol_chw, n_rgb, n_sem, o, d, dn, cfg, in
                starts=starts, ends=ends)
     if n_rgb:
         col = sh0_color(h[:, 1:1 + n_rgb]).reshape(-1, S, 3)
+        out['raw'] = h[:, 1:1 + n_rgb].reshape(-1, S, 3)      # before sh0_color (its relu has a kink)
         rgb = (weights[..., None] * col).sum(-2)
         if cfg.bkgd_mode == 1:
             rgb = rgb + torch.tensor(cfg.bkgd, dtype=o.dtype) * (1.0 - acc[:, None])
