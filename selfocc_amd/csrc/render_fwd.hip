@@ -274,7 +274,8 @@ SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g)
 // Deviates from the canonical order by a few ulp per op; parity tests bound it.
 // ---------------------------------------------------------------------------------------
 struct AxisK { float k1, k0; };
-SO_DEVFN AxisK so_axis_affine(const so_axis &A) {
+#define SO_HOSTDEVFN __host__ __device__ __forceinline__    // launch constants: the same expression on either side
+SO_HOSTDEVFN AxisK so_axis_affine(const so_axis &A) {
     AxisK k;
     k.k1 = A.size0 / A.range0;
     k.k0 = (A.off0 + A.off1) - A.start * k.k1;
@@ -352,9 +353,40 @@ SO_DEVFN void so_trilerp_fast_pk(so_f32x2 p0, so_f32x2 p1, so_f32x2 p2, so_f32x2
 // touching the corners: same results, ~1/4 of the vector instructions of a full step.
 constexpr float kSkipArg = 17.5f;
 constexpr float kAlphaFree = 1e-5f / (1.0f + 1e-5f);
-SO_DEVFN float so_skip_unit(const float aabb[6], int n_samples) {   // metres per code step: box diagonal / S / 255
+SO_HOSTDEVFN float so_skip_unit(const float aabb[6], int n_samples) {   // metres per code step: box diagonal / S / 255
     const float ex = aabb[3] - aabb[0], ey = aabb[4] - aabb[1], ez = aabb[5] - aabb[2];
     return sqrtf(ex * ex + ey * ey + ez * ez) / ((float)n_samples * 255.0f);
+}
+
+// ---- launch constants ---------------------------------------------------------------------------
+// What the skip marchers (so_march_fast_ahead) and the brick pass need of a launch and no ray or cell changes, computed once
+// on the host and passed by value as a kernel argument, instead of once per wave (three IEEE divisions for the axes, a
+// square root and a division for the skip unit) or per cell (sdf_brickify_kernel: four divisions and a square root).  The
+// host evaluates the device's own float32 expressions (so_axis_affine, so_skip_unit, the face margin as in so_march_fast):
+// IEEE division and square root are correctly rounded on either side and the library is built without contraction, so
+// every field is bit for bit what the kernels computed themselves — so_march_fast still does, and the tests that hold the
+// two routes equal compare host against device.  Nothing here depends on inv_s, which may live on the device alone.
+struct so_launch_consts {
+    AxisK kh, kw, kd;             // so_axis_affine of the three axes
+    float skip_unit;              // so_skip_unit
+    float face_m;                 // near-face margin in grid units (see so_march_fast)
+    float n_samples_f;            // (float)S
+    unsigned n_cells;             // H * W * D
+    unsigned codes_off;           // byte offset of the skip codes in the brick workspace: n_cells * 16
+    unsigned row_off;             // byte offset from a cell's record to that of (h, w + 1, d): D * 16
+};
+so_launch_consts so_make_launch_consts(const so_render_args &a) {
+    const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
+    so_launch_consts c;
+    c.kh = so_axis_affine(a.map.h); c.kw = so_axis_affine(a.map.w); c.kd = so_axis_affine(a.map.d);
+    c.skip_unit = so_skip_unit(a.aabb, a.n_samples);
+    const int maxdim = H > W ? (H > D ? H : D) : (W > D ? W : D);
+    c.face_m = 3.0f * 1.1920929e-7f * (float)(1u << (32 - __builtin_clz((unsigned)maxdim)));
+    c.n_samples_f = (float)a.n_samples;
+    c.n_cells = (unsigned)(H * W * D);
+    c.codes_off = c.n_cells * 16u;
+    c.row_off = (unsigned)D * 16u;
+    return c;
 }
 
 
@@ -871,7 +903,7 @@ struct AheadStep {
 };
 
 template <bool FACE_SAFE, class GeomFn>
-SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom) {
+SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_consts &c, int ray, GeomFn geom) {
     const int H = a.map.h.tot_len, W = a.map.w.tot_len, D = a.map.d.tot_len;
     const int S = a.n_samples;
     const RayGeom g = geom(a);
@@ -885,9 +917,10 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
     }
     float tnear, tfar;
     so_collide(a, g, tnear, tfar);
-    const float dt = (tfar - tnear) / (float)S;
+    // the launch's constants come from the host (so_launch_consts); what depends on the ray or on inv_s is computed here
+    const float dt = (tfar - tnear) / c.n_samples_f;
     const float inv_dn = 1.0f / g.dn;
-    const AxisK kh = so_axis_affine(a.map.h), kw = so_axis_affine(a.map.w), kd = so_axis_affine(a.map.d);
+    const AxisK kh = c.kh, kw = c.kw, kd = c.kd;
     const float t_off = (a.sample_pos == SO_SAMPLE_AT_START) ? tnear : tnear + 0.5f * dt;
     const float Gdh = g.dy * kh.k1, Gdw = g.dx * kw.k1, Gdd = g.dz * kd.k1;
     const float G0h = fmaf(g.oy, kh.k1, kh.k0) + Gdh * t_off;
@@ -896,12 +929,11 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
     const float s2 = so_inv_s(a) * 1.44269504088896341f;
     const float hdt = 0.5f * dt, hdt_s2 = hdt * s2;
     const float *__restrict__ vol = a.sdf_vol;
-    const unsigned n_cells = (unsigned)(H * W * D);
+    const unsigned n_cells = c.n_cells, codes_off = c.codes_off, row_off = c.row_off;
     const __amdgpu_buffer_rsrc_t rb = so_make_rsrc(a.sdf_brick, (size_t)n_cells * 17);   // 16-B records, then the code bytes
     const __amdgpu_buffer_rsrc_t rs = so_make_rsrc(vol, (size_t)n_cells * 4);
-    const int rcode = max((int)ceilf(dt / so_skip_unit(a.aabb, S)), 1);
-    const int maxdim = max(H, max(W, D));
-    const float face_m = 3.0f * 1.1920929e-7f * (float)(1u << (32 - __builtin_clz((unsigned)maxdim)));
+    const int rcode = max((int)ceilf(dt / c.skip_unit), 1);
+    const float face_m = c.face_m;
 
     float T = 1.0f, acc = 0.0f, dsum = 0.0f, best_w = -1.0f, best_t = 0.0f;
 
@@ -946,11 +978,11 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
     auto locate = [&](const int i, AheadStep &st, auto in_sure) __attribute__((always_inline)) {
         place(i, st);
         if constexpr (decltype(in_sure)::value) {
-            st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 16u, 0);
+            st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, codes_off, 0);
         } else {
             st.all_interior = interior(st);
             st.code = 0u;
-            if (st.all_interior) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 16u, 0);
+            if (st.all_interior) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, codes_off, 0);
         }
     };
     auto near_face = [&](float fh, float fw, float fd) __attribute__((always_inline)) {
@@ -1050,7 +1082,7 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
                     {   // the records of cells (h, w, d) and (h, w + 1, d) = the four corner pairs, in the register order
                         // so_trilerp_fast_pk takes them
                         // (issuing these loads before locate() above, to run it under them, measured 9 % SLOWER)
-                        const so_f4v lo = so_bload4(rb, cur.cell * 16u, 0u), hi = so_bload4(rb, cur.cell * 16u, (unsigned)D * 16u);
+                        const so_f4v lo = so_bload4(rb, cur.cell * 16u, 0u), hi = so_bload4(rb, cur.cell * 16u, row_off);
                         p0 = lo.xy; p1 = lo.zw; p2 = hi.xy; p3 = hi.zw;
                     }
                 } else {
@@ -1080,7 +1112,7 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, int ray, GeomFn geom)
             const float t_mid = fmaf(st.fi, dt, tnear + hdt);
             ++i;
             place(i, st);
-            st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, n_cells * 16u, 0);
+            st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, codes_off, 0);
             const float w = kAlphaFree * T;
             T = T * ((1.0f - kAlphaFree) + 1e-7f);
             acc = acc + w;
@@ -1162,14 +1194,12 @@ constexpr bool so_face_safe(March m) { return m == March::FastFaceSafe || m == M
 template <class ROW>
 constexpr bool so_is_staged(March m) { return so_is_fast(m) && !ROW::BF16 && ROW::NF >= 4; }
 
-// a spherical-harmonics row has the canonical marches only
+// a spherical-harmonics row has the canonical marches only; the skip marchers have kernels of their own (so_launch_consts)
 template <class ROW, March MODE, class GeomFn>
 SO_DEVFN void so_march(const so_render_args &a, int ray, GeomFn geom) {
+    static_assert(!so_is_skip(MODE), "skip marcher: the kernels that take so_launch_consts");
     if constexpr (MODE == March::CanonicalUpscale) {
         so_march_exact<ROW, SO_MAP_UPSCALE>(a, ray, geom(a));
-    } else if constexpr (so_is_skip(MODE)) {
-        static_assert(ROW::NF == 0, "skip marcher: SDF-only launches");
-        so_march_fast_ahead<so_face_safe(MODE)>(a, ray, geom);
     } else if constexpr (so_is_fast(MODE)) {
         so_march_fast<ROW, false, so_face_safe(MODE)>(a, ray, geom);
     } else {
@@ -1188,13 +1218,14 @@ SO_DEVFN void so_march(const so_render_args &a, int ray, GeomFn geom) {
 // the 10.9 us of the 32-byte pass: its record stores were 64 bytes apart from lane to lane.)  With D % 4 == 0 (uniform) the
 // 4 code bytes of an aligned quad of lanes leave as one dword.
 __global__ __launch_bounds__(256) void sdf_brickify_kernel(const float *__restrict__ vol, float *__restrict__ brick,
-                                                           int H, int W, int D, so_render_args a, int with_codes) {
+                                                           int H, int W, int D, so_render_args a, int with_codes,
+                                                           so_launch_consts c) {
     const int h = blockIdx.x, h1 = min(h + 1, H - 1);
     const size_t n_cells = (size_t)H * W * D;
     uint8_t *codes = (uint8_t *)(brick + n_cells * 4);
     // blockDim.x is a power of two: with D % 4 == 0 the lanes 4 q .. 4 q + 3 of a wave hold 4 consecutive cells of one column
     const bool quads = (D & 3) == 0 && (blockDim.x & 3) == 0;
-    const float kd = a.map.d.size0 / a.map.d.range0, kw = a.map.w.size0 / a.map.w.range0, kh = a.map.h.size0 / a.map.h.range0;
+    const float kd = c.kd.k1, kw = c.kw.k1, kh = c.kh.k1;      // size0 / range0 of each axis, from the host
     for (int w = blockIdx.y * blockDim.y + threadIdx.y; w < W; w += gridDim.y * blockDim.y) {
         const int w1 = min(w + 1, W - 1);
         const float *r00 = vol + ((size_t)h * W + w) * D, *r01 = vol + ((size_t)h * W + w1) * D;
@@ -1216,7 +1247,7 @@ __global__ __launch_bounds__(256) void sdf_brickify_kernel(const float *__restri
                 const float G = sqrtf((gd * gd + gw * gw) + gh * gh) * 1.001f + 1e-20f;
                 const float slack = m - kSkipArg / so_inv_s(a);                       // metres above the saturation level
                 if (slack > 0.0f && so_inv_s(a) > 0.0f) {
-                    const float allow = 2.0f * slack / G / so_skip_unit(a.aabb, a.n_samples);   // in code units
+                    const float allow = 2.0f * slack / G / c.skip_unit;   // in code units
                     code = (unsigned)fminf(floorf(allow * 0.999f), 255.0f);
                 }
             }
@@ -1303,27 +1334,52 @@ __global__ __launch_bounds__(256, so_min_blocks<ROW>()) void render_fwd_pixgrid(
         pixgrid_body<ROW, MODE>(a, tiles_x, tiles_y);
     }
 }
-// The skip marchers (bench.py's kernel) at 8 waves / SIMD need <= 64 VGPRs AND <= 80 SGPRs: a CU admits
+
+// The skip marchers: overloads of the two kernel templates that take the launch's constants from the host.  `a` stays the
+// first argument, at the start of the kernarg segment, where so_reload_args reads it.
+template <class ROW, March MODE>
+__global__ __launch_bounds__(256, 1) void render_fwd_explicit(so_render_args a, so_launch_consts c) {
+    static_assert(so_is_skip(MODE) && ROW::NF == 0 && ROW::NB == 0, "skip marcher: SDF-only launches");
+    int ray = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ray >= a.n_rays) return;
+    auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_explicit_ray(a, ray); };
+    so_march_fast_ahead<so_face_safe(MODE)>(a, c, ray, geom);
+}
+// Pixel grid (bench.py's kernel): launched on the grid (tiles_x, tiles_y, n_cams), so the block reads its tile and camera
+// from blockIdx where so_tile_pixel divides the linear index twice (two v_rcp_iflag -> v_readfirstlane round trips in
+// front of any ray work).  Blocks are dispatched x fastest, then y, then z: the linear order as before.
+// At 8 waves / SIMD the kernel needs <= 64 VGPRs AND <= 80 SGPRs: a CU admits
 // floor(800 / (ceil(sgpr / 16) * 16 + 16)) blocks of 256 threads, 7 at 82 - 96 SGPRs although the compiler's occupancy says 8.
 // Left alone the allocator spends 84 (constants the rare canonical branch needs, hoisted); capped it fits in 80 without spilling.
-template <>
-__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<so_row<0, false>, March::Skip>(
-    so_render_args a, int tiles_x, int tiles_y) {
-    pixgrid_body<so_row<0, false>, March::Skip>(a, tiles_x, tiles_y);
+template <class ROW, March MODE>
+__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid(so_render_args a, so_launch_consts c) {
+    static_assert(so_is_skip(MODE) && ROW::NF == 0 && ROW::NB == 0, "skip marcher: SDF-only launches");
+    const int cam = blockIdx.z, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ix = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), iy = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (ix >= a.nx || iy >= a.ny) return;
+    const int ray = (cam * a.ny + iy) * a.nx + ix;
+    auto geom = [&](const so_render_args &a) __attribute__((always_inline)) { return so_pixel_ray(a, cam, ix, iy); };
+    so_march_fast_ahead<so_face_safe(MODE)>(a, c, ray, geom);
 }
-template <>
-__global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_sgpr(80))) void render_fwd_pixgrid<so_row<0, false>, March::SkipFaceSafe>(
-    so_render_args a, int tiles_x, int tiles_y) {
-    pixgrid_body<so_row<0, false>, March::SkipFaceSafe>(a, tiles_x, tiles_y);
+// gridDim.y and gridDim.z end at 65 535
+bool so_skip_grid_fits(const so_render_args &a) {
+    return a.ray_mode == SO_RAYS_EXPLICIT || ((a.ny + 15) / 16 <= 65535 && a.n_cams <= 65535);
 }
 
 template <class ROW, March MODE>
 int launch_fwd(const so_render_args &a, hipStream_t st) {
-    if (a.ray_mode == SO_RAYS_EXPLICIT) {
+    const int tiles_x = (a.nx + 15) / 16, tiles_y = (a.ny + 15) / 16;
+    if constexpr (so_is_skip(MODE)) {
+        const so_launch_consts c = so_make_launch_consts(a);
+        if (a.ray_mode == SO_RAYS_EXPLICIT) {
+            hipLaunchKernelGGL((render_fwd_explicit<ROW, MODE>), dim3((a.n_rays + 255) / 256), dim3(256), 0, st, a, c);
+        } else {
+            hipLaunchKernelGGL((render_fwd_pixgrid<ROW, MODE>), dim3(tiles_x, tiles_y, a.n_cams), dim3(256), 0, st, a, c);
+        }
+    } else if (a.ray_mode == SO_RAYS_EXPLICIT) {
         int blocks = (a.n_rays + 255) / 256;
         hipLaunchKernelGGL((render_fwd_explicit<ROW, MODE>), dim3(blocks), dim3(256), 0, st, a);
     } else {
-        int tiles_x = (a.nx + 15) / 16, tiles_y = (a.ny + 15) / 16;
         int blocks = tiles_x * tiles_y * a.n_cams;
         hipLaunchKernelGGL((render_fwd_pixgrid<ROW, MODE>), dim3(blocks), dim3(256), 0, st, a, tiles_x, tiles_y);
     }
@@ -1338,7 +1394,7 @@ void so_launch_brickify(const so_render_args &a, hipStream_t st, int with_codes)
     while (qx < D && qx < 256) qx *= 2;
     const int wy = 256 / qx;
     hipLaunchKernelGGL(sdf_brickify_kernel, dim3(H, min((W + wy - 1) / wy, 65535)), dim3(qx, wy), 0, st, a.sdf_vol, a.sdf_brick,
-                       H, W, D, a, with_codes);
+                       H, W, D, a, with_codes, so_make_launch_consts(a));
 }
 
 // the fast march needs g(t) affine in t (no jitter, single-segment axes, the linear mapping kind) and so_cell_index's 24 bits
@@ -1364,7 +1420,8 @@ int dispatch(const so_render_args &a, hipStream_t st) {
         if (a.sdf_brick) so_launch_brickify(a, st, (CAN_SKIP && !(a.flags & SO_FLAG_NO_SKIP)) ? 1 : 0);
         const bool face_safe = ROW::MASKED || !(a.flags & SO_FLAG_NO_FACE_SAFE);
         if constexpr (CAN_SKIP) {
-            if (a.sdf_brick && !(a.flags & (SO_FLAG_NO_SKIP | SO_FLAG_NO_AHEAD)))
+            // a lattice too tall or with too many cameras for the skip marcher's 3-D grid takes the step-by-step march
+            if (a.sdf_brick && !(a.flags & (SO_FLAG_NO_SKIP | SO_FLAG_NO_AHEAD)) && so_skip_grid_fits(a))
                 return face_safe ? launch_fwd<ROW, March::SkipFaceSafe>(a, st) : launch_fwd<ROW, March::Skip>(a, st);
         }
         if constexpr (!ROW::MASKED) {
