@@ -394,42 +394,6 @@ __global__ __launch_bounds__(256) void msda_bwd_kernel(const float *__restrict__
 // Besides the rate, f64 accumulation makes a band's sums order-independent to ~1e-16 relative (only the
 // float flush of several segments into one band is order-dependent).
 // ---------------------------------------------------------------------------------------
-constexpr int kKeyOutside = -32768;
-
-template <int QL>
-SO_DEVFN float so_team_sum(float x) {   // sum over the QL lanes of a channel team, result in every lane
-    if constexpr (QL >= 2)
-        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true));  // [1,0,3,2]
-    if constexpr (QL >= 4)
-        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, true));  // [2,3,0,1]
-    if constexpr (QL >= 8) x += __shfl_xor(x, 4, 64);
-    return x;
-}
-
-// team step I: the team computes value(corner k) . g_out for the point owned by its sub-lane I
-template <int D, int I>
-SO_DEVFN void so_bwd_team_step(const float *__restrict__ value, const float *__restrict__ g_out, int s,
-                               const int (&goff)[4], int gq32, float (&dot)[4]) {
-    constexpr int QL = D / 4;
-    const int gqi = so_team_bcast<QL, I>(gq32);
-    const float4 go = *(const float4 *)(g_out + (size_t)gqi * D + 4 * s);
-    float part[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int off = so_team_bcast<QL, I>(goff[k]);
-        const float4 t = *(const float4 *)(value + off + 4 * s);
-        part[k] = t.x * go.x;
-        part[k] = fmaf(t.y, go.y, part[k]);
-        part[k] = fmaf(t.z, go.z, part[k]);
-        part[k] = fmaf(t.w, go.w, part[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float d = so_team_sum<QL>(part[k]);
-        if (s == I) dot[k] = d;
-    }
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void msda_bwd_point_kernel(const float *__restrict__ value,
                                                              const int32_t *__restrict__ shapes,
@@ -471,18 +435,7 @@ __global__ __launch_bounds__(256) void msda_bwd_point_kernel(const float *__rest
     for (int k = 0; k < 4; ++k) goff[k] = vbase + bl.off[k];
     const int s = threadIdx.x & (QL - 1);
     float dot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    so_bwd_team_step<D, 0>(value, g_out, s, goff, (int)gq, dot);
-    if constexpr (QL > 1) so_bwd_team_step<D, 1>(value, g_out, s, goff, (int)gq, dot);
-    if constexpr (QL > 2) {
-        so_bwd_team_step<D, 2>(value, g_out, s, goff, (int)gq, dot);
-        so_bwd_team_step<D, 3>(value, g_out, s, goff, (int)gq, dot);
-    }
-    if constexpr (QL > 4) {
-        so_bwd_team_step<D, 4>(value, g_out, s, goff, (int)gq, dot);
-        so_bwd_team_step<D, 5>(value, g_out, s, goff, (int)gq, dot);
-        so_bwd_team_step<D, 6>(value, g_out, s, goff, (int)gq, dot);
-        so_bwd_team_step<D, 7>(value, g_out, s, goff, (int)gq, dot);
-    }
+    so_bwd_team_dots<D>(value, MsdaGoRows{g_out, (int)gq}, s, goff, dot, QL);
     if (!live) return;
     float ga = 0.0f, gx = 0.0f, gy = 0.0f;
     if (bl.any) {
@@ -499,32 +452,10 @@ __global__ __launch_bounds__(256) void msda_bwd_point_kernel(const float *__rest
     *(float2 *)(g_loc + 2 * idx) = make_float2(gx, gy);
     const int q = (int)(bq - (long long)b * dm.nq);
     const int p = pt - l * dm.P;
+    // everything the band kernel needs of this point, in ITS order (points of one (b, h, level) contiguous)
     const size_t ki = ((((size_t)b * dm.heads + h) * dm.L + l) * dm.nq + q) * dm.P + p;
     keys[ki] = (int16_t)(bl.any ? bl.h_low : kKeyOutside);
-    // everything the band kernel needs of this point, in ITS order (points of one (b, h, level) contiguous)
-    recs[ki] = make_float4(bl.lh, bl.lw, aw, __int_as_float((int)(((unsigned)bl.h_low << 16) | ((unsigned)bl.w_low & 0xffffu))));
-}
-
-// team step I with the g_out quarter already in registers (all lanes of a team share the group)
-template <int D, int I, typename VT>
-SO_DEVFN void so_bwd_team_step_g(const VT *__restrict__ value, const float4 &go, int s, const int (&goff)[4],
-                                 float (&dot)[4]) {
-    constexpr int QL = D / 4;
-    float part[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int off = so_team_bcast<QL, I>(goff[k]);
-        const float4 t = so_ld4(value + off + 4 * s);
-        part[k] = t.x * go.x;
-        part[k] = fmaf(t.y, go.y, part[k]);
-        part[k] = fmaf(t.z, go.z, part[k]);
-        part[k] = fmaf(t.w, go.w, part[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float d = so_team_sum<QL>(part[k]);
-        if (s == I) dot[k] = d;
-    }
+    recs[ki] = make_float4(bl.lh, bl.lw, aw, so_band_cell(bl.h_low, bl.w_low));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -641,18 +572,7 @@ __global__ __launch_bounds__(256) void msda_fused_bwd_point_kernel(const VT *__r
 #pragma unroll
         for (int k = 0; k < 4; ++k) goff[k] = own ? vbase + bl.off[k] : 0;
         float dot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        so_bwd_team_step_g<D, 0>(value, go, s, goff, dot);
-        if constexpr (QL > 1) so_bwd_team_step_g<D, 1>(value, go, s, goff, dot);
-        if constexpr (QL > 2) {
-            so_bwd_team_step_g<D, 2>(value, go, s, goff, dot);
-            so_bwd_team_step_g<D, 3>(value, go, s, goff, dot);
-        }
-        if constexpr (QL > 4) {
-            so_bwd_team_step_g<D, 4>(value, go, s, goff, dot);
-            so_bwd_team_step_g<D, 5>(value, go, s, goff, dot);
-            so_bwd_team_step_g<D, 6>(value, go, s, goff, dot);
-            so_bwd_team_step_g<D, 7>(value, go, s, goff, dot);
-        }
+        so_bwd_team_dots<D>(value, go, s, goff, dot, QL);
         if (own) {
             float gx = 0.0f, gy = 0.0f;
             if (bl.any) {
@@ -669,7 +589,7 @@ __global__ __launch_bounds__(256) void msda_fused_bwd_point_kernel(const VT *__r
             sum_l = fmaf(aw, ga[r], sum_l);
             const size_t ki = ((((size_t)b * dm.heads + h) * dm.L + l) * dm.nq + q) * dm.P + pp;
             keys[ki] = (int16_t)(bl.any ? bl.h_low : kKeyOutside);
-            recs[ki] = make_float4(bl.lh, bl.lw, aw, __int_as_float((int)(((unsigned)bl.h_low << 16) | ((unsigned)bl.w_low & 0xffffu))));
+            recs[ki] = make_float4(bl.lh, bl.lw, aw, so_band_cell(bl.h_low, bl.w_low));
         }
     }
 #pragma unroll
@@ -794,17 +714,18 @@ __global__ __launch_bounds__(256) void msda_cross_bwd_point_kernel(const VT *__r
                     for (int c = 0; c < 4; ++c) goff[c] = __builtin_amdgcn_ds_permute(dst, goff[c]);
                 }
             }
-            if (steps > 0) so_bwd_team_step_g<D, 0>(value, go, s, goff, dot);
-            if constexpr (QL > 1) { if (steps > 1) so_bwd_team_step_g<D, 1>(value, go, s, goff, dot); }
+            // (so_bwd_team_dots written out: through the helper 8 of these 20 kernels compile to another schedule)
+            if (steps > 0) so_bwd_team_step<D, 0>(value, go, s, goff, dot);
+            if constexpr (QL > 1) { if (steps > 1) so_bwd_team_step<D, 1>(value, go, s, goff, dot); }
             if constexpr (QL > 2) {
-                if (steps > 2) so_bwd_team_step_g<D, 2>(value, go, s, goff, dot);
-                if (steps > 3) so_bwd_team_step_g<D, 3>(value, go, s, goff, dot);
+                if (steps > 2) so_bwd_team_step<D, 2>(value, go, s, goff, dot);
+                if (steps > 3) so_bwd_team_step<D, 3>(value, go, s, goff, dot);
             }
             if constexpr (QL > 4) {
-                if (steps > 4) so_bwd_team_step_g<D, 4>(value, go, s, goff, dot);
-                if (steps > 5) so_bwd_team_step_g<D, 5>(value, go, s, goff, dot);
-                if (steps > 6) so_bwd_team_step_g<D, 6>(value, go, s, goff, dot);
-                if (steps > 7) so_bwd_team_step_g<D, 7>(value, go, s, goff, dot);
+                if (steps > 4) so_bwd_team_step<D, 4>(value, go, s, goff, dot);
+                if (steps > 5) so_bwd_team_step<D, 5>(value, go, s, goff, dot);
+                if (steps > 6) so_bwd_team_step<D, 6>(value, go, s, goff, dot);
+                if (steps > 7) so_bwd_team_step<D, 7>(value, go, s, goff, dot);
             }
             if (moved) {   // wave-uniform
 #pragma unroll
@@ -822,8 +743,7 @@ __global__ __launch_bounds__(256) void msda_cross_bwd_point_kernel(const VT *__r
                 gxs[r] += ((float)Wl * gw * aw) / (float)Wl;
                 gys[r] += ((float)Hl * gh * aw) / (float)Hl;
                 keys[ki] = (int16_t)bl.h_low;
-                recs[ki] = make_float4(bl.lh, bl.lw, aw / cnt,
-                                       __int_as_float((int)(((unsigned)bl.h_low << 16) | ((unsigned)bl.w_low & 0xffffu))));
+                recs[ki] = make_float4(bl.lh, bl.lw, aw / cnt, so_band_cell(bl.h_low, bl.w_low));
                 if (bin_cnt != nullptr) {      // the classification of msda_bin_kernel, on the key in the register
                     int band0 = 0;
                     float inv_rows = plan.inv_rows[0];
@@ -1085,9 +1005,9 @@ __global__ __launch_bounds__(kBandThreads) void msda_bwd_band_list_kernel(const 
             const int e = mine[pos + lane];
             const int q = so_fastdiv(e, plan.divP);
             const float4 rc = recs[kbase + e];
-            const int hw_ = __float_as_int(rc.w);
-            const int h_low = hw_ >> 16, w_low = (int)(short)(hw_ & 0xffff);
-            const float lh = rc.x, lw = rc.y, aw = rc.z;
+            const MsdaBandRec u = so_band_unpack(rc);
+            const int h_low = u.h_low, w_low = u.w_low;
+            const float lh = u.lh, lw = u.lw, aw = u.aw;
             const float hh = 1.0f - lh, hw = 1.0f - lw;
             const bool c0 = w_low >= 0, c1 = w_low + 1 <= Wl - 1;
             const int x0 = max(w_low, 0), x1 = min(w_low + 1, Wl - 1);
@@ -1187,28 +1107,57 @@ static void so_pick_group_fused(int LP, int d, int &G, int &logG) {
 // The (D, log2 G, value type) combinations of the fused / camera-loop families that can be launched: D = 8, 16, 32 channels per
 // head (the shipped lifters use 16; the plain mmcv-boundary op keeps 4), whole channel teams (G >= D / 4: so_pick_group_fused
 // never returns less), bfloat16 `value` for D = 16 only.  Round 4 instantiated all 4 x 7 x 2 = 56 per family (224 kernels, 6 MB).
-#define SO_FUSED_LG(DD, LGMIN, VT)                                                       \
-    switch (logG_) {                                                                      \
-        case 1: if (LGMIN <= 1) { SO_LAUNCH_VT(DD, (LGMIN <= 1 ? 1 : LGMIN), VT); } break; \
-        case 2: if (LGMIN <= 2) { SO_LAUNCH_VT(DD, (LGMIN <= 2 ? 2 : LGMIN), VT); } break; \
-        case 3: SO_LAUNCH_VT(DD, 3, VT); break;                                           \
-        case 4: SO_LAUNCH_VT(DD, 4, VT); break;                                           \
-        case 5: SO_LAUNCH_VT(DD, 5, VT); break;                                           \
-        default: SO_LAUNCH_VT(DD, 6, VT); break;                                          \
+// so_with_msda_shape is that table: it calls fn(D, LOGG, value type) with compile-time values (arguments of a generic lambda).
+template <int V>
+using so_int = std::integral_constant<int, V>;
+template <class T>
+struct so_type_tag { using type = T; };
+
+// fn(so_int<D>) for the head width of a validated call (so_msda_check_sizes: 4, 8, 16 or 32)
+template <class F>
+static int so_with_msda_d(int d, F &&fn) {
+    switch (d) {
+        case 4: return fn(so_int<4>{});
+        case 8: return fn(so_int<8>{});
+        case 16: return fn(so_int<16>{});
+        default: return fn(so_int<32>{});
     }
-#define SO_FUSED_DISPATCH(d_, lg_, bf_)                                                  \
-    do {                                                                                  \
-        const int logG_ = (lg_);                                                          \
-        if ((d_) == 16) {                                                                 \
-            SO_REQUIRE(logG_ >= 2, "msda: group of %d lanes for 16 channels", 1 << logG_);  \
-            if (bf_) { SO_FUSED_LG(16, 2, uint16_t) } else { SO_FUSED_LG(16, 2, float) }  \
-        } else {                                                                          \
-            SO_REQUIRE(!(bf_), "msda: bfloat16 value is built for 16 channels per head only (got %d)", (int)(d_)); \
-            if ((d_) == 8) { SO_REQUIRE(logG_ >= 1, "msda: bad group"); SO_FUSED_LG(8, 1, float) }          \
-            else if ((d_) == 32) { SO_REQUIRE(logG_ >= 3, "msda: bad group"); SO_FUSED_LG(32, 3, float) }   \
-            else SO_REQUIRE(false, "msda fused / camera-loop forms: channels per head must be 8, 16 or 32 (got %d); the plain form takes 4", (int)(d_)); \
-        }                                                                                 \
-    } while (0)
+}
+
+// fn(so_int<LOGG>) for LOGG = logG within LGMIN .. 6
+template <int LGMIN, class F>
+static int so_with_msda_logg(int logG, F &&fn) {
+    if constexpr (LGMIN < 6) {
+        if (logG <= LGMIN) return fn(so_int<LGMIN>{});
+        return so_with_msda_logg<LGMIN + 1>(logG, fn);
+    } else {
+        return fn(so_int<6>{});
+    }
+}
+
+// plain forward: whole channel teams (so_pick_group returns G >= D / 4): 22 of the 4 x 7 combinations can be reached
+template <class F>
+static int so_with_msda_plain_shape(int d, int logG, F &&fn) {
+    SO_REQUIRE((1 << logG) >= d / 4, "msda_fwd: group of %d lanes for %d channels", 1 << logG, d);
+    return so_with_msda_d(d, [&](auto dd) {
+        return so_with_msda_logg<so_ilog2(decltype(dd)::value / 4)>(logG, [&](auto lg) { return fn(dd, lg); });
+    });
+}
+
+template <class F>
+static int so_with_msda_shape(int d, int logG, bool bf16, F &&fn) {
+    if (d == 16) {
+        SO_REQUIRE(logG >= 2, "msda: group of %d lanes for 16 channels", 1 << logG);
+        if (bf16) return so_with_msda_logg<2>(logG, [&](auto lg) { return fn(so_int<16>{}, lg, so_type_tag<uint16_t>{}); });
+        return so_with_msda_logg<2>(logG, [&](auto lg) { return fn(so_int<16>{}, lg, so_type_tag<float>{}); });
+    }
+    SO_REQUIRE(!bf16, "msda: bfloat16 value is built for 16 channels per head only (got %d)", d);
+    SO_REQUIRE(d == 8 || d == 32,
+               "msda fused / camera-loop forms: channels per head must be 8, 16 or 32 (got %d); the plain form takes 4", d);
+    SO_REQUIRE(logG >= (d == 8 ? 1 : 3), "msda: bad group");
+    if (d == 8) return so_with_msda_logg<1>(logG, [&](auto lg) { return fn(so_int<8>{}, lg, so_type_tag<float>{}); });
+    return so_with_msda_logg<3>(logG, [&](auto lg) { return fn(so_int<32>{}, lg, so_type_tag<float>{}); });
+}
 
 // ---- banded backward -------------------------------------------------------------------------
 static size_t so_band_key_bytes(long long n_pts) { return (size_t)((n_pts + 8) * 2 + 15) / 16 * 16; }
@@ -1314,21 +1263,15 @@ int so_band_scatter(const int32_t *shapes, const int32_t *starts, const float *g
                        cursor, off, w.list, vis, bpb, dm, bp);
     const size_t shm = (size_t)bsu.tile_px * d * sizeof(double);
     // the grid is an upper bound (every point in two bands): blocks past item0[nb] return at once
-#define SO_LAUNCH(DD)                                                                                             \
-    {                                                                                                             \
-        /* per launch: the attribute is per device (a process may drive several GPUs) */                          \
-        (void)hipFuncSetAttribute((const void *)msda_bwd_band_list_kernel<DD, kBandBlock>,                        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, band_tile_bytes(kBandBlock));       \
-        hipLaunchKernelGGL((msda_bwd_band_list_kernel<DD, kBandBlock>), dim3((unsigned)max_items), dim3(kBandBlock), \
-                           shm, st, shapes, starts, g_out, g_value, w.recs, cnt, off, item0, w.list, nb, dm_g, bp);  \
-    }
-    switch (d) {
-        case 4: SO_LAUNCH(4); break;
-        case 8: SO_LAUNCH(8); break;
-        case 16: SO_LAUNCH(16); break;
-        default: SO_LAUNCH(32); break;
-    }
-#undef SO_LAUNCH
+    so_with_msda_d(d, [&](auto dd) {
+        constexpr int D = decltype(dd)::value;
+        // per launch: the attribute is per device (a process may drive several GPUs)
+        (void)hipFuncSetAttribute((const void *)msda_bwd_band_list_kernel<D, kBandBlock>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, band_tile_bytes(kBandBlock));
+        hipLaunchKernelGGL((msda_bwd_band_list_kernel<D, kBandBlock>), dim3((unsigned)max_items), dim3(kBandBlock), shm, st,
+                           shapes, starts, g_out, g_value, w.recs, cnt, off, item0, w.list, nb, dm_g, bp);
+        return 0;
+    });
     return so_launch_status();
 }
 
@@ -1460,45 +1403,29 @@ extern "C" int selfocc_msda_fwd(const so_msda_args *args, void *stream) {
     const long long blocks = (n_groups + gpb - 1) / gpb;
     SO_REQUIRE(blocks < (1LL << 31), "msda_fwd: grid too large");
     const bool bf16 = a.value_dtype == SO_DTYPE_BF16;
+    const dim3 grid((unsigned)blocks), block(256);
+    int rc;
     if (a.form == SO_MSDA_PLAIN) {
-        const float *value = (const float *)a.value;
-#define SO_LAUNCH_G(DD, LG)                                                                       \
-    hipLaunchKernelGGL((msda_fwd_kernel<DD, LG>), dim3((unsigned)blocks), dim3(256), 0, st, value, \
-                       a.shapes, a.starts, a.loc, a.attw, a.out, dm)
-    // so_pick_group returns whole channel teams (G >= D / 4): 22 of the 4 x 7 combinations can be reached
-#define SO_LAUNCH(DD, LGMIN)                                                                      \
-    switch (logG) {                                                                               \
-        case 0: SO_LAUNCH_G(DD, (LGMIN > 0 ? LGMIN : 0)); break;                                  \
-        case 1: SO_LAUNCH_G(DD, (LGMIN > 1 ? LGMIN : 1)); break;                                  \
-        case 2: SO_LAUNCH_G(DD, (LGMIN > 2 ? LGMIN : 2)); break;                                  \
-        case 3: SO_LAUNCH_G(DD, 3); break;                                                        \
-        case 4: SO_LAUNCH_G(DD, 4); break;                                                        \
-        case 5: SO_LAUNCH_G(DD, 5); break;                                                        \
-        default: SO_LAUNCH_G(DD, 6); break;                                                       \
-    }
-        SO_REQUIRE((1 << logG) >= d / 4, "msda_fwd: group of %d lanes for %d channels", 1 << logG, d);
-        switch (d) {
-            case 4: SO_LAUNCH(4, 0); break;
-            case 8: SO_LAUNCH(8, 1); break;
-            case 16: SO_LAUNCH(16, 2); break;
-            default: SO_LAUNCH(32, 3); break;
-        }
-#undef SO_LAUNCH
-#undef SO_LAUNCH_G
-    } else if (a.form == SO_MSDA_FUSED) {
-#define SO_LAUNCH_VT(DD, LG, VT) \
-        hipLaunchKernelGGL((msda_fused_fwd_kernel<DD, LG, VT>), dim3((unsigned)blocks), dim3(256), 0, st, \
-                           (const VT *)a.value, a.shapes, a.starts, a.ref, a.ref_kind, a.off_raw, a.logits, a.out, dm)
-        SO_FUSED_DISPATCH(d, logG, bf16);
-#undef SO_LAUNCH_VT
+        rc = so_with_msda_plain_shape(d, logG, [&](auto dd, auto lg) {
+            hipLaunchKernelGGL((msda_fwd_kernel<decltype(dd)::value, decltype(lg)::value>), grid, block, 0, st,
+                               (const float *)a.value, a.shapes, a.starts, a.loc, a.attw, a.out, dm);
+            return 0;
+        });
     } else {
-#define SO_LAUNCH_VT(DD, LG, VT) \
-        hipLaunchKernelGGL((msda_cross_fwd_kernel<DD, LG, VT>), dim3((unsigned)blocks), dim3(256), 0, st, \
-                           (const VT *)a.value, a.shapes, a.starts, a.ref, a.vis, a.off_raw, a.logits, a.out, a.bs, dm)
-        SO_FUSED_DISPATCH(d, logG, bf16);
-#undef SO_LAUNCH_VT
+        rc = so_with_msda_shape(d, logG, bf16, [&](auto dd, auto lg, auto vt) {
+            constexpr int D = decltype(dd)::value, LG = decltype(lg)::value;
+            using VT = typename decltype(vt)::type;
+            if (a.form == SO_MSDA_FUSED) {
+                hipLaunchKernelGGL((msda_fused_fwd_kernel<D, LG, VT>), grid, block, 0, st, (const VT *)a.value, a.shapes, a.starts,
+                                   a.ref, a.ref_kind, a.off_raw, a.logits, a.out, dm);
+            } else {
+                hipLaunchKernelGGL((msda_cross_fwd_kernel<D, LG, VT>), grid, block, 0, st, (const VT *)a.value, a.shapes, a.starts,
+                                   a.ref, a.vis, a.off_raw, a.logits, a.out, a.bs, dm);
+            }
+            return 0;
+        });
     }
-    return so_launch_status();
+    return rc ? rc : so_launch_status();
 }
 
 extern "C" int selfocc_msda_bwd(const so_msda_args *args, void *stream) {
@@ -1516,29 +1443,19 @@ extern "C" int selfocc_msda_bwd(const so_msda_args *args, void *stream) {
         const long long pblocks = (n_pts + 255) / 256;
         SO_REQUIRE(pblocks < (1LL << 31), "msda_bwd: grid too large");
         if (!bsu.ok) {   // no host shapes, or the banded scatter does not apply: global float atomics
-#define SO_LAUNCH(DD)                                                                                 \
-    hipLaunchKernelGGL((msda_bwd_kernel<DD>), dim3((unsigned)pblocks), dim3(256), 0, st, value,       \
-                       a.shapes, a.starts, a.loc, a.attw, a.g_out, a.g_value, a.g_loc, a.g_attw, dm)
-            switch (d) {
-                case 4: SO_LAUNCH(4); break;
-                case 8: SO_LAUNCH(8); break;
-                case 16: SO_LAUNCH(16); break;
-                default: SO_LAUNCH(32); break;
-            }
-#undef SO_LAUNCH
+            so_with_msda_d(d, [&](auto dd) {
+                hipLaunchKernelGGL((msda_bwd_kernel<decltype(dd)::value>), dim3((unsigned)pblocks), dim3(256), 0, st, value,
+                                   a.shapes, a.starts, a.loc, a.attw, a.g_out, a.g_value, a.g_loc, a.g_attw, dm);
+                return 0;
+            });
             return so_launch_status();
         }
         const BandWorkspace w = so_band_workspace(a.workspace, a.bs, a.nq, a.heads, a.L, a.P);
-#define SO_LAUNCH(DD)                                                                                 \
-    hipLaunchKernelGGL((msda_bwd_point_kernel<DD>), dim3((unsigned)pblocks), dim3(256), 0, st, value, \
-                       a.shapes, a.starts, a.loc, a.attw, a.g_out, a.g_loc, a.g_attw, w.keys, w.recs, dm)
-        switch (d) {
-            case 4: SO_LAUNCH(4); break;
-            case 8: SO_LAUNCH(8); break;
-            case 16: SO_LAUNCH(16); break;
-            default: SO_LAUNCH(32); break;
-        }
-#undef SO_LAUNCH
+        so_with_msda_d(d, [&](auto dd) {
+            hipLaunchKernelGGL((msda_bwd_point_kernel<decltype(dd)::value>), dim3((unsigned)pblocks), dim3(256), 0, st, value,
+                               a.shapes, a.starts, a.loc, a.attw, a.g_out, a.g_loc, a.g_attw, w.keys, w.recs, dm);
+            return 0;
+        });
         return so_band_scatter(a.shapes, a.starts, a.g_out, a.g_value, w, bsu, dm, d, nullptr, st);
     }
     // fused / camera loop: the banded scatter is part of the op
@@ -1559,15 +1476,18 @@ extern "C" int selfocc_msda_bwd(const so_msda_args *args, void *stream) {
     const long long blocks = (rows * a.heads + gpb - 1) / gpb;
     SO_REQUIRE(blocks < (1LL << 31), "msda_bwd: grid too large");
     const bool bf16 = a.value_dtype == SO_DTYPE_BF16;
+    const dim3 grid((unsigned)blocks), block(256);
     if (a.form == SO_MSDA_FUSED) {
         // (counting the sort's buckets inside this kernel, as the camera loop does, measured slower here: 454 -> 570 us for
         // 58 us of msda_bin_kernel<false>: 32 groups per block contend for the few buckets of one plane)
-#define SO_LAUNCH_VT(DD, LG, VT) \
-        hipLaunchKernelGGL((msda_fused_bwd_point_kernel<DD, LG, VT>), dim3((unsigned)blocks), dim3(256), 0, st, \
-                           (const VT *)a.value, a.shapes, a.starts, a.ref, a.ref_kind, a.off_raw, a.logits, a.g_out, a.g_off, \
-                           a.g_logits, w.keys, w.recs, dm)
-        SO_FUSED_DISPATCH(d, logG, bf16);
-#undef SO_LAUNCH_VT
+        if (so_with_msda_shape(d, logG, bf16, [&](auto dd, auto lg, auto vt) {
+                using VT = typename decltype(vt)::type;
+                hipLaunchKernelGGL((msda_fused_bwd_point_kernel<decltype(dd)::value, decltype(lg)::value, VT>), grid, block, 0, st,
+                                   (const VT *)a.value, a.shapes, a.starts, a.ref, a.ref_kind, a.off_raw, a.logits, a.g_out,
+                                   a.g_off, a.g_logits, w.keys, w.recs, dm);
+                return 0;
+            }))
+            return -1;
         return so_band_scatter(a.shapes, a.starts, a.g_out, a.g_value, w, bsu, dm, d, nullptr, st, false, a.g_value_stride);
     }
     const int cams = a.bs;
@@ -1584,11 +1504,13 @@ extern "C" int selfocc_msda_bwd(const so_msda_args *args, void *stream) {
         const size_t nb_all = (size_t)cams * a.heads * bsu.bin.nbands;
         (void)hipMemsetAsync(w.counters, 0, nb_all * 4 * sizeof(int32_t), st);      // cnt and cursor, before the counting kernel
     }
-#define SO_LAUNCH_VT(DD, LG, VT) \
-        hipLaunchKernelGGL((msda_cross_bwd_point_kernel<DD, LG, VT>), dim3((unsigned)blocks), dim3(256), hist_bytes, st, \
-                           (const VT *)a.value, a.shapes, a.starts, a.ref, a.vis, a.off_raw, a.logits, a.g_out, a.g_off, a.g_logits, \
-                           w.keys, w.recs, cams, dm, count_here ? w.counters : nullptr, bsu.bin)
-    SO_FUSED_DISPATCH(d, logG, bf16);
-#undef SO_LAUNCH_VT
+    if (so_with_msda_shape(d, logG, bf16, [&](auto dd, auto lg, auto vt) {
+            using VT = typename decltype(vt)::type;
+            hipLaunchKernelGGL((msda_cross_bwd_point_kernel<decltype(dd)::value, decltype(lg)::value, VT>), grid, block, hist_bytes,
+                               st, (const VT *)a.value, a.shapes, a.starts, a.ref, a.vis, a.off_raw, a.logits, a.g_out, a.g_off,
+                               a.g_logits, w.keys, w.recs, cams, dm, count_here ? w.counters : nullptr, bsu.bin);
+            return 0;
+        }))
+        return -1;
     return so_band_scatter(a.shapes, a.starts, a.g_out, a.g_value, w, bsu, dm, d, bin_vis, st, count_here, a.g_value_stride);
 }

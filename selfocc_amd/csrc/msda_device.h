@@ -370,6 +370,83 @@ SO_DEVFN void so_group_reduce_store(float (&acc)[4], int j, bool live, float *o4
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// backward building blocks (the kernels and what they are for: "backward" in msda.hip)
+// ---------------------------------------------------------------------------------------
+template <int QL>
+SO_DEVFN float so_team_sum(float x) {   // sum over the QL lanes of a channel team, result in every lane
+    if constexpr (QL >= 2)
+        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true));  // [1,0,3,2]
+    if constexpr (QL >= 4)
+        x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, true));  // [2,3,0,1]
+    if constexpr (QL >= 8) x += __shfl_xor(x, 4, 64);
+    return x;
+}
+
+// The g_out quarter (channels 4 s .. 4 s + 3) a team multiplies in step I: one float4 already in registers when every lane of
+// the team belongs to the same (query, head) group (fused / camera-loop kernels), or loaded from the row of the group that
+// owns the step's point (plain kernel: a team may straddle two groups).
+struct MsdaGoRows {
+    const float *g_out;
+    int gq32;   // this lane's (b, q, h) group: row of g_out
+};
+template <int D, int I>
+SO_DEVFN float4 so_team_go(const float4 &go, int) { return go; }
+template <int D, int I>
+SO_DEVFN float4 so_team_go(const MsdaGoRows &g, int s) {
+    const int gqi = so_team_bcast<D / 4, I>(g.gq32);
+    return *(const float4 *)(g.g_out + (size_t)gqi * D + 4 * s);
+}
+
+// team step I: the team computes value(corner k) . g_out for the point owned by its sub-lane I
+template <int D, int I, typename VT, typename GO>
+SO_DEVFN void so_bwd_team_step(const VT *__restrict__ value, const GO &gsrc, int s, const int (&goff)[4], float (&dot)[4]) {
+    constexpr int QL = D / 4;
+    const float4 go = so_team_go<D, I>(gsrc, s);
+    float part[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int off = so_team_bcast<QL, I>(goff[k]);
+        const float4 t = so_ld4(value + off + 4 * s);
+        part[k] = t.x * go.x;
+        part[k] = fmaf(t.y, go.y, part[k]);
+        part[k] = fmaf(t.z, go.z, part[k]);
+        part[k] = fmaf(t.w, go.w, part[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float d = so_team_sum<QL>(part[k]);
+        if (s == I) dot[k] = d;
+    }
+}
+
+// the first `steps` team steps (wave-uniform; D / 4: all of them): dot[k] = value(corner k) . g_out of the lane's own point
+template <int D, int I = 0, typename VT, typename GO>
+SO_DEVFN void so_bwd_team_dots(const VT *value, const GO &go, int s, const int (&goff)[4], float (&dot)[4], int steps) {
+    if constexpr (I < D / 4) {
+        if (steps > I) so_bwd_team_step<D, I>(value, go, s, goff, dot);
+        so_bwd_team_dots<D, I + 1>(value, go, s, goff, dot, steps);
+    }
+}
+
+// What a point kernel hands to the banded scatter: a 2-byte key per point (its upper corner row floor(h_im), or kKeyOutside) for
+// the counting sort, and a 16-byte record (lh, lw, attention weight, so_band_cell) for the band kernel.  so_band_cell packs
+// the corner row / column (both in -1 .. 32766) into the record's fourth float; so_band_unpack is its inverse.
+constexpr int kKeyOutside = -32768;
+SO_DEVFN float so_band_cell(int h_low, int w_low) {
+    return __int_as_float((int)(((unsigned)h_low << 16) | ((unsigned)w_low & 0xffffu)));
+}
+struct MsdaBandRec {
+    float lh, lw, aw;
+    int h_low, w_low;
+};
+SO_DEVFN MsdaBandRec so_band_unpack(const float4 &rc) {
+    MsdaBandRec u;
+    const int hw_ = __float_as_int(rc.w);
+    u.h_low = hw_ >> 16; u.w_low = (int)(short)(hw_ & 0xffff);
+    u.lh = rc.x; u.lw = rc.y; u.aw = rc.z;
+    return u;
+}
 
 // 4 waves / SIMD (<= 128 VGPRs) for the shipped head width: the camera-loop kernel otherwise takes 144 VGPRs (3 waves);
 // measured -1.5 % on the eval encoder, 5 / 6 waves spill (+20 % / +39 %)

@@ -355,7 +355,7 @@ class MSDACrossFunction(_SamplingFunction):
 
 def msda_fused_kernels_built(d, value_bf16=False):
     """The fused / camera-loop kernels exist for 8, 16, 32 channels per head; a bfloat16 ``value`` for 16 only
-    (csrc/msda.hip: SO_FUSED_DISPATCH).  Everything else goes through the plain op (4, 8, 16, 32; float32)."""
+    (csrc/msda.hip: so_with_msda_shape).  Everything else goes through the plain op (4, 8, 16, 32; float32)."""
     return d in (8, 16, 32) and (not value_bf16 or d == 16)
 
 

@@ -669,3 +669,102 @@ def test_msda_args_strides_are_validated_at_the_c_boundary(hip):
     assert float(g_rows[:, :, 0].abs().sum()) > 0 and float(g_rows[:, :, 1].abs().sum()) == 0      # only this op's column block is written
     for bad in (heads * d - 16, -1):
         assert bwd(bad) != 0 and b"g_value_stride" in l.selfocc_last_error()
+
+
+def _shape_dispatch_case(d):
+    """2 batch items / cameras x 70 queries x 2 heads x (2 levels x 18 points = 36 logits: groups of 8 lanes, five rounds per
+    lane) on maps of 3 x 5 and 2 x 3 pixels"""
+    g = torch.Generator().manual_seed(1000 + d)
+    n, nq, H, L, P = 2, 70, 2, 2, 18
+    shapes, starts, nv = torch.tensor([[3, 5], [2, 3]]), torch.tensor([0, 15]), 21
+    value = torch.randn(n, nv, H, d, generator=g)
+    off = torch.randn(n, nq, H, L, P, 2, generator=g) * 1.5
+    logits = torch.randn(n, nq, H, L * P, generator=g) * 2
+    ref = torch.rand(n, nq, P, 2, generator=g) * 1.3 - 0.15
+    vis = torch.rand(n, nq, generator=g) < 0.6
+    vis[:, 0] = False; vis[:, 1] = True
+    gout = torch.randn(n, nq, H * d, generator=g)
+    return n, nq, H, L, P, shapes, starts, nv, value, off, logits, ref, vis, gout
+
+
+def _softmax_backward(aw, ga):
+    aw, ga = aw.double(), ga.double()
+    return (aw * (ga - (aw * ga).flatten(-2).sum(-1)[..., None, None])).flatten(-2).float()
+
+
+def _shape_dispatch_accepted(d, bf16):
+    """one call per family (fused and camera loop, forward and backward point kernel) against the C oracle composed with the
+    torch prologue"""
+    from selfocc_amd.msda import MSDAFusedFunction, MSDACrossFunction, msda_fused_supported
+    n, nq, H, L, P, shapes, starts, nv, value, off, logits, ref, vis, gout = _shape_dispatch_case(d)
+    host = [int(v) for v in shapes.reshape(-1)]
+    assert msda_fused_supported(host, n, nq, H, d, L, P, bf16)
+    seen = value.to(torch.bfloat16).float() if bf16 else value      # what the kernels gather
+    norm = torch.stack([shapes[:, 1], shapes[:, 0]], -1).float()[None, None, None, :, None, :]
+    dev = torch.device("cuda:0")
+    sh, st = shapes.to(dev), starts.to(dev)
+
+    def close(got, want):
+        out, g_value, g_off, g_lg = (t.cpu() for t in got)
+        assert torch.allclose(out, want[0], rtol=1e-4, atol=1e-5)
+        assert torch.allclose(g_value, want[1], rtol=1e-4, atol=2e-4)
+        assert torch.allclose(g_off, want[2], rtol=1e-3, atol=1e-4 * want[2].abs().max().item())
+        assert torch.allclose(g_lg, want[3], rtol=1e-3, atol=1e-4 * want[3].abs().max().item())
+
+    # fused form, one anchor per point (ref_kind 1)
+    v, o, lg = (t.to(dev).requires_grad_(True) for t in (value, off, logits))
+    out = MSDAFusedFunction.apply(v, sh, st, ref.to(dev), 1, o, lg, host, False, bf16)
+    out.backward(gout.to(dev))
+    loc = (ref[:, :, None, None, :, :] + off / norm).contiguous()
+    aw = logits.softmax(-1).view(n, nq, H, L, P).contiguous()
+    gv, gl, ga = oracle.msda_bwd(seen, shapes, starts, loc, aw, gout)
+    close((out.detach(), v.grad, o.grad, lg.grad),
+          (oracle.msda_fwd(seen, shapes, starts, loc, aw), gv, gl / norm, _softmax_backward(aw, ga)))
+
+    # camera loop: the offsets and logits of batch item 0 shared by the cameras, mean over the cameras that see a query
+    offc, lgc, goutc = off[0].contiguous(), logits[0].contiguous(), gout[0].contiguous()
+    v, o, lg = (t.to(dev).requires_grad_(True) for t in (value, offc, lgc))
+    out = MSDACrossFunction.apply(v, sh, st, ref.to(dev), vis.to(dev), o, lg, host, False, bf16)
+    out.backward(goutc.to(dev))
+    cnt = vis.sum(0).clamp(min=1)[:, None].float()
+    aw = lgc.softmax(-1).view(1, nq, H, L, P).contiguous()
+    want_out, want_gv = torch.zeros(nq, H * d), torch.zeros_like(value)
+    gl_sum, ga_sum = torch.zeros(1, nq, H, L, P, 2), torch.zeros(1, nq, H, L, P)
+    for c in range(n):
+        loc = (ref[c][None, :, None, None, :, :] + offc[None] / norm).contiguous()
+        want_out += oracle.msda_fwd(seen[c:c + 1], shapes, starts, loc, aw)[0] * vis[c][:, None] / cnt
+        gv, gl, ga = oracle.msda_bwd(seen[c:c + 1], shapes, starts, loc, aw, (goutc * vis[c][:, None] / cnt)[None].contiguous())
+        want_gv[c] = gv[0]
+        gl_sum += gl
+        ga_sum += ga
+    close((out.detach(), v.grad, o.grad, lg.grad), (want_out, want_gv, (gl_sum / norm)[0], _softmax_backward(aw, ga_sum)[0]))
+
+
+def test_msda_shape_dispatch(hip):
+    """so_with_msda_shape (csrc/msda.hip), the one ladder from (channels per head, group size, value type) to a kernel of the
+    fused and camera-loop families.  It refuses what is not built, by name, before anything is launched: either form at 4
+    channels per head, bfloat16 `value` at 8 and at 32.  It accepts 8, 16, 32 and bfloat16 at 16: one call per family each."""
+    from selfocc_amd import abi
+    from selfocc_amd._lib import lib, current_stream
+    from selfocc_amd.msda import _msda_args, _i32, _u8
+    dev = torch.device("cuda:0")
+    l = lib()
+    widths = b"msda fused / camera-loop forms: channels per head must be 8, 16 or 32 (got 4); the plain form takes 4"
+    bf16_only = b"msda: bfloat16 value is built for 16 channels per head only (got %d)"
+    for form, d, bf16, message in [(abi.MSDA_FUSED, 4, False, widths), (abi.MSDA_FUSED, 8, True, bf16_only % 8),
+                                   (abi.MSDA_FUSED, 32, True, bf16_only % 32), (abi.MSDA_CROSS, 4, False, widths)]:
+        n, nq, H, L, P, shapes, starts, nv, value, off, logits, ref, vis, _ = _shape_dispatch_case(d)
+        cross = form == abi.MSDA_CROSS
+        out = torch.full((nq, H * d) if cross else (n, nq, H * d), 7.0, device=dev)
+        fields = dict(value=value.to(dev, torch.bfloat16 if bf16 else torch.float32), value_layout=0,
+                      value_dtype=abi.DTYPE_BF16 if bf16 else abi.DTYPE_F32, shapes=_i32(shapes, dev), starts=_i32(starts, dev),
+                      ref=ref.to(dev), ref_kind=1, off_raw=(off[0] if cross else off).contiguous().to(dev),
+                      logits=(logits[0] if cross else logits).contiguous().to(dev), out=out)
+        if cross:
+            fields["vis"] = _u8(vis.to(dev))
+        rc = l.selfocc_msda_fwd(_msda_args(form, (n, nv, nq, H, d, L, P), **fields), current_stream(dev))
+        torch.cuda.synchronize()
+        assert rc != 0 and l.selfocc_last_error() == message, (form, d, bf16, l.selfocc_last_error())
+        assert bool((out == 7.0).all()), "a refused call wrote its output"
+    for d, bf16 in [(8, False), (16, False), (32, False), (16, True)]:
+        _shape_dispatch_accepted(d, bf16)
