@@ -894,6 +894,14 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
 // therefore stays above 1e-10 to its end, and the wave-wide exit test `all lanes T < 1e-10` is false throughout.
 constexpr int kRunExitFreeSteps = 60000;
 constexpr int kSureScan = 8;   // steps tried from either end of the march for the sure-interior range
+// Low mode of the sure loop (see `low` in so_march_fast_ahead); -DSO_NO_LOW_MODE builds the marcher without it, for A/B runs.
+#ifdef SO_NO_LOW_MODE
+constexpr bool kLowMode = false;
+#else
+constexpr bool kLowMode = true;
+#endif
+// kLowC lies 15 * 2^-24 relative below kSkipArg * log2(e) = 25.2471632...: see the proof in `low`
+constexpr float kLowC = 25.24714f;
 
 struct AheadStep {
     float gh, gw, gd, fi;         // grid coordinates (the fractions are taken only by the steps that interpolate)
@@ -936,6 +944,8 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
     const float face_m = c.face_m;
 
     float T = 1.0f, acc = 0.0f, dsum = 0.0f, best_w = -1.0f, best_t = 0.0f;
+    bool low_hint_a = false, low_hint_b = false;     // wave-uniform: set by the two steps of the sure loop's body (low mode)
+    const float low_thr = kLowC * so_fast_rcp(s2);   // low mode: a corner at or under it is under the brick pass's 17.5 / inv_s
 
     // position and cell of step i
     auto place = [&](const int i, AheadStep &st) __attribute__((always_inline)) {
@@ -1035,11 +1045,15 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
     };
 
     // Returns whether the step skipped (wave-uniform).  IN_SURE: steps i and i + 1 both lie in the sure range.
-    auto step = [&](const int i, AheadStep &cur, AheadStep &nxt, auto in_sure) __attribute__((always_inline)) {
+    auto step = [&](const int i, AheadStep &cur, AheadStep &nxt, auto in_sure, bool &hint) __attribute__((always_inline)) {
         constexpr bool IN_SURE = decltype(in_sure)::value;
         bool skip;
         if constexpr (IN_SURE) {
-            skip = so_all((int)cur.code >= rcode);
+            const auto free_lanes = __builtin_amdgcn_ballot_w64((int)cur.code >= rcode);
+            skip = free_lanes == __builtin_amdgcn_ballot_w64(true);
+            // the hint that opens low mode (below): no lane of the step could skip.  Scalar work on the compare the step makes
+            // anyway; a wrong hint costs one unproven low step, never a wrong result.
+            if constexpr (kLowMode) hint = free_lanes == 0;
             locate(i + 1, nxt, in_sure);
         } else {
             skip = cur.all_interior && so_all((int)cur.code >= rcode);
@@ -1103,6 +1117,70 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
         return skip;
     };
 
+    // Low mode of the sure loop.  Interpolated steps come in long stretches that hug a surface, and in most of them some lane's
+    // cell has a corner under the saturation level 17.5 / inv_s, where the brick pass gives code 0 (its `slack > 0` fails):
+    // the wave cannot skip, and the code byte loaded for the step could only say so.  A low step is located without the code
+    // load (place), loads its records, and PROVES from them that the parent interpolated it; a step it cannot prove loads
+    // its code after all, takes the parent's decision and hands back to the sure loop.  A proven step is two vector-memory
+    // instructions instead of three and a few vector and scalar instructions shorter than a sure step (no code compare, one
+    // loop); what a lane composites is what step() composites, in the same order.  
+    //   The proof: some lane's corner v0 = lo.x is at or under low_thr = fl(kLowC * rcp(s2)).  The brick pass gives code 0
+    // unless the cell's smallest corner m exceeds q = fl(17.5 / inv_s), and m <= v0.  With u = 2^-24: v_rcp_f32 is good to one
+    // ulp, so low_thr <= (kLowC / s2) (1 + 2 u) (1 + u); s2 = fl(inv_s * fl(log2 e)) >= inv_s log2 e (1 - u)^2; and
+    // q >= (17.5 / inv_s) (1 - u).  Hence v0 <= low_thr implies v0 <= q whenever kLowC <= 17.5 log2 e (1 - 6 u - O(u^2)), and
+    // kLowC lies 15 u below 17.5 log2 e.  Edge cases agree with the brick pass: inv_s <= 0 gives every cell code 0, whatever is
+    // claimed; a NaN corner or a NaN inv_s compares false, not proven; an infinite s2 gives low_thr = 0 against q = 0; an s2 so
+    // small that rcp or the product overflows gives low_thr = inf where q is infinite or the slack NaN as well.  No division:
+    // inv_s may live on the device alone, and tests/test_render_prelude_cpu.py pins the kernel's division count.
+    // (The 8-corner minimum proves 95.5 % of the bench frame's interpolated wave-steps against 94.0 % for v0 alone and costs 4
+    // more vector instructions per step: measured slower.  The interpolated sdf proves nothing: a rounded nested lerp can
+    // undershoot m.)
+    //   On entry `st` holds step i, placed (its code is not looked at), i_lo <= i.  Steps i with i + 1 < i_hi only, so that
+    // the sure loop finds the range's end the way it always does.  A step with a lane near a face goes back to the sure loop
+    // untouched: the canonical-cell block exists once, there.  On return `st` is the located step i, code included, unless
+    // the march is over (returns true).
+    auto low = [&](int &i, AheadStep &st) __attribute__((always_inline)) {
+        // One loop, one exit: every reason to leave is folded into `go` (a loop with several exits gets an exit number from
+        // the compiler, made in a VGPR and read back with v_readfirstlane on every trip).  The next step's fractions and
+        // near-face test are taken at the end of a trip, for the same reason.
+        float fh = __builtin_amdgcn_fractf(st.gh), fw = __builtin_amdgcn_fractf(st.gw), fd = __builtin_amdgcn_fractf(st.gd);
+        bool coded = false;                  // st.code is on its way
+        bool go = i + 1 < i_hi && !(FACE_SAFE && __any(near_face(fh, fw, fd)));
+#pragma nounroll
+        while (go) {
+            const so_f4v lo = so_bload4(rb, st.cell * 16u, 0u), hi = so_bload4(rb, st.cell * 16u, row_off);
+            float t_mid = fmaf(st.fi, dt, tnear + hdt);
+            asm volatile("" : "+v"(t_mid));      // here, while st.fi is the step's: computed later it keeps a copy of st.fi alive
+            ++i;
+            place(i, st);
+            const bool proven = __any(lo.x <= low_thr);
+            float sdf, dh0, gvw, gvd;
+            so_trilerp_fast_pk(lo.xy, lo.zw, hi.xy, hi.zw, fh, fw, fd, sdf, dh0, gvw, gvd);
+            const float cosv = fmaf(gvd, Gdd, fmaf(gvw, Gdw, dh0 * Gdh));
+            float alpha = so_alpha_fast(sdf * s2, fminf(cosv, 0.0f) * hdt_s2);
+            if (__builtin_expect(!proven, 0)) {
+                // the parent's decision, from the code of the step (its cell placed once more: the hot path keeps only the
+                // next step's) and with the next step's code on its way
+                AheadStep was;
+                place(i - 1, was);
+                const unsigned code = __builtin_amdgcn_raw_buffer_load_b8(rb, was.cell, codes_off, 0);
+                st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, codes_off, 0);
+                if (so_all((int)code >= rcode)) alpha = kAlphaFree;     // skipped: the constant alpha, as step() composites it
+                coded = true;
+            }
+            const float w = alpha * T;
+            T = T * ((1.0f - alpha) + 1e-7f);
+            acc = acc + w;
+            dsum = fmaf(w, t_mid, dsum);
+            if (w > best_w) { best_w = w; best_t = t_mid; }
+            fh = __builtin_amdgcn_fractf(st.gh); fw = __builtin_amdgcn_fractf(st.gw); fd = __builtin_amdgcn_fractf(st.gd);
+            go = !coded && !so_all(T < 1e-10f) && i + 1 < i_hi && !(FACE_SAFE && __any(near_face(fh, fw, fd)));
+        }
+        if (so_all(T < 1e-10f)) return true;    // false on entry: the caller has just tested it
+        if (!coded) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, codes_off, 0);
+        return false;
+    };
+
     // The run loop, entered from the sure loop only.  On entry step i - 1 skipped and passed the exit test, `st` holds step
     // i, located, and i_lo <= i <= i_hi.  It composites steps i, i + 1, ... while they skip and the step after them is inside
     // the sure range (so that `st`, re-located in place after each decision, needs no interior test), then hands `st` = the
@@ -1143,11 +1221,11 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
         AheadStep A, B;
         locate(0, A, general);
         int i = 0;
-        bool over = false;
+        bool over = false, unused_hint = false;
         auto gen = [&](int end) __attribute__((always_inline)) {
 #pragma nounroll
             while (i < end) {
-                step(i, A, B, general);
+                step(i, A, B, general, unused_hint);
                 if (++i >= S || so_all(T < 1e-10f)) { over = true; break; }
                 A = B;
             }
@@ -1155,13 +1233,19 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
         gen(i_lo);
         if (!over) {
             while (i < i_hi) {
-                const bool sa = step(i, A, B, in_sure);
+                const bool sa = step(i, A, B, in_sure, low_hint_a);
                 ++i;
                 if (so_all(T < 1e-10f) || (sa && run(i, B))) { over = true; break; }
                 if (i >= i_hi) { A = B; break; }        // the tail takes its located step from A
-                const bool sb = step(i, B, A, in_sure);
+                const bool sb = step(i, B, A, in_sure, low_hint_b);
                 ++i;
                 if (so_all(T < 1e-10f) || (sb && run(i, A))) { over = true; break; }
+                // Low mode opens here only, on A, so that the loop has one copy of it, and after two steps in a row in which
+                // no lane could skip (the hint of step()).  A low step that the code skipped hands the skipping step back,
+                // and the step above takes it to the run loop.
+                if constexpr (kLowMode) {
+                    if (low_hint_a && low_hint_b && low(i, A)) { over = true; break; }
+                }
             }
             if (!over) { A.all_interior = true; gen(S); }
         }
