@@ -396,6 +396,19 @@ size_t selfocc_msda_ws_bytes(const so_msda_args *args);
  * bands per level or 8 levels, >= 2^30 sampling points), -1: bad arguments.  Reads the form, the sizes and
  * host_shapes only. */
 int selfocc_msda_banded_supported(const so_msda_args *args);
+/* What selfocc_msda_fwd / _bwd would decide for this call, without launching anything: reads the form, the sizes,
+ * value_dtype and host_shapes (may be NULL: the band entries stay 0), no device pointer.  Writes SO_MSDA_PLAN_INTS ints:
+ *   [SO_MSDA_PLAN_LOG2_GROUP]  log2 of the lanes per (query, head) group of this form's forward (and of the fused / camera-loop
+ *                              backward point kernel): with d and value_dtype, the kernel instantiation
+ *   [SO_MSDA_PLAN_BANDED]      1: the banded scatter applies (selfocc_msda_banded_supported)
+ *   [SO_MSDA_PLAN_COUNT_HERE]  CROSS backward: the point kernel counts the sort's buckets itself (else a separate pass does)
+ *   [SO_MSDA_PLAN_BIN_VIS]     CROSS backward: the sort skips invisible (camera, query) pairs by `vis` (else keys are preset)
+ *   [SO_MSDA_PLAN_BANDS + l]   bands level l < min(L, 8) is cut into,  [SO_MSDA_PLAN_ROWS + l]  map rows per band
+ * Returns -1 with selfocc_last_error() for sizes the checks refuse and for shapes no kernel is built for.  A new entry point:
+ * SELFOCC_ABI_VERSION is unchanged. */
+enum { SO_MSDA_PLAN_LOG2_GROUP = 0, SO_MSDA_PLAN_BANDED = 1, SO_MSDA_PLAN_COUNT_HERE = 2, SO_MSDA_PLAN_BIN_VIS = 3,
+       SO_MSDA_PLAN_BANDS = 4, SO_MSDA_PLAN_ROWS = 12, SO_MSDA_PLAN_INTS = 20 };
+int selfocc_msda_plan(const so_msda_args *args, int32_t *out);
 
 /* ------------------------------------------------------------------------------------
  * Dense SDF / semantic query on a regular metre lattice + Occ3D occupancy tail.

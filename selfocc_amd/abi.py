@@ -15,6 +15,8 @@ BKGD_NONE, BKGD_CONST, BKGD_PER_RAY = 0, 1, 2
 JITTER_NONE, JITTER_SINGLE, JITTER_PER_BIN = 0, 1, 2
 FLAG_DEPTH_DIV_NORM, FLAG_CLAMP_RGB, FLAG_EXACT, FLAG_NO_SKIP, FLAG_NO_FACE_SAFE, FLAG_NO_AHEAD, FLAG_RAY_PER_LANE = 1, 2, 4, 8, 16, 32, 64
 MSDA_PLAIN, MSDA_FUSED, MSDA_CROSS = 0, 1, 2
+# selfocc_msda_plan: indices into its SO_MSDA_PLAN_INTS outputs
+MSDA_PLAN_LOG2_GROUP, MSDA_PLAN_BANDED, MSDA_PLAN_COUNT_HERE, MSDA_PLAN_BIN_VIS, MSDA_PLAN_BANDS, MSDA_PLAN_ROWS, MSDA_PLAN_INTS = 0, 1, 2, 3, 4, 12, 20
 VALUE_PIXEL_MAJOR, VALUE_HEAD_MAJOR = 0, 1
 DTYPE_F32, DTYPE_BF16 = 0, 1
 LINEAR_RELU = 1
@@ -193,6 +195,7 @@ SYMBOLS = {
     "selfocc_msda_bwd": (C.c_int, [C.POINTER(SoMsdaArgs), _p]),
     "selfocc_msda_ws_bytes": (C.c_size_t, [C.POINTER(SoMsdaArgs)]),
     "selfocc_msda_banded_supported": (C.c_int, [C.POINTER(SoMsdaArgs)]),
+    "selfocc_msda_plan": (C.c_int, [C.POINTER(SoMsdaArgs), C.POINTER(C.c_int32)]),
     "selfocc_field_query": (C.c_int, [C.POINTER(SoQueryArgs), _p]),
     "selfocc_field_query_bwd": (C.c_int, [C.POINTER(SoQueryArgs), _p, _p, _p, _p, _p]),
     "selfocc_field_volume_bwd": (C.c_int, [_p] * 3 + [_i] * 4 + [_p, _p, _p, _i, _p, _p, _i] + [_p] * 7 + [_p]),

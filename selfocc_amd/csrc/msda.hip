@@ -1366,6 +1366,21 @@ MsdaDims so_msda_dims(const so_msda_args &a, bool bwd) {
     }
     return dm;
 }
+
+// the two host decisions of the camera-loop backward (selfocc_msda_bwd; reported by selfocc_msda_plan).  gpb: groups per block
+struct CrossBwdPlan {
+    bool bin_vis;        // the bin kernels skip invisible (camera, query) pairs by `vis`; else their keys are preset to "outside"
+    bool count_here;     // the point kernel counts the sort's buckets in an LDS histogram of hist_need bytes
+    size_t hist_need;
+};
+
+CrossBwdPlan so_cross_bwd_plan(const so_msda_args &a, const BandSetup &bsu, int gpb) {
+    CrossBwdPlan cp;
+    cp.bin_vis = a.P >= 4;
+    cp.hist_need = (size_t)2 * a.bs * bsu.bin.nbands * 2 * sizeof(int);
+    cp.count_here = a.nq >= gpb && cp.hist_need <= 32 * 1024;
+    return cp;
+}
 }  // namespace
 
 extern "C" size_t selfocc_msda_ws_bytes(const so_msda_args *a) {
@@ -1493,13 +1508,13 @@ extern "C" int selfocc_msda_bwd(const so_msda_args *args, void *stream) {
     const int cams = a.bs;
     // the point kernel writes the keys of every (camera, query) pair it visits; the bin kernels skip the others by
     // `vis` (P >= 4), otherwise the unvisited keys are preset to "outside"
-    const unsigned char *bin_vis = a.P >= 4 ? a.vis : nullptr;
+    const CrossBwdPlan cp = so_cross_bwd_plan(a, bsu, gpb);
+    const unsigned char *bin_vis = cp.bin_vis ? a.vis : nullptr;
     if (bin_vis == nullptr) (void)hipMemsetD16Async((hipDeviceptr_t)w.keys, (unsigned short)0x8000, (size_t)n_pts, st);
     // the point kernel does the sort's counting pass itself (an LDS histogram per block, flushed once) when a block's groups
     // span at most two heads and the histogram fits: saves one pass over the keys (msda_bin_kernel<false>, 0.9 ms per iteration)
-    const size_t hist_need = (size_t)2 * cams * bsu.bin.nbands * 2 * sizeof(int);
-    const bool count_here = a.nq >= gpb && hist_need <= 32 * 1024;
-    const size_t hist_bytes = count_here ? hist_need : 0;
+    const bool count_here = cp.count_here;
+    const size_t hist_bytes = count_here ? cp.hist_need : 0;
     if (count_here) {
         const size_t nb_all = (size_t)cams * a.heads * bsu.bin.nbands;
         (void)hipMemsetAsync(w.counters, 0, nb_all * 4 * sizeof(int32_t), st);      // cnt and cursor, before the counting kernel
@@ -1513,4 +1528,38 @@ extern "C" int selfocc_msda_bwd(const so_msda_args *args, void *stream) {
         }))
         return -1;
     return so_band_scatter(a.shapes, a.starts, a.g_out, a.g_value, w, bsu, dm, d, bin_vis, st, count_here, a.g_value_stride);
+}
+
+// What the two entries above would decide for this call, without launching anything: host arithmetic only, no pointer but
+// host_shapes is read.  The tests ask it which kernel instantiation and which branches a case reaches.
+extern "C" int selfocc_msda_plan(const so_msda_args *a, int32_t *out) {
+    if (so_msda_check_sizes(a)) return -1;
+    SO_REQUIRE(out != nullptr, "msda_plan: out is NULL");
+    for (int i = 0; i < SO_MSDA_PLAN_INTS; ++i) out[i] = 0;
+    const int LP = a->L * a->P;
+    int G = 1, logG = 0;
+    if (a->form == SO_MSDA_PLAIN) {
+        so_pick_group(LP, a->d, 8, G, logG);
+        if (so_with_msda_plain_shape(a->d, logG, [](auto, auto) { return 0; })) return -1;
+    } else {
+        SO_REQUIRE(a->value_dtype == SO_DTYPE_F32 || a->value_dtype == SO_DTYPE_BF16, "msda: bad value_dtype");
+        SO_REQUIRE(LP <= 256, "msda: L * P must be <= 256 for the fused / camera-loop forms (got %d); use the plain form", LP);
+        so_pick_group_fused(LP, a->d, G, logG);
+        if (so_with_msda_shape(a->d, logG, a->value_dtype == SO_DTYPE_BF16, [](auto, auto, auto) { return 0; })) return -1;
+    }
+    out[SO_MSDA_PLAN_LOG2_GROUP] = logG;
+    if (a->host_shapes == nullptr) return 0;
+    BandSetup bsu{};
+    if (so_band_setup(a->host_shapes, a->bs, a->nq, a->heads, a->d, a->L, a->P, bsu)) return -1;
+    out[SO_MSDA_PLAN_BANDED] = bsu.ok ? 1 : 0;
+    if (a->form == SO_MSDA_CROSS && bsu.ok) {   // as selfocc_msda_bwd decides them
+        const CrossBwdPlan cp = so_cross_bwd_plan(*a, bsu, 256 / G);
+        out[SO_MSDA_PLAN_COUNT_HERE] = cp.count_here ? 1 : 0;
+        out[SO_MSDA_PLAN_BIN_VIS] = cp.bin_vis ? 1 : 0;
+    }
+    for (int l = 0; l < a->L && l < 8; ++l) {
+        out[SO_MSDA_PLAN_BANDS + l] = bsu.bin.bands[l];
+        out[SO_MSDA_PLAN_ROWS + l] = bsu.bin.rows[l];
+    }
+    return 0;
 }
