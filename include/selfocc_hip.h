@@ -550,6 +550,29 @@ int selfocc_layernorm_bwd(const float *x, const float *gamma, const float *mean,
                           const float *dy, float *dx, float *dgamma, float *dbeta, int64_t rows, int32_t C,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* Row groups of a (rows, C) tensor: group g owns rows row_start[g] .. row_start[g + 1] - 1.  1 <= n_groups <= 8,
+ * row_start[0] = 0, non-decreasing, row_start[n_groups] = rows; a group may be empty.  Passed BY VALUE: host constants
+ * that travel in the kernel arguments (no device upload, no synchronisation). */
+typedef struct so_row_groups {
+    int32_t n_groups;
+    int64_t row_start[9];
+} so_row_groups;
+
+/* The LayerNorm above with one (gamma, beta) pair PER ROW GROUP — the reference's MultiPlaneNorm
+ * (model/encoder/tpvformer/modules/split_norm.py: one norm layer per TPV plane) on the concatenated planes in ONE launch
+ * per direction.  gamma / beta / dgamma / dbeta are (n_groups, C); x, y, dy, dx, mean, rstd as above.  A workgroup serves
+ * rows of one group only; the backward keeps per-group partial sums and adds them in a fixed order (deterministic, no
+ * atomics); an empty group gets dgamma = dbeta = 0.  With n_groups = 1 the results are bit-identical to the ungrouped
+ * entry points.  selfocc_layernorm_grouped_supported: 1 / 0 / < 0 (bad table: message in selfocc_last_error()), host
+ * logic only; every argument check of the other entries happens before anything touches the device. */
+int selfocc_layernorm_grouped_supported(int64_t rows, int32_t C, so_row_groups groups);
+int selfocc_layernorm_fwd_grouped(const float *x, const float *gamma, const float *beta, float *y, float *mean,
+                                  float *rstd, int64_t rows, int32_t C, float eps, so_row_groups groups, void *stream);
+size_t selfocc_layernorm_bwd_grouped_workspace(int64_t rows, int32_t C, so_row_groups groups);
+int selfocc_layernorm_bwd_grouped(const float *x, const float *gamma, const float *mean, const float *rstd,
+                                  const float *dy, float *dx, float *dgamma, float *dbeta, int64_t rows, int32_t C,
+                                  so_row_groups groups, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The image features as the encoders' `value`: n_levels maps (B, N, C, h_l, w_l) float32 -> out (N, sum h_l w_l, B, C) with
  * out[n][start_l + p][b][c] = (feats[l][b][n][c][p] + cams_embeds[n][c]) + level_embeds[l][c]
  * (/root/reference/model/encoder/tpvformer/tpvformer_encoder.py:261-277, bevformer/bevformer_encoder.py:194-210: two
@@ -585,6 +608,34 @@ size_t selfocc_camera_se_flatten_bwd_workspace(const int32_t *host_hw, int32_t n
 int selfocc_camera_se_flatten_bwd(const float *g, const float *const *feats, const int32_t *host_hw, int32_t n_levels, int32_t B,
                                   int32_t N, int32_t C, int32_t M, const float *gate, const float *w, float *const *d_feats,
                                   float *dwc, float *colsum, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * The three tall-Linear passes below with one weight PER ROW GROUP (so_row_groups, by value) — the reference's MultiPlaneFFN
+ * (model/encoder/tpvformer/modules/split_fpn.py: one mmcv FFN per TPV plane) on the concatenated planes, ONE launch each:
+ * group g's rows use w[g] (N, K), bias[g] (N), and write dw[g] (N, K), db[g] (N).  The kernels are the ungrouped ones with a
+ * group selection in front: a workgroup (forward / dgrad: a persistent block; wgrad: a row chunk) serves rows of one group
+ * only, so W is staged once per block and a chunk never straddles a group; the wgrad's fixed-order reduction runs per group
+ * (an empty group gets dw = db = 0).  Deterministic, no atomics.  Every other argument is its ungrouped twin's.
+ *   forward: w_group_stride = N * K (weights and biases stacked on a leading axis) or 0 (one shared w / bias);
+ *            ln_group_stride = N (ln_gamma / ln_beta stacked) or 0 (shared): a shared projection followed by a per-group
+ *            LayerNorm is one launch too.
+ *   dgrad:   workspace = selfocc_linear_dgrad_grouped_workspace(N, K, groups) bytes (every group's split planes of W^T).
+ *   wgrad:   workspace = selfocc_linear_wgrad_grouped_workspace(T, N, K, groups) bytes.
+ * *_grouped_supported: 1 / 0 / < 0 (bad table), host logic only; argument checks come before anything touches the device.
+ * ---------------------------------------------------------------------------------- */
+int selfocc_linear_fwd_grouped_supported(int64_t T, int32_t N, int32_t K, so_row_groups groups);
+int selfocc_linear_fwd_grouped(const float *x, const float *w, const float *bias, const float *residual, int32_t ldr,
+                               const float *ln_gamma, const float *ln_beta, float ln_eps, float *y, int32_t ldy, float *y_pre,
+                               float *mean, float *rstd, int64_t T, int32_t N, int32_t K, uint32_t flags, so_row_groups groups,
+                               int64_t w_group_stride, int64_t ln_group_stride, void *stream);
+int selfocc_linear_dgrad_grouped_supported(int64_t T, int32_t N, int32_t K, so_row_groups groups);
+size_t selfocc_linear_dgrad_grouped_workspace(int32_t N, int32_t K, so_row_groups groups);
+int selfocc_linear_dgrad_grouped(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K, so_row_groups groups,
+                                 void *workspace, int64_t workspace_bytes, void *stream);
+int selfocc_linear_wgrad_grouped_supported(int64_t T, int32_t N, int32_t K, so_row_groups groups);
+size_t selfocc_linear_wgrad_grouped_workspace(int64_t T, int32_t N, int32_t K, so_row_groups groups);
+int selfocc_linear_wgrad_grouped(const float *dy, const float *x, float *dw, float *db, int64_t T, int32_t N, int32_t K,
+                                 so_row_groups groups, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * point_sampling of the TPV / BEV encoders (model/encoder/bevformer/utils.py:114-170): project the pillar reference

@@ -182,6 +182,22 @@ class SoSscMetricArgs(C.Structure):
     ]
 
 
+class SoRowGroups(C.Structure):
+    """so_row_groups: passed BY VALUE; group g owns rows row_start[g] .. row_start[g + 1] - 1"""
+    _fields_ = [("n_groups", _i), ("row_start", C.c_int64 * 9)]
+
+    @classmethod
+    def from_sizes(cls, sizes):
+        g = cls()
+        g.n_groups = len(sizes)
+        if 1 <= len(sizes) <= 8:
+            o = 0
+            for k, n in enumerate(sizes):
+                o += int(n)
+                g.row_start[k + 1] = o
+        return g
+
+
 # every symbol include/selfocc_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "selfocc_abi_version": (C.c_int, []),
@@ -205,6 +221,19 @@ SYMBOLS = {
     "selfocc_layernorm_fwd": (C.c_int, [_p] * 6 + [C.c_int64, _i, C.c_float, _p]),
     "selfocc_layernorm_bwd_workspace": (C.c_size_t, [C.c_int64, _i]),
     "selfocc_layernorm_bwd": (C.c_int, [_p] * 8 + [C.c_int64, _i, _p, C.c_size_t, _p]),
+    "selfocc_layernorm_grouped_supported": (C.c_int, [C.c_int64, _i, SoRowGroups]),
+    "selfocc_layernorm_fwd_grouped": (C.c_int, [_p] * 6 + [C.c_int64, _i, C.c_float, SoRowGroups, _p]),
+    "selfocc_layernorm_bwd_grouped_workspace": (C.c_size_t, [C.c_int64, _i, SoRowGroups]),
+    "selfocc_layernorm_bwd_grouped": (C.c_int, [_p] * 8 + [C.c_int64, _i, SoRowGroups, _p, C.c_size_t, _p]),
+    "selfocc_linear_fwd_grouped_supported": (C.c_int, [C.c_int64, _i, _i, SoRowGroups]),
+    "selfocc_linear_fwd_grouped": (C.c_int, [_p] * 4 + [_i, _p, _p, C.c_float, _p, _i, _p, _p, _p, C.c_int64, _i, _i, C.c_uint32,
+                                             SoRowGroups, C.c_int64, C.c_int64, _p]),
+    "selfocc_linear_dgrad_grouped_supported": (C.c_int, [C.c_int64, _i, _i, SoRowGroups]),
+    "selfocc_linear_dgrad_grouped_workspace": (C.c_size_t, [_i, _i, SoRowGroups]),
+    "selfocc_linear_dgrad_grouped": (C.c_int, [_p] * 3 + [C.c_int64, _i, _i, SoRowGroups, _p, C.c_int64, _p]),
+    "selfocc_linear_wgrad_grouped_supported": (C.c_int, [C.c_int64, _i, _i, SoRowGroups]),
+    "selfocc_linear_wgrad_grouped_workspace": (C.c_size_t, [C.c_int64, _i, _i, SoRowGroups]),
+    "selfocc_linear_wgrad_grouped": (C.c_int, [_p] * 4 + [C.c_int64, _i, _i, SoRowGroups, _p, C.c_size_t, _p]),
     "selfocc_flatten_feats": (C.c_int, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "selfocc_camera_se_supported": (C.c_int, [_i] * 5),
     "selfocc_camera_se_flatten_fwd": (C.c_int, [_p, _p] + [_i] * 5 + [_p] * 7),

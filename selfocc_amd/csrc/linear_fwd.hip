@@ -53,7 +53,34 @@ extern "C" int selfocc_diag_lin_trace(unsigned long long *dst, size_t n) {
 
 namespace {
 
+// Row groups (selfocc_linear_*_grouped): the persistent blocks with row index rc_start[g] .. rc_start[g + 1] - 1 (per column
+// block) serve the rows row_start[g] .. row_start[g + 1] - 1 with group g's weights — a block belongs to ONE group, so it stages
+// W once, exactly as the ungrouped launch does.  By value in the kernel arguments, indexed with constants only.
+struct LinGroups {
+    int n;
+    int rc_start[9];
+    long long row_start[9];
+    long long w_stride, b_stride, ln_stride;      // floats between two groups' W / bias / LayerNorm parameters (0: shared)
+    long long planes_stride;                      // dgrad: bf16 elements between two groups' split planes
+};
+
+template <bool GRP>
+SO_DEVFN int so_lin_pick_group(const LinGroups &gr, long long &rc, int &groups, long long &r_lo, long long &r_hi) {
+    int g = 0;
+    if constexpr (GRP) {
+        int c0 = 0, c1 = gr.rc_start[1];
+        r_lo = 0; r_hi = gr.row_start[1];
+#pragma unroll
+        for (int i = 1; i < 8; ++i)
+            if (i < gr.n && rc >= gr.rc_start[i]) { g = i; c0 = gr.rc_start[i]; c1 = gr.rc_start[i + 1]; r_lo = gr.row_start[i]; r_hi = gr.row_start[i + 1]; }
+        rc -= c0;
+        groups = c1 - c0;
+    }
+    return g;
+}
+
 struct LinearFwdArgs {
+    LinGroups gr;
     const float *x, *w, *bias, *residual, *gamma, *beta;
     float *y, *y_pre, *mean, *rstd;
     long long T;
@@ -64,6 +91,23 @@ struct LinearFwdArgs {
     unsigned hm_sg;          // floats per 96-column group of the head-major output: (T / nv) * 6 * nv * 16
     float eps;
 };
+
+// the block's group: its rows become the whole problem (x / y / residual / y_pre / mean / rstd rebased, T = the group's rows), its
+// weights and LayerNorm parameters the group's
+template <bool GRP>
+SO_DEVFN void so_lin_group(LinearFwdArgs &a, long long &rc) {
+    if constexpr (GRP) {
+        long long r_lo = 0, r_hi = 0;
+        const int g = so_lin_pick_group<GRP>(a.gr, rc, a.groups, r_lo, r_hi);
+        a.x += r_lo * a.K; a.y += r_lo * a.ldy; a.T = r_hi - r_lo;
+        if (a.residual) a.residual += r_lo * a.ldr;
+        if (a.y_pre) a.y_pre += r_lo * a.N;
+        if (a.mean) { a.mean += r_lo; a.rstd += r_lo; }
+        a.w += g * a.gr.w_stride;
+        if (a.bias) a.bias += g * a.gr.b_stride;
+        if (a.gamma) { a.gamma += g * a.gr.ln_stride; a.beta += g * a.gr.ln_stride; }
+    }
+}
 
 SO_DEVFN unsigned so_lin_xcd_block() {   // workgroup b runs on XCD b % 8: give each XCD a contiguous range
     const unsigned nb = gridDim.x, b = blockIdx.x;
@@ -161,7 +205,7 @@ SO_DEVFN void so_linear_epilogue16_hm(f32x4 (&acc)[NT16], const float (&bv)[NT16
     }
 }
 
-template <int KQ /* K / 4 */, bool LN, int NT /* 32-column tiles per block */, int WAVES>
+template <int KQ /* K / 4 */, bool LN, int NT /* 32-column tiles per block */, int WAVES, bool GRP = false>
 __global__ __launch_bounds__(WAVES * 64) void linear_fwd16_kernel(LinearFwdArgs a) {
     constexpr int K = 4 * KQ, KP = K + 4, NT16 = 2 * NT, THREADS = WAVES * 64;
     extern __shared__ __attribute__((aligned(16))) float wl[];    // [32 NT][KP]
@@ -169,7 +213,8 @@ __global__ __launch_bounds__(WAVES * 64) void linear_fwd16_kernel(LinearFwdArgs 
     const int n = lane & 15, kq = lane >> 4;
     const unsigned logical = so_lin_xcd_block();
     const int cb = __builtin_amdgcn_readfirstlane((int)(logical % (unsigned)a.ncb));
-    const long long rc = __builtin_amdgcn_readfirstlane((int)(logical / (unsigned)a.ncb));
+    long long rc = __builtin_amdgcn_readfirstlane((int)(logical / (unsigned)a.ncb));
+    so_lin_group<GRP>(a, rc);
     const int n0 = a.col0 + cb * 96;
     const long long nwt = (a.T + 15) / 16, wt_step = (long long)WAVES * a.groups;
     // the A operand of the NEXT tile is loaded before the MFMAs of the current one (24 - 48 more registers; the kernel
@@ -430,7 +475,8 @@ SO_DEVFN void so_linear_epilogue_t_hm(f32x4 (&acc)[NT16], const f32x4 (&bv)[NT16
     }
 }
 
-template <int KS /* K / 32 */, bool LN, int NT /* 32-column tiles per block */, int WAVES, int H = 2 /* 16-row halves per wave tile */>
+template <int KS /* K / 32 */, bool LN, int NT /* 32-column tiles per block */, int WAVES, int H = 2 /* 16-row halves per wave tile */,
+          bool GRP = false>
 __global__ __launch_bounds__(WAVES * 64, 2) void linear_fwd_b3_kernel(LinearFwdArgs a) {
     constexpr int TR = 16 * H;
     constexpr int K = 32 * KS, KPB = K + 8, NT16 = 2 * NT, THREADS = WAVES * 64, NCOL = 32 * NT;
@@ -439,7 +485,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void linear_fwd_b3_kernel(LinearFwdA
     const int n = lane & 15, kb = lane >> 4;
     const unsigned logical = so_lin_xcd_block();
     const int cb = __builtin_amdgcn_readfirstlane((int)(logical % (unsigned)a.ncb));
-    const long long rc = __builtin_amdgcn_readfirstlane((int)(logical / (unsigned)a.ncb));
+    long long rc = __builtin_amdgcn_readfirstlane((int)(logical / (unsigned)a.ncb));
+    so_lin_group<GRP>(a, rc);
     const int n0 = a.col0 + cb * 96;
     const long long nwt = (a.T + TR - 1) / TR, wt_step = (long long)WAVES * a.groups;
     SO_TR(0);
@@ -618,6 +665,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void linear_fwd_b3_kernel(LinearFwdA
 //      of W through LDS and was a chain of load -> barrier -> stage -> barrier -> MFMA latencies (63 us at 66 049 x 384 x 96
 //      where the dy stream takes 16).
 __global__ __launch_bounds__(256) void linear_dgrad_split_kernel(const float *w, __bf16 *planes, int N, int K, int Npad) {
+    w += (size_t)blockIdx.y * N * K;                          // blockIdx.y: row group (its own W and planes)
+    planes += (size_t)blockIdx.y * 3 * K * Npad;
     const int nk8 = Npad / 8;
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < K * nk8; idx += gridDim.x * 256) {
         const int k8 = idx / K, c = idx - k8 * K;                 // consecutive threads: consecutive columns (coalesced reads)
@@ -637,6 +686,7 @@ __global__ __launch_bounds__(256) void linear_dgrad_split_kernel(const float *w,
 }
 
 struct LinearDgradArgs {
+    LinGroups gr;
     const float *dy;         // (T, N)
     const __bf16 *planes;    // [3][K][Npad], Npad = 96 nchunks; NULL (one chunk only): the kernel splits W itself
     const float *w;          // (N, K) as stored: read when planes == NULL
@@ -649,7 +699,7 @@ struct LinearDgradArgs {
 // Before the MFMAs of item i every lane issues the dy loads of item i + 1, so that the HBM stream and the matrix pipe overlap
 // inside one wave; the chunk's planes are copied from L2 between two barriers, which the CU's other block (60 KB of LDS each)
 // covers with its MFMAs.
-template <int DUMMY>
+template <bool GRP>
 __global__ __launch_bounds__(256) void linear_dgrad_b3_kernel(LinearDgradArgs a) {
     constexpr int KC = 96, KS = 3, KPB = KC + 8, NT16 = 6, NCOL = 96, WAVES = 4, THREADS = 256;
     constexpr int NST = (3 * NCOL * (KC / 8) + THREADS - 1) / THREADS;     // 16-byte staging copies per thread and chunk: 14
@@ -659,7 +709,14 @@ __global__ __launch_bounds__(256) void linear_dgrad_b3_kernel(LinearDgradArgs a)
     const unsigned logical = so_lin_xcd_block();
     const int ncb = a.K / 96;
     const int cb = __builtin_amdgcn_readfirstlane((int)(logical % (unsigned)ncb));
-    const long long rc = __builtin_amdgcn_readfirstlane((int)(logical / (unsigned)ncb));
+    long long rc = __builtin_amdgcn_readfirstlane((int)(logical / (unsigned)ncb));
+    if constexpr (GRP) {
+        long long r_lo = 0, r_hi = 0;
+        const int g = so_lin_pick_group<GRP>(a.gr, rc, a.groups, r_lo, r_hi);
+        a.dy += r_lo * a.N; a.dx += r_lo * a.K; a.T = r_hi - r_lo;
+        a.w += g * a.gr.w_stride;
+        if (a.planes) a.planes += g * a.gr.planes_stride;
+    }
     const int n0 = cb * 96;
     const long long nwt = (a.T + 31) / 32, wt_step = (long long)WAVES * a.groups;
     const int nchunks = a.Npad / KC;
@@ -811,7 +868,8 @@ extern "C" int selfocc_linear_fwd_supported(int64_t T, int32_t N, int32_t K) { r
 static int so_linear_fwd_launch(const float *x, const float *w, const float *bias, const float *residual, int32_t ldr,
                                 const float *ln_gamma, const float *ln_beta, float ln_eps, float *y, int32_t ldy,
                                 float *y_pre, float *mean, float *rstd, int64_t T, int32_t N, int32_t K,
-                                uint32_t flags, int32_t hm_nv, void *stream) {
+                                uint32_t flags, int32_t hm_nv, void *stream, const so_row_groups *row_groups = nullptr,
+                                long long w_group_stride = 0, long long ln_group_stride = 0) {
     SO_REQUIRE(so_linear_fwd_ok(T, N, K), "linear_fwd: unsupported shape (T = %lld rows, N = %d, K = %d; K must be 32, 64, 96, "
                "128 or 192)", (long long)T, N, K);
     SO_REQUIRE(x && w && y, "linear_fwd: NULL pointer");
@@ -820,7 +878,33 @@ static int so_linear_fwd_launch(const float *x, const float *w, const float *bia
     SO_REQUIRE(!ln || (ln_beta && N <= 96), "linear_fwd: the LayerNorm epilogue needs beta and N <= 96 (one column block)");
     SO_REQUIRE(ln || (!y_pre && !mean && !rstd), "linear_fwd: y_pre / mean / rstd are outputs of the LayerNorm epilogue");
     SO_REQUIRE((mean == nullptr) == (rstd == nullptr), "linear_fwd: mean and rstd come together");
+    const bool grouped = row_groups != nullptr;
     LinearFwdArgs a;
+    a.gr = LinGroups{};
+    if (grouped) {
+        a.gr.n = row_groups->n_groups;
+        for (int i = 0; i < 9; ++i) a.gr.row_start[i] = row_groups->row_start[i < row_groups->n_groups ? i : row_groups->n_groups];
+        a.gr.w_stride = w_group_stride;
+        a.gr.b_stride = w_group_stride ? N : 0;
+        a.gr.ln_stride = ln_group_stride;
+    }
+    // grouped: the `total` row blocks (per column block) the ungrouped launch would use, dealt to the groups in proportion to
+    // their row tiles — at least one for a group with rows, never more than it has tiles for its waves; returns their sum
+    auto deal = [&](long long total, long long tile_rows, long long waves) -> long long {
+        if (!grouped) return total;
+        long long tiles[8], all = 0, acc = 0;
+        for (int g = 0; g < a.gr.n; ++g) {
+            tiles[g] = (a.gr.row_start[g + 1] - a.gr.row_start[g] + tile_rows - 1) / tile_rows;
+            all += tiles[g];
+        }
+        for (int g = 0; g < a.gr.n; ++g) {
+            long long want = 0;
+            if (tiles[g] > 0) want = std::max(1LL, std::min((tiles[g] + waves - 1) / waves, (total * tiles[g] + all / 2) / all));
+            a.gr.rc_start[g + 1] = (int)(acc += want);
+        }
+        for (int i = a.gr.n + 1; i < 9; ++i) a.gr.rc_start[i] = (int)acc;
+        return acc;
+    };
     a.x = x; a.w = w; a.bias = bias; a.residual = residual; a.gamma = ln_gamma; a.beta = ln_beta;
     a.y = y; a.y_pre = y_pre; a.mean = mean; a.rstd = rstd;
     a.T = T; a.N = N; a.K = K; a.ldy = ldy; a.ldr = ldr;
@@ -854,23 +938,29 @@ static int so_linear_fwd_launch(const float *x, const float *w, const float *bia
             long long groups3 = std::max(1LL, 256LL / a.ncb);
             groups3 = std::min(groups3, (nwt3 + 7) / 8);
             a.groups = (int)groups3;
-            const long long nblk3 = groups3 * a.ncb;
-#define SO_B3_K192(LN_, NT_)                                                                                          \
+            const long long nblk3 = deal(groups3, 16, 8) * a.ncb;
+#define SO_B3_K192_G(LN_, NT_, GRP_)                                                                                  \
     do {                                                                                                             \
         static std::atomic<unsigned long long> done_mask{0};                                                         \
         int dev_ = 0;                                                                                                \
         (void)hipGetDevice(&dev_);                                                                                   \
         const unsigned long long bit_ = 1ull << (dev_ & 63);                                                         \
         if (!(done_mask.load(std::memory_order_relaxed) & bit_)) {                                                   \
-            (void)hipFuncSetAttribute((const void *)linear_fwd_b3_kernel<6, LN_, NT_, 8, 1>,                         \
+            (void)hipFuncSetAttribute((const void *)linear_fwd_b3_kernel<6, LN_, NT_, 8, 1, GRP_>,                   \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);                \
             done_mask.fetch_or(bit_, std::memory_order_relaxed);                                                     \
         }                                                                                                            \
-        hipLaunchKernelGGL((linear_fwd_b3_kernel<6, LN_, NT_, 8, 1>), dim3((unsigned)nblk3), dim3(512), lds_b3, st, a); \
+        hipLaunchKernelGGL((linear_fwd_b3_kernel<6, LN_, NT_, 8, 1, GRP_>), dim3((unsigned)nblk3), dim3(512), lds_b3, st, a); \
+    } while (0)
+#define SO_B3_K192(LN_, NT_)                                                                                          \
+    do {                                                                                                             \
+        if (grouped) SO_B3_K192_G(LN_, NT_, true);                                                                   \
+        else SO_B3_K192_G(LN_, NT_, false);                                                                          \
     } while (0)
             if (ln) { if (nt == 3) SO_B3_K192(true, 3); else if (nt == 2) SO_B3_K192(true, 2); else SO_B3_K192(true, 1); }
             else { if (nt == 3) SO_B3_K192(false, 3); else if (nt == 2) SO_B3_K192(false, 2); else SO_B3_K192(false, 1); }
 #undef SO_B3_K192
+#undef SO_B3_K192_G
             continue;
         }
         const bool use_b3 = b3_env && K <= 128 && (T >= 16384 || N >= 384);
@@ -886,8 +976,8 @@ static int so_linear_fwd_launch(const float *x, const float *w, const float *bia
             long long groups3 = std::max(1LL, 256 * per_cu3 / a.ncb);
             groups3 = std::min(groups3, (nwt3 + 3) / 4);
             a.groups = (int)groups3;
-            const long long nblk3 = groups3 * a.ncb;
-#define SO_B3_0(KS_, LN_, NT_, H_)                                                                                    \
+            const long long nblk3 = deal(groups3, half_tiles ? 16 : 32, 4) * a.ncb;
+#define SO_B3_0(KS_, LN_, NT_, H_, GRP_)                                                                                  \
     do {                                                                                                             \
         /* the attribute is per device: set once per (device, instantiation) — the call is a driver round trip of tens of */ \
         /* microseconds, which at ~45 launches per frame would make the host the bottleneck                                */ \
@@ -896,16 +986,16 @@ static int so_linear_fwd_launch(const float *x, const float *w, const float *bia
         (void)hipGetDevice(&dev_);                                                                                   \
         const unsigned long long bit_ = 1ull << (dev_ & 63);                                                         \
         if (lds_b3 > 48 * 1024 && !(done_mask.load(std::memory_order_relaxed) & bit_)) {                             \
-            (void)hipFuncSetAttribute((const void *)linear_fwd_b3_kernel<KS_, LN_, NT_, 4, H_>,                      \
+            (void)hipFuncSetAttribute((const void *)linear_fwd_b3_kernel<KS_, LN_, NT_, 4, H_, GRP_>,                \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);                \
             done_mask.fetch_or(bit_, std::memory_order_relaxed);                                                     \
         }                                                                                                            \
-        hipLaunchKernelGGL((linear_fwd_b3_kernel<KS_, LN_, NT_, 4, H_>), dim3((unsigned)nblk3), dim3(256), lds_b3, st, a); \
+        hipLaunchKernelGGL((linear_fwd_b3_kernel<KS_, LN_, NT_, 4, H_, GRP_>), dim3((unsigned)nblk3), dim3(256), lds_b3, st, a); \
     } while (0)
 #define SO_B3_1(KS_, LN_, NT_)                                                                                        \
     do {                                                                                                             \
-        if (half_tiles) SO_B3_0(KS_, LN_, NT_, 1);                                                                   \
-        else SO_B3_0(KS_, LN_, NT_, 2);                                                                              \
+        if (half_tiles) { if (grouped) SO_B3_0(KS_, LN_, NT_, 1, true); else SO_B3_0(KS_, LN_, NT_, 1, false); }      \
+        else { if (grouped) SO_B3_0(KS_, LN_, NT_, 2, true); else SO_B3_0(KS_, LN_, NT_, 2, false); }                 \
     } while (0)
 #define SO_B3_2(KS_, LN_)                                                                                             \
     do {                                                                                                             \
@@ -941,11 +1031,18 @@ static int so_linear_fwd_launch(const float *x, const float *w, const float *bia
         long long groups = std::max(1LL, 256 * per_cu / a.ncb);
         groups = std::min(groups, (nwt + 3) / 4);
         a.groups = (int)groups;
-        const long long nblk = groups * a.ncb;
+        const long long nblk = deal(groups, 16, 4) * a.ncb;
 #define SO_L16_1(KQ_, LN_, NT_)                                                                                       \
     do {                                                                                                             \
         /* per launch, not once per process: the attribute is per device, and a second GPU in the same process */    \
         /* would otherwise launch without it (cheap: no driver round trip after the first call on a device)      */    \
+        if (grouped) {                                                                                               \
+            if (lds_blk > 48 * 1024)                                                                                 \
+                (void)hipFuncSetAttribute((const void *)linear_fwd16_kernel<KQ_, LN_, NT_, 4, true>,                 \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_blk);                 \
+            hipLaunchKernelGGL((linear_fwd16_kernel<KQ_, LN_, NT_, 4, true>), dim3((unsigned)nblk), dim3(256), lds_blk, st, a); \
+            break;                                                                                                   \
+        }                                                                                                            \
         if (lds_blk > 48 * 1024)                                                                                     \
             (void)hipFuncSetAttribute((const void *)linear_fwd16_kernel<KQ_, LN_, NT_, 4>,                           \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_blk);                     \
@@ -995,44 +1092,117 @@ extern "C" int selfocc_linear_fwd_heads(const float *x, const float *w, const fl
                                 stream);
 }
 
+extern "C" int selfocc_linear_fwd_grouped_supported(int64_t T, int32_t N, int32_t K, so_row_groups groups) {
+    if (so_check_row_groups(groups, T, "linear_fwd_grouped") < 0) return -1;
+    return so_linear_fwd_ok(T > 0 ? T : 1, N, K) ? 1 : 0;
+}
+
+extern "C" int selfocc_linear_fwd_grouped(const float *x, const float *w, const float *bias, const float *residual, int32_t ldr,
+                                          const float *ln_gamma, const float *ln_beta, float ln_eps, float *y, int32_t ldy,
+                                          float *y_pre, float *mean, float *rstd, int64_t T, int32_t N, int32_t K, uint32_t flags,
+                                          so_row_groups groups, int64_t w_group_stride, int64_t ln_group_stride, void *stream) {
+    if (so_check_row_groups(groups, T, "linear_fwd_grouped") < 0) return -1;
+    SO_REQUIRE(so_linear_fwd_ok(T > 0 ? T : 1, N, K), "linear_fwd_grouped: unsupported shape (T = %lld rows, N = %d, K = %d; K must be "
+               "32, 64, 96, 128 or 192)", (long long)T, N, K);
+    SO_REQUIRE(w_group_stride == 0 || w_group_stride == (int64_t)N * K, "linear_fwd_grouped: w_group_stride must be 0 (shared) or "
+               "N * K = %lld (got %lld)", (long long)N * K, (long long)w_group_stride);
+    SO_REQUIRE(ln_group_stride == 0 || ln_group_stride == N, "linear_fwd_grouped: ln_group_stride must be 0 (shared) or N = %d "
+               "(got %lld)", N, (long long)ln_group_stride);
+    if (T == 0) return 0;
+    return so_linear_fwd_launch(x, w, bias, residual, ldr, ln_gamma, ln_beta, ln_eps, y, ldy, y_pre, mean, rstd, T, N, K, flags, 0,
+                                stream, &groups, w_group_stride, ln_group_stride);
+}
+
 // dx = dy W for a tall Linear (the input gradient; replaces the `dy @ weight` GEMM of torch.nn.functional.linear's backward
-// on the encoder's projections, /root/reference/model/encoder/tpvformer/tpvformer_encoder.py:257-291 runs them under autograd)
+// on the encoder's projections, model/encoder/tpvformer/tpvformer_encoder.py:257-291 runs them under autograd)
 extern "C" int selfocc_linear_dgrad_supported(int64_t T, int32_t N, int32_t K) { return so_linear_dgrad_ok(T, N, K) ? 1 : 0; }
 
 extern "C" size_t selfocc_linear_dgrad_workspace(int32_t N, int32_t K) {
     return (size_t)3 * K * ((N + 95) / 96 * 96) * 2;
 }
 
-extern "C" int selfocc_linear_dgrad(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K, void *workspace,
-                                    int64_t workspace_bytes, void *stream) {
-    SO_REQUIRE(so_linear_dgrad_ok(T, N, K), "linear_dgrad: unsupported shape (T = %lld rows, N = %d reduced features (multiple of 8, "
-               "<= 4096), K = %d input features (96, 192, 288 or 384))", (long long)T, N, K);
+static int so_linear_dgrad_launch(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K, void *workspace,
+                                  int64_t workspace_bytes, void *stream, const so_row_groups *row_groups) {
+    const bool grouped = row_groups != nullptr;
+    const int G = grouped ? row_groups->n_groups : 1;
     SO_REQUIRE(dy && w && dx && workspace, "linear_dgrad: NULL pointer");
-    SO_REQUIRE(workspace_bytes >= (int64_t)selfocc_linear_dgrad_workspace(N, K), "linear_dgrad: workspace of %lld bytes, need %lld",
-               (long long)workspace_bytes, (long long)selfocc_linear_dgrad_workspace(N, K));
+    SO_REQUIRE(workspace_bytes >= (int64_t)(G * selfocc_linear_dgrad_workspace(N, K)), "linear_dgrad: workspace of %lld bytes, need %lld",
+               (long long)workspace_bytes, (long long)(G * selfocc_linear_dgrad_workspace(N, K)));
     SO_REQUIRE(((uintptr_t)workspace & 15) == 0, "linear_dgrad: workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int Npad = (N + 95) / 96 * 96;
     LinearDgradArgs a;
+    a.gr = LinGroups{};
     a.dy = dy; a.planes = (const __bf16 *)workspace; a.w = w; a.dx = dx; a.T = T; a.N = N; a.K = K; a.Npad = Npad;
     if (Npad == 96) a.planes = nullptr;        // one chunk: the main kernel splits W while it stages it (one launch less)
-    else hipLaunchKernelGGL(linear_dgrad_split_kernel, dim3((unsigned)std::min(256, (K * (Npad / 8) + 255) / 256)), dim3(256), 0,
-                            st, w, (__bf16 *)workspace, N, K, Npad);
+    else hipLaunchKernelGGL(linear_dgrad_split_kernel, dim3((unsigned)std::min(256, (K * (Npad / 8) + 255) / 256), (unsigned)G),
+                            dim3(256), 0, st, w, (__bf16 *)workspace, N, K, Npad);
     const int ncb = K / 96;
     const long long nwt = (T + 31) / 32;
     static const int percu = getenv("SELFOCC_DGRAD_PERCU") ? atoi(getenv("SELFOCC_DGRAD_PERCU")) : 2;      // dev A/B
     long long groups = std::max<long long>(1, 256 * percu / ncb);
     groups = std::min<long long>(groups, (nwt + 3) / 4);
     a.groups = (int)groups;
-    const size_t lds = (size_t)3 * 96 * (96 + 8) * 2;
-    static std::atomic<unsigned long long> done_mask{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done_mask.load(std::memory_order_relaxed) & bit)) {
-        (void)hipFuncSetAttribute((const void *)linear_dgrad_b3_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-        done_mask.fetch_or(bit, std::memory_order_relaxed);
+    if (grouped) {      // the row blocks dealt to the groups in proportion to their 32-row tiles (see so_linear_fwd_launch)
+        a.gr.n = G;
+        a.gr.w_stride = (long long)N * K;
+        a.gr.planes_stride = (long long)3 * K * Npad;
+        long long tiles[8], all = 0, acc = 0;
+        for (int g = 0; g < G; ++g) {
+            a.gr.row_start[g + 1] = row_groups->row_start[g + 1];
+            tiles[g] = (row_groups->row_start[g + 1] - row_groups->row_start[g] + 31) / 32;
+            all += tiles[g];
+        }
+        for (int g = 0; g < G; ++g) {
+            long long want = 0;
+            if (tiles[g] > 0) want = std::max(1LL, std::min((tiles[g] + 3) / 4, (groups * tiles[g] + all / 2) / all));
+            a.gr.rc_start[g + 1] = (int)(acc += want);
+        }
+        for (int i = G + 1; i < 9; ++i) { a.gr.rc_start[i] = (int)acc; a.gr.row_start[i] = T; }
+        groups = acc;
     }
-    hipLaunchKernelGGL(linear_dgrad_b3_kernel<0>, dim3((unsigned)(groups * ncb)), dim3(256), lds, st, a);
+    const size_t lds = (size_t)3 * 96 * (96 + 8) * 2;
+#define SO_DGRAD(GRP_)                                                                                                \
+    do {                                                                                                             \
+        static std::atomic<unsigned long long> done_mask{0};                                                         \
+        int dev = 0;                                                                                                 \
+        (void)hipGetDevice(&dev);                                                                                    \
+        const unsigned long long bit = 1ull << (dev & 63);                                                           \
+        if (!(done_mask.load(std::memory_order_relaxed) & bit)) {                                                    \
+            (void)hipFuncSetAttribute((const void *)linear_dgrad_b3_kernel<GRP_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                      160 * 1024 - 256);                                                             \
+            done_mask.fetch_or(bit, std::memory_order_relaxed);                                                      \
+        }                                                                                                            \
+        hipLaunchKernelGGL(linear_dgrad_b3_kernel<GRP_>, dim3((unsigned)(groups * ncb)), dim3(256), lds, st, a);      \
+    } while (0)
+    if (grouped) SO_DGRAD(true);
+    else SO_DGRAD(false);
+#undef SO_DGRAD
     return so_launch_status();
+}
+
+extern "C" int selfocc_linear_dgrad(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K, void *workspace,
+                                    int64_t workspace_bytes, void *stream) {
+    SO_REQUIRE(so_linear_dgrad_ok(T, N, K), "linear_dgrad: unsupported shape (T = %lld rows, N = %d reduced features (multiple of 8, "
+               "<= 4096), K = %d input features (96, 192, 288 or 384))", (long long)T, N, K);
+    return so_linear_dgrad_launch(dy, w, dx, T, N, K, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int selfocc_linear_dgrad_grouped_supported(int64_t T, int32_t N, int32_t K, so_row_groups groups) {
+    if (so_check_row_groups(groups, T, "linear_dgrad_grouped") < 0) return -1;
+    return so_linear_dgrad_ok(T > 0 ? T : 1, N, K) ? 1 : 0;
+}
+
+extern "C" size_t selfocc_linear_dgrad_grouped_workspace(int32_t N, int32_t K, so_row_groups groups) {
+    if (groups.n_groups < 1 || groups.n_groups > 8) return 0;
+    return (size_t)groups.n_groups * selfocc_linear_dgrad_workspace(N, K);
+}
+
+extern "C" int selfocc_linear_dgrad_grouped(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K,
+                                            so_row_groups groups, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (so_check_row_groups(groups, T, "linear_dgrad_grouped") < 0) return -1;
+    SO_REQUIRE(so_linear_dgrad_ok(T > 0 ? T : 1, N, K), "linear_dgrad_grouped: unsupported shape (T = %lld rows, N = %d reduced features "
+               "(multiple of 8, <= 4096), K = %d input features (96, 192, 288 or 384))", (long long)T, N, K);
+    if (T == 0) return 0;
+    return so_linear_dgrad_launch(dy, w, dx, T, N, K, workspace, workspace_bytes, stream, &groups);
 }

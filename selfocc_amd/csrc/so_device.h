@@ -36,6 +36,18 @@ static inline int so_launch_status() {
     return 0;
 }
 
+// so_row_groups (by value through the C ABI): 1 .. 8 groups, row_start[0] = 0, non-decreasing, row_start[n] = T.  Host logic only.
+static inline int so_check_row_groups(const so_row_groups &g, long long T, const char *who) {
+    SO_REQUIRE(g.n_groups >= 1 && g.n_groups <= 8, "%s: n_groups must be in [1, 8] (got %d)", who, g.n_groups);
+    SO_REQUIRE(g.row_start[0] == 0, "%s: row_start[0] must be 0 (got %lld)", who, (long long)g.row_start[0]);
+    for (int i = 0; i < g.n_groups; ++i)
+        SO_REQUIRE(g.row_start[i + 1] >= g.row_start[i], "%s: row_start must be non-decreasing (row_start[%d] = %lld < "
+                   "row_start[%d] = %lld)", who, i + 1, (long long)g.row_start[i + 1], i, (long long)g.row_start[i]);
+    SO_REQUIRE(g.row_start[g.n_groups] == T, "%s: row_start[n_groups] = %lld must equal the row count %lld", who,
+               (long long)g.row_start[g.n_groups], T);
+    return 0;
+}
+
 // ---- canonical expf / sigmoid -----------------------------------------------------------
 // Cody-Waite reduction + Cephes degree-5 polynomial, every step an explicit IEEE op so that
 // the CPU oracle reproduces it bit for bit (the NeuS alpha subtracts two sigmoids that

@@ -114,3 +114,109 @@ def linear_fwd_heads(x, weight, bias, nv, relu=False):
     check(lib().selfocc_linear_fwd_heads(ptr(x), ptr(weight), ptr(bias), ptr(y), T, N, K, int(nv),
                                          LINEAR_RELU if relu else 0, current_stream(x.device)), "selfocc_linear_fwd_heads")
     return y
+
+
+# ---- one weight per ROW GROUP (so_row_groups: the TPV planes of a MultiPlaneFFN, concatenated): one launch for all groups ----
+_ROW_GROUPS = {}
+
+
+def row_groups(sizes):
+    """the by-value so_row_groups of these group sizes (host constants: no upload, no synchronisation; built once per tuple)"""
+    key = tuple(int(n) for n in sizes)
+    hit = _ROW_GROUPS.get(key)
+    if hit is None:
+        from .abi import SoRowGroups
+        hit = _ROW_GROUPS[key] = SoRowGroups.from_sizes(key)
+    return hit
+
+
+def linear_fwd_grouped_supported(sizes, n_out, n_in):
+    return 1 <= len(sizes) <= 8 and lib().selfocc_linear_fwd_grouped_supported(int(sum(sizes)), int(n_out), int(n_in), row_groups(sizes)) == 1
+
+
+def linear_dgrad_grouped_supported(sizes, n_out, n_in):
+    return 1 <= len(sizes) <= 8 and lib().selfocc_linear_dgrad_grouped_supported(int(sum(sizes)), int(n_out), int(n_in), row_groups(sizes)) == 1
+
+
+def linear_wgrad_grouped_supported(sizes, n_out, n_in):
+    return 1 <= len(sizes) <= 8 and lib().selfocc_linear_wgrad_grouped_supported(int(sum(sizes)), int(n_out), int(n_in), row_groups(sizes)) == 1
+
+
+def linear_fwd_grouped(x, sizes, weight, bias=None, relu=False, residual=None, ln=None, want_stats=False, shared_w=False):
+    """y = LN?(relu?(x W_g^T + b_g) + residual) for the rows of group g, ONE launch (selfocc_linear_fwd_grouped).
+
+    x (T, K) with T = sum(sizes); weight [G][N][K] (any shape with that layout: (G, N, K), (G * N, K)) with bias [G][N] | None —
+    or, with ``shared_w``, (N, K) / (N) shared by the groups;
+    residual (T, N) | None; ln = (gamma, beta, eps) with gamma / beta (G, N) per group or (N) shared.
+    -> y (T, N), or (y, y_pre, mean, rstd) with ``want_stats``."""
+    from .abi import LINEAR_RELU
+    if not x.is_cuda:
+        raise RuntimeError("linear_fwd_grouped needs CUDA(HIP) tensors: selfocc_amd has no CPU fallback")
+    T, K = x.shape
+    G = len(sizes)
+    assert sum(sizes) == T and x.dtype == torch.float32 and weight.dtype == torch.float32
+    x, weight = x.contiguous(), weight.contiguous()
+    N = weight.numel() // (K if shared_w else G * K)
+    assert weight.shape[-1] == K and weight.numel() == (N * K if shared_w else G * N * K)
+    w_stride = 0 if shared_w else N * K
+    if bias is not None:
+        bias = bias.contiguous()
+        assert bias.numel() == (G * N if w_stride else N)
+    out = torch.empty(T, N, device=x.device, dtype=torch.float32)
+    ldr = 0
+    if residual is not None:
+        assert residual.shape == (T, N) and residual.dtype == torch.float32
+        if residual.stride(1) != 1:
+            residual = residual.contiguous()
+        ldr = residual.stride(0) if T > 1 else N
+    g = b = y_pre = mean = rstd = None
+    eps, ln_stride = 0.0, 0
+    if ln is not None:
+        g, b, eps = ln
+        g, b = g.contiguous(), b.contiguous()
+        assert g.numel() == b.numel() and g.numel() in (N, G * N)
+        ln_stride = N if g.numel() == G * N and G > 1 else 0      # (G = 1: either way the one set)
+        if want_stats:
+            y_pre = torch.empty(T, N, device=x.device, dtype=torch.float32)
+            mean = torch.empty(T, device=x.device, dtype=torch.float32)
+            rstd = torch.empty(T, device=x.device, dtype=torch.float32)
+    elif want_stats:
+        raise ValueError("want_stats needs ln")
+    check(lib().selfocc_linear_fwd_grouped(ptr(x), ptr(weight), ptr(bias), ptr(residual), int(ldr), ptr(g), ptr(b), float(eps),
+                                           ptr(out), N, ptr(y_pre), ptr(mean), ptr(rstd), T, N, K, LINEAR_RELU if relu else 0,
+                                           row_groups(sizes), w_stride, ln_stride, current_stream(x.device)),
+          "selfocc_linear_fwd_grouped")
+    return (out, y_pre, mean, rstd) if want_stats else out
+
+
+def linear_dgrad_grouped(dy, weight, sizes):
+    """dx (T, K): the rows of group g are dy_g (T_g, N) @ weight[g] (N, K); weight (G, N, K); ONE launch (+ the split of W)"""
+    T, N = dy.shape
+    G = len(sizes)
+    K = weight.shape[-1]
+    assert sum(sizes) == T and weight.numel() == G * N * K and dy.dtype == torch.float32 and weight.dtype == torch.float32
+    dy, weight = dy.contiguous(), weight.contiguous()
+    dx = torch.empty(T, K, device=dy.device, dtype=torch.float32)
+    groups = row_groups(sizes)
+    nbytes = int(lib().selfocc_linear_dgrad_grouped_workspace(N, K, groups))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
+    check(lib().selfocc_linear_dgrad_grouped(ptr(dy), ptr(weight), ptr(dx), T, N, K, groups, ptr(ws), nbytes,
+                                             current_stream(dy.device)), "selfocc_linear_dgrad_grouped")
+    return dx
+
+
+def linear_wgrad_grouped(dy, x, sizes, with_bias=True):
+    """dy (T, N), x (T, K) -> (dw (G, N, K), db (G, N) | None): group g's gradients from its rows; ONE pass + a per-group reduction"""
+    T, N = dy.shape
+    K = x.shape[1]
+    G = len(sizes)
+    assert sum(sizes) == T and x.shape[0] == T and dy.dtype == torch.float32 and x.dtype == torch.float32
+    dy, x = dy.contiguous(), x.contiguous()
+    dw = torch.empty(G, N, K, device=dy.device, dtype=torch.float32)
+    db = torch.empty(G, N, device=dy.device, dtype=torch.float32) if with_bias else None
+    groups = row_groups(sizes)
+    nbytes = int(lib().selfocc_linear_wgrad_grouped_workspace(T, N, K, groups))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
+    check(lib().selfocc_linear_wgrad_grouped(ptr(dy), ptr(x), ptr(dw), ptr(db), T, N, K, groups, ptr(ws), nbytes,
+                                             current_stream(dy.device)), "selfocc_linear_wgrad_grouped")
+    return dw, db

@@ -98,6 +98,8 @@ class FastLayerNorm(nn.LayerNorm):
 
 def build_norm_layer(cfg, num_features):
     typ = cfg.get('type', 'LN')
+    if typ == 'MultiPlaneNorm':     # the registered module, built as mmcv does: layer(num_features, **the other keys)
+        return 'mpn', MultiPlaneNorm(num_features, **{k: v for k, v in cfg.items() if k != 'type'})
     if typ != 'LN':
         raise NotImplementedError(f"norm {typ}: only LN is used on the SelfOcc hot path")
     return 'ln', FastLayerNorm(num_features, eps=cfg.get('eps', 1e-5))
@@ -480,6 +482,217 @@ class FFN(BaseModule):
         if identity is None:
             identity = x
         return identity + self.dropout_layer(out)
+
+
+# MultiPlaneNorm on the concatenated planes as ONE selfocc_layernorm_*_grouped launch per direction (csrc/layernorm.hip);
+# env SELFOCC_GROUPED_LN=0: one FastLayerNorm call per plane + a cat (A/B)
+GROUPED_LN = os.environ.get('SELFOCC_GROUPED_LN', '1') == '1'
+GROUPED_LN_CALLS = [0]             # forward calls served by the grouped kernel (tests read this)
+
+
+def _row_groups(sizes):
+    from ..linear import row_groups
+    return row_groups(sizes)
+
+
+# MultiPlaneFFN on the concatenated planes through the grouped tall-Linear kernels (selfocc_linear_{fwd,dgrad,wgrad}_grouped): one
+# launch per Linear and direction for the three planes; env SELFOCC_GROUPED_FFN=0: one FFN call per plane (A/B)
+GROUPED_FFN = os.environ.get('SELFOCC_GROUPED_FFN', '1') == '1'
+GROUPED_FFN_CALLS = [0]            # FFN steps served by the grouped kernels (tests read this)
+
+
+class _GroupedTallLinear(torch.autograd.Function):
+    """y = relu?(x W_g^T + b_g) for the rows of group g (``sizes``: host integers), G Linears of the SAME shape with their
+    weights stacked ([G][N][K], the parameters aliased by stacked_view): forward, input gradient and weight / bias gradient
+    are ONE launch each for all groups.  ``wb`` = (weight_1, bias_1, weight_2, bias_2, ...)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, x, sizes, relu, *wb):
+        from ..linear import linear_fwd_grouped
+        w, b = stack_rows(wb[0::2]), stack_rows(wb[1::2])
+        y = linear_fwd_grouped(x, sizes, w, b, relu=relu)
+        # the parameters themselves, not the stacked view: autograd's version check catches in-place updates before backward
+        ctx.save_for_backward(x, y if relu else None, *wb[0::2])
+        ctx.sizes = list(sizes)
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, dy):
+        from ..linear import linear_dgrad_grouped, linear_dgrad_grouped_supported, linear_wgrad_grouped
+        x, y, *ws = ctx.saved_tensors
+        G, (N, K) = len(ws), ws[0].shape
+        dy = dy.contiguous().to(x.dtype)
+        if y is not None:
+            dy = torch.ops.aten.threshold_backward(dy, y, 0)
+        dw, db = linear_wgrad_grouped(dy, x, ctx.sizes)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            if FUSED_DGRAD and linear_dgrad_grouped_supported(ctx.sizes, N, K):
+                dx = linear_dgrad_grouped(dy, stack_rows(ws), ctx.sizes)
+            else:
+                dx = torch.cat([d @ w for d, w in zip(torch.split(dy, ctx.sizes), ws)])
+        return (dx, None, None, *[t for g in range(G) for t in (dw[g], db[g])])
+
+
+class _GroupedLayerNormFunction(torch.autograd.Function):
+    """LayerNorm of (rows, C) with one (weight, bias) pair per row group — the planes of a MultiPlaneNorm, concatenated —
+    through selfocc_layernorm_fwd_grouped / _bwd_grouped: one launch for all groups in each direction.  ``sizes`` are host
+    integers (the plane sizes): no upload, no synchronisation.  ``wb`` = (weight_1, bias_1, weight_2, bias_2, ...)."""
+
+    @staticmethod
+    def forward(ctx, x, sizes, eps, *wb):
+        from .._lib import lib, check, ptr, current_stream
+        C = x.shape[-1]
+        x2 = x.reshape(-1, C).contiguous().float()
+        rows = x2.shape[0]
+        assert sum(sizes) == rows, (sizes, rows)
+        y = torch.empty_like(x2)
+        need = any(ctx.needs_input_grad)
+        mean = torch.empty(rows, device=x.device) if need else None
+        rstd = torch.empty(rows, device=x.device) if need else None
+        w, b = stack_rows(wb[0::2]), stack_rows(wb[1::2])          # (G * C,) = [G][C]
+        check(lib().selfocc_layernorm_fwd_grouped(ptr(x2), ptr(w), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, C, float(eps),
+                                                  _row_groups(sizes), current_stream(x.device)), "selfocc_layernorm_fwd_grouped")
+        if need:
+            # the parameters themselves, not the stacked view: autograd's version check catches in-place updates before backward
+            ctx.save_for_backward(x2, mean, rstd, *wb[0::2])
+        ctx.shape, ctx.sizes = x.shape, list(sizes)
+        GROUPED_LN_CALLS[0] += 1
+        return y.view(x.shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from .._lib import lib, check, ptr, current_stream
+        x2, mean, rstd, *ws = ctx.saved_tensors
+        rows, C = x2.shape
+        G = len(ws)
+        w = stack_rows(ws)
+        dy2 = dy.reshape(rows, C).contiguous().float()
+        dx = torch.empty_like(x2)
+        dg, db = x2.new_empty(G, C), x2.new_empty(G, C)
+        groups = _row_groups(ctx.sizes)
+        nbytes = int(lib().selfocc_layernorm_bwd_grouped_workspace(rows, C, groups))
+        wsp = torch.empty(nbytes, dtype=torch.uint8, device=x2.device)
+        check(lib().selfocc_layernorm_bwd_grouped(ptr(x2), ptr(w), ptr(mean), ptr(rstd), ptr(dy2), ptr(dx), ptr(dg), ptr(db), rows,
+                                                  C, groups, ptr(wsp), nbytes, current_stream(x2.device)),
+              "selfocc_layernorm_bwd_grouped")
+        return (dx.view(ctx.shape), None, None, *[t for g in range(G) for t in (dg[g], db[g])])
+
+
+@MODELS.register_module()
+class MultiPlaneNorm(BaseModule):
+    """model/encoder/tpvformer/modules/split_norm.py: one norm layer per TPV plane (hw, zh, wz) — same constructor, same
+    parameters ``norms.P.{weight,bias}``; ``forward`` takes and returns the planes.  ``forward_cat`` is the same function of
+    the planes' concatenation (what TPVFormerLayer keeps): on the GPU one grouped LayerNorm launch per direction."""
+
+    def __init__(self, embed_dims=64, norm_cfg=dict(type='LN'), init_cfg=None, **kwargs):
+        super().__init__(init_cfg)
+        self.embed_dim = embed_dims
+        self.norm_cfg = norm_cfg
+        if norm_cfg.get('type', 'LN') != 'LN':
+            raise NotImplementedError(f"MultiPlaneNorm of {norm_cfg.get('type')}: only LN is used on the SelfOcc hot path")
+        self.norms = nn.ModuleList([build_norm_layer(self.norm_cfg, self.embed_dim)[1] for _ in range(3)])
+
+    def _grouped_ok(self, x):
+        C = x.shape[-1]
+        n0 = self.norms[0]
+        return (GROUPED_LN and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
+                and C % 4 == 0 and 4 <= C <= 128
+                and all(isinstance(n, FastLayerNorm) and n.elementwise_affine and n.bias is not None
+                        and tuple(n.normalized_shape) == (C,) and n.eps == n0.eps and n.weight.dtype == torch.float32
+                        for n in self.norms))
+
+    def forward_cat(self, x, sizes):
+        """(B, sum sizes, C) concatenated planes -> the same shape, plane p normalised by ``norms[p]``"""
+        assert len(sizes) == len(self.norms) and sum(sizes) == x.shape[1], (sizes, tuple(x.shape))
+        if x.shape[0] == 1 and self._grouped_ok(x):
+            wb = [t for n in self.norms for t in (n.weight, n.bias)]
+            return _GroupedLayerNormFunction.apply(x, list(sizes), self.norms[0].eps, *wb)
+        return torch.cat([n(p) for n, p in zip(self.norms, torch.split(x, list(sizes), 1))], 1)
+
+    def forward(self, tpv):
+        tpv = list(tpv)
+        if len(tpv) == len(self.norms) and tpv[0].dim() == 3 and tpv[0].shape[0] == 1 and self._grouped_ok(tpv[0]):
+            sizes = [p.shape[1] for p in tpv]
+            return list(torch.split(self.forward_cat(torch.cat(tpv, 1), sizes), sizes, 1))
+        return [self.norms[i](plane) for i, plane in enumerate(tpv)]
+
+
+@MODELS.register_module()
+class MultiPlaneFFN(BaseModule):
+    """model/encoder/tpvformer/modules/split_fpn.py: one FFN per TPV plane — same constructor, same parameters
+    ``ffns.P.layers...``; ``forward`` takes and returns the planes, each through the FFN above.  ``forward_cat`` is the same
+    function of the planes' concatenation (what TPVFormerLayer keeps) on the grouped tall-Linear kernels."""
+
+    def __init__(self, embed_dims=256, feedforward_channels=1024, num_fcs=2, ffn_drop=0.,
+                 act_cfg=dict(type='ReLU', inplace=True), init_cfg=None):
+        super().__init__(init_cfg)
+        self.ffn_cfg = dict(type='FFN', embed_dims=embed_dims, feedforward_channels=feedforward_channels, num_fcs=num_fcs,
+                            ffn_drop=ffn_drop, act_cfg=act_cfg)
+        self.embed_dims = embed_dims
+        self.ffns = nn.ModuleList([MODELS.build(dict(self.ffn_cfg)) for _ in range(3)])
+
+    def forward_cat(self, x, sizes, identity=None, post_norm=None):
+        """The same function of the planes' concatenation (1, sum sizes, C) — what TPVFormerLayer keeps — through the grouped
+        tall-Linear kernels, or None where they do not cover the case (the caller then runs the per-plane composition):
+        training = Linear + ReLU, Linear (one _GroupedTallLinear node each), torch dropout on the hidden rows, dropout_add for
+        the last dropout + identity; inference = Linear + ReLU, then Linear + identity + the per-plane LayerNorm of ``post_norm``
+        in the epilogue: two launches for all planes."""
+        from ..linear import linear_fwd_grouped, linear_fwd_grouped_supported, linear_wgrad_grouped_supported
+        f0 = self.ffns[0]
+        if not (GROUPED_FFN and FUSED_LINEAR_FWD and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 1
+                and not torch.is_autocast_enabled() and len(sizes) == len(self.ffns) and sum(sizes) == x.shape[1]
+                and x.shape[1] >= LINEAR_FWD_MIN_ROWS
+                and all(f.num_fcs == 2 and f.add_identity and isinstance(f.layers[0][1], nn.ReLU)
+                        and isinstance(f.dropout_layer, nn.Identity) and f.layers[0][0].weight.dtype == torch.float32
+                        and f.layers[0][0].bias is not None and f.layers[1].bias is not None for f in self.ffns)):
+            return None
+        C, FF = f0.embed_dims, f0.feedforward_channels
+        if not (x.shape[2] == C and linear_fwd_grouped_supported(sizes, FF, C) and linear_fwd_grouped_supported(sizes, C, FF)):
+            return None
+        norms = None
+        if post_norm is not None:
+            norms = list(post_norm.norms)
+            if not (C <= 96 and post_norm._grouped_ok(x)):
+                return None
+        lin0 = [f.layers[0][0] for f in self.ffns]
+        lin1 = [f.layers[1] for f in self.ffns]
+        wb0 = [t for l in lin0 for t in (l.weight, l.bias)]          # the only stacks these parameters are in (stacked_view)
+        wb1 = [t for l in lin1 for t in (l.weight, l.bias)]
+        x2 = x.reshape(x.shape[1], C)
+        idt = x2 if identity is None else identity.reshape(x.shape[1], C)
+        drop0, drop1 = f0.layers[0][2], f0.layers[2]
+        sizes = list(sizes)
+        if torch.is_grad_enabled() and (x.requires_grad or lin0[0].weight.requires_grad):
+            if not (linear_wgrad_grouped_supported(sizes, FF, C) and linear_wgrad_grouped_supported(sizes, C, FF)):
+                return None
+            GROUPED_FFN_CALLS[0] += 1
+            h = drop0(_GroupedTallLinear.apply(x2, sizes, True, *wb0))
+            out = _GroupedTallLinear.apply(h, sizes, False, *wb1)
+            if FUSED_DROPOUT_ADD:
+                out = dropout_add(out, idt, drop1.p, drop1.training)
+            else:
+                out = idt + drop1(out)
+            out = out.view(x.shape)
+            return post_norm.forward_cat(out, sizes) if post_norm is not None else out
+        if torch.is_grad_enabled() or (self.training and (drop0.p > 0 or drop1.p > 0)):
+            return None
+        GROUPED_FFN_CALLS[0] += 1
+        h = linear_fwd_grouped(x2, sizes, stack_rows(wb0[0::2]), stack_rows(wb0[1::2]), relu=True)
+        ln = None
+        if norms is not None:
+            ln = (stack_rows([n.weight for n in norms]), stack_rows([n.bias for n in norms]), norms[0].eps)
+        return linear_fwd_grouped(h, sizes, stack_rows(wb1[0::2]), stack_rows(wb1[1::2]), residual=idt, ln=ln).view(x.shape)
+
+    def forward(self, tpv, identity=None, post_norm=None):
+        """``post_norm``: the layer's next MultiPlaneNorm; plane p's result then goes through ``post_norm.norms[p]``"""
+        if identity is None:
+            identity = [None] * 3
+        norms = [None] * 3 if post_norm is None else list(post_norm.norms)
+        return [self.ffns[i](plane, identity[i], post_norm=norms[i]) for i, plane in enumerate(tpv)]
 
 
 # training: the FFN's Linear + ReLU as one autograd node (_TallLinear with relu); env SELFOCC_FUSED_FFN_RELU=0: nn.Sequential

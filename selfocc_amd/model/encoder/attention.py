@@ -283,10 +283,13 @@ class TPVCrossAttention(BaseModule):
                                               self.attns[0].deformable_attention.num_heads)
             if v3 is not None:
                 vpre = list(v3)    # (cams, heads, l, d) each: `_forward_camera_loop` takes a 4-d value_pre as head-major
+        # the layer's next norm rides in each plane's output projection: the shared LayerNorm, or plane i's own of a MultiPlaneNorm
+        post_norm = kwargs.get('post_norm')
+        norms = list(post_norm.norms) if isinstance(post_norm, bricks.MultiPlaneNorm) else [post_norm] * 3
         return [self.attns[i](query[i], key, value, residual[i] if residual is not None else None,
                               spatial_shapes=spatial_shapes, level_start_index=level_start_index,
                               reference_points_cams=reference_points_cams[i], bev_masks=tpv_masks[i],
-                              rebatch_plan=plans[i], out=outs[i], value_pre=vpre[i], post_norm=kwargs.get('post_norm'))
+                              rebatch_plan=plans[i], out=outs[i], value_pre=vpre[i], post_norm=norms[i])
                 for i in range(3)]
 
 
