@@ -12,36 +12,14 @@
 //
 // Row groups (selfocc_layernorm_*_grouped: the reference's MultiPlaneNorm, modules/split_norm.py — one (gamma, beta) per TPV
 // plane — on the concatenated planes): the same kernels, a workgroup serving rows of ONE group.  The launcher gives group g
-// the blocks blk_start[g] .. blk_start[g + 1] - 1 (what the ungrouped launch would give a tensor of that many rows); a block
-// finds its group with <= 7 scalar compares on the by-value table, strides over that group's rows only and reads that group's
+// the blocks unit_start[g] .. unit_start[g + 1] - 1 of the group table (so_device.h; what the ungrouped launch would give a tensor
+// of that many rows); a block finds its group with <= 7 scalar compares on the by-value table (so_group_of), strides over that group's rows only and reads that group's
 // gamma / beta once, as before.  The backward's partials stay one slot per block, and the reduce kernel runs once per group
 // (blockIdx.y) over the group's slots — fixed order, an empty group sums nothing and writes zeros.  One group = the ungrouped
 // launch: same blocks, same rows per lane, same summation order, same bits.
 #include "so_device.h"
 
 namespace {
-
-struct LnGroups {            // by value in the kernel arguments; indexed with compile-time constants only (no scratch copy)
-    int n;
-    int blk_start[9];
-    long long row_start[9];
-};
-
-struct LnBlock { int g, blk, nblk; long long row_lo, row_hi; };
-
-SO_DEVFN LnBlock so_ln_block(const LnGroups &gr) {      // the group this workgroup serves (uniform: scalar registers)
-    const int b = (int)blockIdx.x;
-    LnBlock r;
-    r.g = 0; r.blk = b; r.nblk = gr.blk_start[1]; r.row_lo = 0; r.row_hi = gr.row_start[1];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) {
-        if (i < gr.n && b >= gr.blk_start[i]) {
-            r.g = i; r.blk = b - gr.blk_start[i]; r.nblk = gr.blk_start[i + 1] - gr.blk_start[i];
-            r.row_lo = gr.row_start[i]; r.row_hi = gr.row_start[i + 1];
-        }
-    }
-    return r;
-}
 
 SO_DEVFN float so_half_sum(float v) {   // sum over the 32 lanes of a half wave
 #pragma unroll
@@ -52,8 +30,8 @@ SO_DEVFN float so_half_sum(float v) {   // sum over the 32 lanes of a half wave
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
                                                             const float *__restrict__ beta, float *__restrict__ y,
                                                             float *__restrict__ mean_out, float *__restrict__ rstd_out,
-                                                            LnGroups gr, int C, float eps) {
-    const LnBlock blk = so_ln_block(gr);
+                                                            so_group_table gr, int C, float eps) {
+    const auto blk = so_group_of(gr, (int)blockIdx.x);      // uniform: scalar registers
     gamma += (size_t)blk.g * C;
     beta += (size_t)blk.g * C;
     const int C4 = C >> 2;
@@ -62,8 +40,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restr
     const float4 g4 = lane_on ? ((const float4 *)gamma)[l] : make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 b4 = lane_on ? ((const float4 *)beta)[l] : make_float4(0.f, 0.f, 0.f, 0.f);
     const float inv_c = 1.0f / (float)C;
-    const long long half0 = ((long long)blk.blk * 256 + threadIdx.x) >> 5;
-    const long long nhalf = ((long long)blk.nblk * 256) >> 5;
+    const long long half0 = ((long long)blk.unit * 256 + threadIdx.x) >> 5;
+    const long long nhalf = ((long long)blk.units * 256) >> 5;
     const long long rows = blk.row_hi;
     for (long long row = blk.row_lo + half0; row < rows; row += nhalf) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -87,9 +65,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float *__restr
                                                             const float *__restrict__ mean_in, const float *__restrict__ rstd_in,
                                                             const float *__restrict__ dy, float *__restrict__ dx,
                                                             float *__restrict__ partial /* [gridDim.x][2][C] */,
-                                                            LnGroups gr, int C) {
+                                                            so_group_table gr, int C) {
     __shared__ float s_red[8][2][128];
-    const LnBlock blk = so_ln_block(gr);
+    const auto blk = so_group_of(gr, (int)blockIdx.x);      // uniform: scalar registers
     gamma += (size_t)blk.g * C;
     const int C4 = C >> 2;
     const int l = threadIdx.x & 31, hw = threadIdx.x >> 5;
@@ -97,8 +75,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float *__restr
     const float4 g4 = lane_on ? ((const float4 *)gamma)[l] : make_float4(0.f, 0.f, 0.f, 0.f);
     const float inv_c = 1.0f / (float)C;
     float4 dg = make_float4(0.f, 0.f, 0.f, 0.f), db = make_float4(0.f, 0.f, 0.f, 0.f);
-    const long long half0 = ((long long)blk.blk * 256 + threadIdx.x) >> 5;
-    const long long nhalf = ((long long)blk.nblk * 256) >> 5;
+    const long long half0 = ((long long)blk.unit * 256 + threadIdx.x) >> 5;
+    const long long nhalf = ((long long)blk.units * 256) >> 5;
     const long long rows = blk.row_hi;
     for (long long row = blk.row_lo + half0; row < rows; row += nhalf) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f), g = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -132,16 +110,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float *__restr
     }
 }
 
-__global__ __launch_bounds__(256) void layernorm_bwd_reduce_kernel(const float *__restrict__ partial, LnGroups gr, int C,
+__global__ __launch_bounds__(256) void layernorm_bwd_reduce_kernel(const float *__restrict__ partial, so_group_table gr, int C,
                                                                    float *__restrict__ dgamma, float *__restrict__ dbeta) {
     // one wave per output element (2 * C of them per group = blockIdx.y): fixed-order tree over the group's blocks' partials
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (e >= 2 * C) return;
-    int b0 = 0, nblocks = gr.blk_start[1];
-#pragma unroll
-    for (int i = 1; i < 8; ++i)
-        if (i == (int)blockIdx.y) { b0 = gr.blk_start[i]; nblocks = gr.blk_start[i + 1] - gr.blk_start[i]; }
-    partial += (size_t)b0 * 2 * C;
+    const auto grp = so_group_of<true>(gr, (int)blockIdx.y);
+    const int nblocks = grp.units;
+    partial += (size_t)grp.first * 2 * C;
     dgamma += (size_t)blockIdx.y * C;
     dbeta += (size_t)blockIdx.y * C;
     const int which = e / C, c = e - which * C;
@@ -157,47 +133,33 @@ int ln_blocks(long long rows) {
     return (int)(need < 2048 ? (need < 1 ? 1 : need) : 2048);
 }
 
-LnGroups ln_one_group(long long rows) {
-    LnGroups g = {};
+so_group_table ln_one_group(long long rows) {
+    so_group_table g = {};
     g.n = 1;
-    g.blk_start[1] = ln_blocks(rows);
+    g.unit_start[1] = ln_blocks(rows);
     g.row_start[1] = rows;
     return g;
 }
 
 // host logic only: < 0 (message set) for a bad table, else 0 and the block table — group g gets the blocks an ungrouped launch
 // of its rows would get, an empty group none
-int ln_groups(const so_row_groups &in, long long rows, LnGroups *out) {
-    SO_REQUIRE(in.n_groups >= 1 && in.n_groups <= 8, "layernorm: n_groups must be in [1, 8] (got %d)", in.n_groups);
-    SO_REQUIRE(in.row_start[0] == 0, "layernorm: row_start[0] must be 0 (got %lld)", (long long)in.row_start[0]);
-    for (int g = 0; g < in.n_groups; ++g)
-        SO_REQUIRE(in.row_start[g + 1] >= in.row_start[g], "layernorm: row_start must be non-decreasing (row_start[%d] = %lld < "
-                   "row_start[%d] = %lld)", g + 1, (long long)in.row_start[g + 1], g, (long long)in.row_start[g]);
-    SO_REQUIRE(in.row_start[in.n_groups] == rows, "layernorm: row_start[n_groups] = %lld must equal rows = %lld",
-               (long long)in.row_start[in.n_groups], rows);
-    LnGroups g = {};
-    g.n = in.n_groups;
-    for (int i = 0; i < in.n_groups; ++i) {
-        const long long r = in.row_start[i + 1] - in.row_start[i];
-        g.blk_start[i + 1] = g.blk_start[i] + (r > 0 ? ln_blocks(r) : 0);
-        g.row_start[i + 1] = in.row_start[i + 1];
-    }
-    for (int i = in.n_groups + 1; i < 9; ++i) { g.blk_start[i] = g.blk_start[in.n_groups]; g.row_start[i] = rows; }
-    *out = g;
+int ln_groups(const so_row_groups &in, long long rows, so_group_table *out) {
+    if (so_check_row_groups(in, rows, "layernorm") < 0) return -1;
+    *out = so_build_group_table(in, [](long long r) { return r > 0 ? ln_blocks(r) : 0; });
     return 0;
 }
 
 int ln_fwd_launch(const float *x, const float *gamma, const float *beta, float *y, float *mean, float *rstd, long long rows,
-                  int C, float eps, const LnGroups &gr, hipStream_t st) {
+                  int C, float eps, const so_group_table &gr, hipStream_t st) {
     if (rows == 0) return 0;
     SO_REQUIRE(x && gamma && beta && y, "layernorm: NULL pointer");
     SO_REQUIRE((mean == nullptr) == (rstd == nullptr), "layernorm: mean and rstd go together");
-    hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(gr.blk_start[gr.n]), dim3(256), 0, st, x, gamma, beta, y, mean, rstd, gr, C, eps);
+    hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(gr.unit_start[gr.n]), dim3(256), 0, st, x, gamma, beta, y, mean, rstd, gr, C, eps);
     return so_launch_status();
 }
 
 int ln_bwd_launch(const float *x, const float *gamma, const float *mean, const float *rstd, const float *dy, float *dx,
-                  float *dgamma, float *dbeta, long long rows, int C, const LnGroups &gr, void *workspace, size_t workspace_bytes,
+                  float *dgamma, float *dbeta, long long rows, int C, const so_group_table &gr, void *workspace, size_t workspace_bytes,
                   hipStream_t st) {
     SO_REQUIRE(dgamma && dbeta, "layernorm_bwd: NULL gradient pointer");
     if (rows == 0) {   // empty input: the parameter gradients are zero, nothing else to write
@@ -205,7 +167,7 @@ int ln_bwd_launch(const float *x, const float *gamma, const float *mean, const f
         return (int)hipMemsetAsync(dbeta, 0, (size_t)gr.n * C * sizeof(float), st);
     }
     SO_REQUIRE(x && gamma && mean && rstd && dy && dx, "layernorm_bwd: NULL pointer");
-    const int nb = gr.blk_start[gr.n];
+    const int nb = gr.unit_start[gr.n];
     SO_REQUIRE(workspace && workspace_bytes >= (size_t)nb * 2 * C * sizeof(float), "layernorm_bwd: workspace too small");
     hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nb), dim3(256), 0, st, x, gamma, mean, rstd, dy, dx, (float *)workspace, gr, C);
     hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((2 * C + 3) / 4, gr.n), dim3(256), 0, st, (const float *)workspace, gr, C,
@@ -238,7 +200,7 @@ extern "C" int selfocc_layernorm_bwd(const float *x, const float *gamma, const f
 }
 
 extern "C" int selfocc_layernorm_grouped_supported(int64_t rows, int32_t C, so_row_groups groups) {
-    LnGroups gr;
+    so_group_table gr;
     if (ln_groups(groups, rows, &gr) < 0) return -1;
     return (rows >= 0 && C >= 4 && C <= 128 && C % 4 == 0) ? 1 : 0;
 }
@@ -247,15 +209,15 @@ extern "C" int selfocc_layernorm_fwd_grouped(const float *x, const float *gamma,
                                              float *rstd, int64_t rows, int32_t C, float eps, so_row_groups groups,
                                              void *stream) {
     SO_LN_CHECK_SHAPE();
-    LnGroups gr;
+    so_group_table gr;
     if (ln_groups(groups, rows, &gr) < 0) return -1;
     return ln_fwd_launch(x, gamma, beta, y, mean, rstd, rows, C, eps, gr, (hipStream_t)stream);
 }
 
 extern "C" size_t selfocc_layernorm_bwd_grouped_workspace(int64_t rows, int32_t C, so_row_groups groups) {
-    LnGroups gr;
+    so_group_table gr;
     if (rows < 0 || C < 4 || ln_groups(groups, rows, &gr) < 0) return 0;
-    const size_t nb = (size_t)(gr.blk_start[gr.n] > 0 ? gr.blk_start[gr.n] : 1);
+    const size_t nb = (size_t)(gr.unit_start[gr.n] > 0 ? gr.unit_start[gr.n] : 1);
     return nb * 2 * (size_t)C * sizeof(float);
 }
 
@@ -263,7 +225,7 @@ extern "C" int selfocc_layernorm_bwd_grouped(const float *x, const float *gamma,
                                              const float *dy, float *dx, float *dgamma, float *dbeta, int64_t rows, int32_t C,
                                              so_row_groups groups, void *workspace, size_t workspace_bytes, void *stream) {
     SO_LN_CHECK_SHAPE();
-    LnGroups gr;
+    so_group_table gr;
     if (ln_groups(groups, rows, &gr) < 0) return -1;
     return ln_bwd_launch(x, gamma, mean, rstd, dy, dx, dgamma, dbeta, rows, C, gr, workspace, workspace_bytes, (hipStream_t)stream);
 }

@@ -34,27 +34,16 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// Row groups (selfocc_linear_wgrad_grouped): group g owns the chunks chunk_start[g] .. chunk_start[g + 1] - 1, which walk its rows
-// row_start[g] .. row_start[g + 1] - 1 in steps of rows_per_block — a chunk never straddles a group.  By value in the kernel
-// arguments, indexed with constants only.
-struct WgGroups {
-    int n;
-    int chunk_start[9];
-    long long row_start[9];
-};
-
+// Row groups (selfocc_linear_wgrad_grouped): the units of the table (so_device.h) are the chunks, which walk their group's rows
+// in steps of rows_per_block — a chunk never straddles a group.
 template <bool GRP>
-SO_DEVFN void so_wgrad_chunk(const WgGroups &gr, int chunk, long long rows_per_block, long long T, long long &r_blk, long long &r_end) {
+SO_DEVFN void so_wgrad_chunk(const so_group_table &gr, int chunk, long long rows_per_block, long long T, long long &r_blk, long long &r_end) {
     r_blk = (long long)chunk * rows_per_block;
     r_end = T;
     if constexpr (GRP) {
-        int c0 = 0;
-        long long lo = 0, hi = gr.row_start[1];
-#pragma unroll
-        for (int i = 1; i < 8; ++i)
-            if (i < gr.n && chunk >= gr.chunk_start[i]) { c0 = gr.chunk_start[i]; lo = gr.row_start[i]; hi = gr.row_start[i + 1]; }
-        r_blk = lo + (long long)(chunk - c0) * rows_per_block;
-        r_end = hi;
+        const auto p = so_group_of(gr, chunk);
+        r_blk = p.row_lo + (long long)p.unit * rows_per_block;
+        r_end = p.row_hi;
     }
 }
 
@@ -64,7 +53,7 @@ template <int KT, int NTW, bool GRP = false>
 __global__ __launch_bounds__(256, 2) void linear_wgrad_kernel(const float *__restrict__ dy, const float *__restrict__ x,
                                                               float *__restrict__ part_w /* [chunks][N][K] */,
                                                               float *__restrict__ part_b /* [chunks][N] */,
-                                                              long long T, int N, int K, long long rows_per_block, WgGroups gr) {
+                                                              long long T, int N, int K, long long rows_per_block, so_group_table gr) {
     constexpr int U = (NTW * KT > 9) ? kRowPairsAhead / 2 : kRowPairsAhead;   // 12 tiles: 192 accumulator registers
     __shared__ float red[NTW * KT * 1024];
     __shared__ float red_b[4][NTW * 32];
@@ -195,7 +184,7 @@ SO_DEVFN void so_wsplit3(const float (&x)[8], bf16x8w &a1, bf16x8w &a2, bf16x8w 
 template <int KT, int NTW, bool GRP = false>
 __global__ __launch_bounds__(256, 2) void linear_wgrad_b3_kernel(const float *__restrict__ dy, const float *__restrict__ x,
                                                                  float *__restrict__ part_w, float *__restrict__ part_b,
-                                                                 long long T, int N, int K, long long rows_per_block, WgGroups gr) {
+                                                                 long long T, int N, int K, long long rows_per_block, so_group_table gr) {
     __shared__ float red[NTW * KT * 1024];
     __shared__ float red_b[4][NTW * 32];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -321,15 +310,13 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_b3_kernel(const float *__
 // elements (8 loads in flight), the four waves are combined through LDS
 __global__ __launch_bounds__(256) void linear_wgrad_reduce_kernel(const float *__restrict__ part_w,
                                                                   const float *__restrict__ part_b,
-                                                                  float *__restrict__ dw, float *__restrict__ db, WgGroups gr,
+                                                                  float *__restrict__ dw, float *__restrict__ db, so_group_table gr,
                                                                   int NK, int N) {
     // blockIdx.y = row group: its chunks' partials -> its dw / db (an empty group sums nothing: zeros)
-    int c0 = 0, chunks = gr.chunk_start[1];
-#pragma unroll
-    for (int i = 1; i < 8; ++i)
-        if (i == (int)blockIdx.y) { c0 = gr.chunk_start[i]; chunks = gr.chunk_start[i + 1] - gr.chunk_start[i]; }
-    part_w += (size_t)c0 * NK;
-    part_b += (size_t)c0 * N;
+    const auto grp = so_group_of<true>(gr, (int)blockIdx.y);
+    const int chunks = grp.units;
+    part_w += (size_t)grp.first * NK;
+    part_b += (size_t)grp.first * N;
     dw += (size_t)blockIdx.y * NK;
     if (db) db += (size_t)blockIdx.y * N;
     __shared__ float red[4][64];
@@ -411,56 +398,44 @@ extern "C" size_t selfocc_linear_wgrad_workspace(int64_t T, int32_t N, int32_t K
 }
 
 // the chunk table: group g's rows in ceil(rows_g / rows_per_block) chunks of the plan's rows_per_block (none for an empty group)
-static WgGroups so_wgrad_groups(const so_row_groups &in, const WgradPlan &p) {
-    WgGroups g = {};
-    g.n = in.n_groups;
-    for (int i = 0; i < in.n_groups; ++i) {
-        const long long r = in.row_start[i + 1] - in.row_start[i];
-        g.chunk_start[i + 1] = g.chunk_start[i] + (int)((r + p.rows_per_block - 1) / p.rows_per_block);
-        g.row_start[i + 1] = in.row_start[i + 1];
-    }
-    for (int i = in.n_groups + 1; i < 9; ++i) { g.chunk_start[i] = g.chunk_start[in.n_groups]; g.row_start[i] = in.row_start[in.n_groups]; }
-    return g;
+static so_group_table so_wgrad_groups(const so_row_groups &in, const WgradPlan &p) {
+    return so_build_group_table(in, [&](long long rows) { return (rows + p.rows_per_block - 1) / p.rows_per_block; });
 }
 
 static int so_wgrad_launch(const float *dy, const float *x, float *dw, float *db, long long T, int N, int K, const WgradPlan &p,
-                           const WgGroups &gr, bool grouped, void *workspace, size_t workspace_bytes, void *stream) {
+                           const so_group_table &gr, bool grouped, void *workspace, size_t workspace_bytes, void *stream) {
     SO_REQUIRE(dy && x && dw, "linear_wgrad: NULL pointer");
-    const int chunks = gr.chunk_start[gr.n];
+    const int chunks = gr.unit_start[gr.n];
     const size_t need = (size_t)chunks * ((size_t)N * K + N) * sizeof(float);
     SO_REQUIRE(workspace != nullptr && workspace_bytes >= need, "linear_wgrad: workspace too small (%zu bytes, need %zu)",
                workspace_bytes, need);
     float *part_w = (float *)workspace, *part_b = part_w + (size_t)chunks * N * K;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)chunks, (unsigned)p.ngroups);
-    const bool use_b3 = so_wgrad_b3();
-#define SO_LAUNCH_F32(KT_, NTW_)                                                                                   \
-    do {                                                                                                           \
-        if (grouped) hipLaunchKernelGGL((linear_wgrad_kernel<KT_, NTW_, true>), grid, dim3(256), 0, st, dy, x, part_w, part_b, T, N, K, p.rows_per_block, gr); \
-        else hipLaunchKernelGGL((linear_wgrad_kernel<KT_, NTW_, false>), grid, dim3(256), 0, st, dy, x, part_w, part_b, T, N, K, p.rows_per_block, gr); \
-    } while (0)
-#define SO_LAUNCH_B3(KT_, NTW_)                                                                                    \
-    do {                                                                                                           \
-        if (grouped) hipLaunchKernelGGL((linear_wgrad_b3_kernel<KT_, NTW_, true>), grid, dim3(256), 0, st, dy, x, part_w, part_b, T, N, K, p.rows_per_block, gr); \
-        else hipLaunchKernelGGL((linear_wgrad_b3_kernel<KT_, NTW_, false>), grid, dim3(256), 0, st, dy, x, part_w, part_b, T, N, K, p.rows_per_block, gr); \
-    } while (0)
-    // (KT, NTW) pairs of the plan; only the pairs a plan can produce are instantiated (the b3 kernel at 3 x 3 / 4 x 3 / 6 x 2
+    const bool b3 = so_wgrad_b3() && p.kt != 4;      // K = 128 stays on the f32-MFMA kernel
+    bool launched = chunks == 0;
+    // one (kernel, KT, NTW) of the list below: launched when it is the plan's
+    auto pass = [&](auto B3, auto KT, auto NTW) {
+        if (launched || b3 != B3 || p.kt != KT || p.ntw != NTW) return;
+        launched = true;
+        so_with_const<bool, true, false>(grouped, [&](auto GRP) {
+            if constexpr (B3)
+                hipLaunchKernelGGL((linear_wgrad_b3_kernel<KT, NTW, GRP>), grid, dim3(256), 0, st, dy, x, part_w, part_b, T, N, K,
+                                   p.rows_per_block, gr);
+            else
+                hipLaunchKernelGGL((linear_wgrad_kernel<KT, NTW, GRP>), grid, dim3(256), 0, st, dy, x, part_w, part_b, T, N, K,
+                                   p.rows_per_block, gr);
+        });
+    };
+    // the (KT, NTW) pairs so_wgrad_plan can produce; only these are instantiated (the b3 kernel at 3 x 3 / 4 x 3 / 6 x 2
     // accumulator tiles needs more than 256 registers)
-    if (chunks > 0) {
-        switch (p.kt) {
-            case 1: if (use_b3) SO_LAUNCH_B3(1, 4); else SO_LAUNCH_F32(1, 4); break;
-            case 2: if (use_b3) SO_LAUNCH_B3(2, 2); else SO_LAUNCH_F32(2, 4); break;
-            case 3:
-                if (!use_b3) SO_LAUNCH_F32(3, 3);
-                else if (p.ntw == 1) SO_LAUNCH_B3(3, 1);
-                else SO_LAUNCH_B3(3, 2);
-                break;
-            case 4: SO_LAUNCH_F32(4, 3); break;
-            default: if (use_b3) SO_LAUNCH_B3(6, 1); else SO_LAUNCH_F32(6, 2); break;
-        }
-    }
-#undef SO_LAUNCH_F32
-#undef SO_LAUNCH_B3
+    constexpr std::true_type B3;
+    constexpr std::false_type F32;
+    pass(B3, so_int<1>{}, so_int<4>{}); pass(B3, so_int<2>{}, so_int<2>{}); pass(B3, so_int<3>{}, so_int<1>{});
+    pass(B3, so_int<3>{}, so_int<2>{}); pass(B3, so_int<6>{}, so_int<1>{});
+    pass(F32, so_int<1>{}, so_int<4>{}); pass(F32, so_int<2>{}, so_int<4>{}); pass(F32, so_int<3>{}, so_int<3>{});
+    pass(F32, so_int<4>{}, so_int<3>{}); pass(F32, so_int<6>{}, so_int<2>{});
+    SO_REQUIRE(launched, "linear_wgrad: no kernel for the plan's KT = %d, NTW = %d", p.kt, p.ntw);
     const int NK = N * K;
     hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((unsigned)((NK + N + 63) / 64), (unsigned)gr.n), dim3(256), 0, st, part_w,
                        part_b, dw, db, gr, NK, N);
@@ -472,15 +447,15 @@ extern "C" int selfocc_linear_wgrad(const float *dy, const float *x, float *dw, 
     WgradPlan p;
     SO_REQUIRE(so_wgrad_plan(T, N, K, p), "linear_wgrad: unsupported shape (T = %lld rows, N = %d, K = %d; K must be 32, 64, "
                "96, 128 or 192)", (long long)T, N, K);
-    WgGroups gr = {};
+    so_group_table gr = {};
     gr.n = 1;
-    gr.chunk_start[1] = p.chunks;
+    gr.unit_start[1] = p.chunks;
     gr.row_start[1] = T;
     return so_wgrad_launch(dy, x, dw, db, T, N, K, p, gr, false, workspace, workspace_bytes, stream);
 }
 
 // the plan of the grouped pass: the ungrouped plan of all T rows (kernel choice, rows per chunk), chunks cut per group
-static int so_wgrad_grouped_plan(long long T, int N, int K, const so_row_groups &groups, WgradPlan &p, WgGroups &gr) {
+static int so_wgrad_grouped_plan(long long T, int N, int K, const so_row_groups &groups, WgradPlan &p, so_group_table &gr) {
     if (so_check_row_groups(groups, T, "linear_wgrad_grouped") < 0) return -1;
     SO_REQUIRE(so_wgrad_plan(T > 0 ? T : 1, N, K, p), "linear_wgrad_grouped: unsupported shape (T = %lld rows, N = %d, K = %d; K must "
                "be 32, 64, 96, 128 or 192)", T, N, K);
@@ -496,16 +471,16 @@ extern "C" int selfocc_linear_wgrad_grouped_supported(int64_t T, int32_t N, int3
 
 extern "C" size_t selfocc_linear_wgrad_grouped_workspace(int64_t T, int32_t N, int32_t K, so_row_groups groups) {
     WgradPlan p;
-    WgGroups gr;
+    so_group_table gr;
     if (so_wgrad_grouped_plan(T, N, K, groups, p, gr) < 0) return 0;
-    const size_t chunks = (size_t)std::max(1, gr.chunk_start[gr.n]);
+    const size_t chunks = (size_t)std::max(1, gr.unit_start[gr.n]);
     return chunks * ((size_t)N * K + N) * sizeof(float);
 }
 
 extern "C" int selfocc_linear_wgrad_grouped(const float *dy, const float *x, float *dw, float *db, int64_t T, int32_t N, int32_t K,
                                             so_row_groups groups, void *workspace, size_t workspace_bytes, void *stream) {
     WgradPlan p;
-    WgGroups gr;
+    so_group_table gr;
     if (so_wgrad_grouped_plan(T, N, K, groups, p, gr) < 0) return -1;
     return so_wgrad_launch(dy, x, dw, db, T, N, K, p, gr, true, workspace, workspace_bytes, stream);
 }

@@ -53,31 +53,13 @@ extern "C" int selfocc_diag_lin_trace(unsigned long long *dst, size_t n) {
 
 namespace {
 
-// Row groups (selfocc_linear_*_grouped): the persistent blocks with row index rc_start[g] .. rc_start[g + 1] - 1 (per column
-// block) serve the rows row_start[g] .. row_start[g + 1] - 1 with group g's weights — a block belongs to ONE group, so it stages
-// W once, exactly as the ungrouped launch does.  By value in the kernel arguments, indexed with constants only.
+// Row groups (selfocc_linear_*_grouped): the units of the table (so_device.h) are the persistent blocks' row indices (per column
+// block) — a block belongs to ONE group, so it stages W once, exactly as the ungrouped launch does.
 struct LinGroups {
-    int n;
-    int rc_start[9];
-    long long row_start[9];
+    so_group_table t;
     long long w_stride, b_stride, ln_stride;      // floats between two groups' W / bias / LayerNorm parameters (0: shared)
     long long planes_stride;                      // dgrad: bf16 elements between two groups' split planes
 };
-
-template <bool GRP>
-SO_DEVFN int so_lin_pick_group(const LinGroups &gr, long long &rc, int &groups, long long &r_lo, long long &r_hi) {
-    int g = 0;
-    if constexpr (GRP) {
-        int c0 = 0, c1 = gr.rc_start[1];
-        r_lo = 0; r_hi = gr.row_start[1];
-#pragma unroll
-        for (int i = 1; i < 8; ++i)
-            if (i < gr.n && rc >= gr.rc_start[i]) { g = i; c0 = gr.rc_start[i]; c1 = gr.rc_start[i + 1]; r_lo = gr.row_start[i]; r_hi = gr.row_start[i + 1]; }
-        rc -= c0;
-        groups = c1 - c0;
-    }
-    return g;
-}
 
 struct LinearFwdArgs {
     LinGroups gr;
@@ -97,15 +79,15 @@ struct LinearFwdArgs {
 template <bool GRP>
 SO_DEVFN void so_lin_group(LinearFwdArgs &a, long long &rc) {
     if constexpr (GRP) {
-        long long r_lo = 0, r_hi = 0;
-        const int g = so_lin_pick_group<GRP>(a.gr, rc, a.groups, r_lo, r_hi);
-        a.x += r_lo * a.K; a.y += r_lo * a.ldy; a.T = r_hi - r_lo;
-        if (a.residual) a.residual += r_lo * a.ldr;
-        if (a.y_pre) a.y_pre += r_lo * a.N;
-        if (a.mean) { a.mean += r_lo; a.rstd += r_lo; }
-        a.w += g * a.gr.w_stride;
-        if (a.bias) a.bias += g * a.gr.b_stride;
-        if (a.gamma) { a.gamma += g * a.gr.ln_stride; a.beta += g * a.gr.ln_stride; }
+        const auto p = so_group_of(a.gr.t, rc);
+        rc = p.unit; a.groups = p.units;
+        a.x += p.row_lo * a.K; a.y += p.row_lo * a.ldy; a.T = p.row_hi - p.row_lo;
+        if (a.residual) a.residual += p.row_lo * a.ldr;
+        if (a.y_pre) a.y_pre += p.row_lo * a.N;
+        if (a.mean) { a.mean += p.row_lo; a.rstd += p.row_lo; }
+        a.w += p.g * a.gr.w_stride;
+        if (a.bias) a.bias += p.g * a.gr.b_stride;
+        if (a.gamma) { a.gamma += p.g * a.gr.ln_stride; a.beta += p.g * a.gr.ln_stride; }
     }
 }
 
@@ -711,11 +693,11 @@ __global__ __launch_bounds__(256) void linear_dgrad_b3_kernel(LinearDgradArgs a)
     const int cb = __builtin_amdgcn_readfirstlane((int)(logical % (unsigned)ncb));
     long long rc = __builtin_amdgcn_readfirstlane((int)(logical / (unsigned)ncb));
     if constexpr (GRP) {
-        long long r_lo = 0, r_hi = 0;
-        const int g = so_lin_pick_group<GRP>(a.gr, rc, a.groups, r_lo, r_hi);
-        a.dy += r_lo * a.N; a.dx += r_lo * a.K; a.T = r_hi - r_lo;
-        a.w += g * a.gr.w_stride;
-        if (a.planes) a.planes += g * a.gr.planes_stride;
+        const auto p = so_group_of(a.gr.t, rc);
+        rc = p.unit; a.groups = p.units;
+        a.dy += p.row_lo * a.N; a.dx += p.row_lo * a.K; a.T = p.row_hi - p.row_lo;
+        a.w += p.g * a.gr.w_stride;
+        if (a.planes) a.planes += p.g * a.gr.planes_stride;
     }
     const int n0 = cb * 96;
     const long long nwt = (a.T + 31) / 32, wt_step = (long long)WAVES * a.groups;
@@ -882,28 +864,15 @@ static int so_linear_fwd_launch(const float *x, const float *w, const float *bia
     LinearFwdArgs a;
     a.gr = LinGroups{};
     if (grouped) {
-        a.gr.n = row_groups->n_groups;
-        for (int i = 0; i < 9; ++i) a.gr.row_start[i] = row_groups->row_start[i < row_groups->n_groups ? i : row_groups->n_groups];
         a.gr.w_stride = w_group_stride;
         a.gr.b_stride = w_group_stride ? N : 0;
         a.gr.ln_stride = ln_group_stride;
     }
-    // grouped: the `total` row blocks (per column block) the ungrouped launch would use, dealt to the groups in proportion to
-    // their row tiles — at least one for a group with rows, never more than it has tiles for its waves; returns their sum
+    // the row blocks (per column block) of a launch: the `total` of the ungrouped launch, or those dealt to the groups
     auto deal = [&](long long total, long long tile_rows, long long waves) -> long long {
         if (!grouped) return total;
-        long long tiles[8], all = 0, acc = 0;
-        for (int g = 0; g < a.gr.n; ++g) {
-            tiles[g] = (a.gr.row_start[g + 1] - a.gr.row_start[g] + tile_rows - 1) / tile_rows;
-            all += tiles[g];
-        }
-        for (int g = 0; g < a.gr.n; ++g) {
-            long long want = 0;
-            if (tiles[g] > 0) want = std::max(1LL, std::min((tiles[g] + waves - 1) / waves, (total * tiles[g] + all / 2) / all));
-            a.gr.rc_start[g + 1] = (int)(acc += want);
-        }
-        for (int i = a.gr.n + 1; i < 9; ++i) a.gr.rc_start[i] = (int)acc;
-        return acc;
+        a.gr.t = so_deal_row_blocks(*row_groups, total, tile_rows, waves);
+        return a.gr.t.unit_start[a.gr.t.n];
     };
     a.x = x; a.w = w; a.bias = bias; a.residual = residual; a.gamma = ln_gamma; a.beta = ln_beta;
     a.y = y; a.y_pre = y_pre; a.mean = mean; a.rstd = rstd;
@@ -939,28 +908,14 @@ static int so_linear_fwd_launch(const float *x, const float *w, const float *bia
             groups3 = std::min(groups3, (nwt3 + 7) / 8);
             a.groups = (int)groups3;
             const long long nblk3 = deal(groups3, 16, 8) * a.ncb;
-#define SO_B3_K192_G(LN_, NT_, GRP_)                                                                                  \
-    do {                                                                                                             \
-        static std::atomic<unsigned long long> done_mask{0};                                                         \
-        int dev_ = 0;                                                                                                \
-        (void)hipGetDevice(&dev_);                                                                                   \
-        const unsigned long long bit_ = 1ull << (dev_ & 63);                                                         \
-        if (!(done_mask.load(std::memory_order_relaxed) & bit_)) {                                                   \
-            (void)hipFuncSetAttribute((const void *)linear_fwd_b3_kernel<6, LN_, NT_, 8, 1, GRP_>,                   \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);                \
-            done_mask.fetch_or(bit_, std::memory_order_relaxed);                                                     \
-        }                                                                                                            \
-        hipLaunchKernelGGL((linear_fwd_b3_kernel<6, LN_, NT_, 8, 1, GRP_>), dim3((unsigned)nblk3), dim3(512), lds_b3, st, a); \
-    } while (0)
-#define SO_B3_K192(LN_, NT_)                                                                                          \
-    do {                                                                                                             \
-        if (grouped) SO_B3_K192_G(LN_, NT_, true);                                                                   \
-        else SO_B3_K192_G(LN_, NT_, false);                                                                          \
-    } while (0)
-            if (ln) { if (nt == 3) SO_B3_K192(true, 3); else if (nt == 2) SO_B3_K192(true, 2); else SO_B3_K192(true, 1); }
-            else { if (nt == 3) SO_B3_K192(false, 3); else if (nt == 2) SO_B3_K192(false, 2); else SO_B3_K192(false, 1); }
-#undef SO_B3_K192
-#undef SO_B3_K192_G
+            so_with_const<int, 1, 2, 3>(nt, [&](auto NT) {
+                so_with_const<bool, true, false>(ln, [&](auto LN) {
+                    so_with_const<bool, true, false>(grouped, [&](auto GRP) {
+                        so_launch_lds<linear_fwd_b3_kernel<6, LN, NT, 8, 1, GRP>>(dim3((unsigned)nblk3), dim3(512), lds_b3,
+                                                                                  160 * 1024 - 2048, st, a);
+                    });
+                });
+            });
             continue;
         }
         const bool use_b3 = b3_env && K <= 128 && (T >= 16384 || N >= 384);
@@ -977,47 +932,18 @@ static int so_linear_fwd_launch(const float *x, const float *w, const float *bia
             groups3 = std::min(groups3, (nwt3 + 3) / 4);
             a.groups = (int)groups3;
             const long long nblk3 = deal(groups3, half_tiles ? 16 : 32, 4) * a.ncb;
-#define SO_B3_0(KS_, LN_, NT_, H_, GRP_)                                                                                  \
-    do {                                                                                                             \
-        /* the attribute is per device: set once per (device, instantiation) — the call is a driver round trip of tens of */ \
-        /* microseconds, which at ~45 launches per frame would make the host the bottleneck                                */ \
-        static std::atomic<unsigned long long> done_mask{0};                                                         \
-        int dev_ = 0;                                                                                                \
-        (void)hipGetDevice(&dev_);                                                                                   \
-        const unsigned long long bit_ = 1ull << (dev_ & 63);                                                         \
-        if (lds_b3 > 48 * 1024 && !(done_mask.load(std::memory_order_relaxed) & bit_)) {                             \
-            (void)hipFuncSetAttribute((const void *)linear_fwd_b3_kernel<KS_, LN_, NT_, 4, H_, GRP_>,                \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);                \
-            done_mask.fetch_or(bit_, std::memory_order_relaxed);                                                     \
-        }                                                                                                            \
-        hipLaunchKernelGGL((linear_fwd_b3_kernel<KS_, LN_, NT_, 4, H_, GRP_>), dim3((unsigned)nblk3), dim3(256), lds_b3, st, a); \
-    } while (0)
-#define SO_B3_1(KS_, LN_, NT_)                                                                                        \
-    do {                                                                                                             \
-        if (half_tiles) { if (grouped) SO_B3_0(KS_, LN_, NT_, 1, true); else SO_B3_0(KS_, LN_, NT_, 1, false); }      \
-        else { if (grouped) SO_B3_0(KS_, LN_, NT_, 2, true); else SO_B3_0(KS_, LN_, NT_, 2, false); }                 \
-    } while (0)
-#define SO_B3_2(KS_, LN_)                                                                                             \
-    do {                                                                                                             \
-        if (nt == 3) SO_B3_1(KS_, LN_, 3);                                                                           \
-        else if (nt == 2) SO_B3_1(KS_, LN_, 2);                                                                      \
-        else SO_B3_1(KS_, LN_, 1);                                                                                   \
-    } while (0)
-#define SO_B3_3(KS_)                                                                                                  \
-    do {                                                                                                             \
-        if (ln) SO_B3_2(KS_, true);                                                                                  \
-        else SO_B3_2(KS_, false);                                                                                    \
-    } while (0)
-            switch (K) {
-                case 32: SO_B3_3(1); break;
-                case 64: SO_B3_3(2); break;
-                case 96: SO_B3_3(3); break;
-                default: SO_B3_3(4); break;      // K = 128
-            }
-#undef SO_B3_3
-#undef SO_B3_2
-#undef SO_B3_1
-#undef SO_B3_0
+            so_with_const<int, 32, 64, 96, 128>(K, [&](auto KK) {
+                so_with_const<int, 1, 2, 3>(nt, [&](auto NT) {
+                    so_with_const<bool, true, false>(ln, [&](auto LN) {
+                        so_with_const<bool, true, false>(half_tiles, [&](auto HALF) {
+                            so_with_const<bool, true, false>(grouped, [&](auto GRP) {
+                                so_launch_lds<linear_fwd_b3_kernel<KK / 32, LN, NT, 4, HALF ? 1 : 2, GRP>>(
+                                    dim3((unsigned)nblk3), dim3(256), lds_b3, 160 * 1024 - 2048, st, a);
+                            });
+                        });
+                    });
+                });
+            });
             continue;
         }
         const size_t lds_blk = (size_t)nt * 32 * (K + 4) * sizeof(float);
@@ -1032,43 +958,16 @@ static int so_linear_fwd_launch(const float *x, const float *w, const float *bia
         groups = std::min(groups, (nwt + 3) / 4);
         a.groups = (int)groups;
         const long long nblk = deal(groups, 16, 4) * a.ncb;
-#define SO_L16_1(KQ_, LN_, NT_)                                                                                       \
-    do {                                                                                                             \
-        /* per launch, not once per process: the attribute is per device, and a second GPU in the same process */    \
-        /* would otherwise launch without it (cheap: no driver round trip after the first call on a device)      */    \
-        if (grouped) {                                                                                               \
-            if (lds_blk > 48 * 1024)                                                                                 \
-                (void)hipFuncSetAttribute((const void *)linear_fwd16_kernel<KQ_, LN_, NT_, 4, true>,                 \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_blk);                 \
-            hipLaunchKernelGGL((linear_fwd16_kernel<KQ_, LN_, NT_, 4, true>), dim3((unsigned)nblk), dim3(256), lds_blk, st, a); \
-            break;                                                                                                   \
-        }                                                                                                            \
-        if (lds_blk > 48 * 1024)                                                                                     \
-            (void)hipFuncSetAttribute((const void *)linear_fwd16_kernel<KQ_, LN_, NT_, 4>,                           \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_blk);                     \
-        hipLaunchKernelGGL((linear_fwd16_kernel<KQ_, LN_, NT_, 4>), dim3((unsigned)nblk), dim3(256), lds_blk, st, a); \
-    } while (0)
-#define SO_L16_2(KQ_, LN_)                                                                                            \
-    do {                                                                                                             \
-        if (nt == 3) SO_L16_1(KQ_, LN_, 3);                                                                          \
-        else if (nt == 2) SO_L16_1(KQ_, LN_, 2);                                                                     \
-        else SO_L16_1(KQ_, LN_, 1);                                                                                  \
-    } while (0)
-#define SO_L16_3(KQ_)                                                                                                 \
-    do {                                                                                                             \
-        if (ln) SO_L16_2(KQ_, true);                                                                                 \
-        else SO_L16_2(KQ_, false);                                                                                   \
-    } while (0)
-        switch (K) {
-            case 32: SO_L16_3(8); break;
-            case 64: SO_L16_3(16); break;
-            case 96: SO_L16_3(24); break;
-            case 128: SO_L16_3(32); break;
-            default: SO_L16_3(48); break;
-        }
-#undef SO_L16_3
-#undef SO_L16_2
-#undef SO_L16_1
+        so_with_const<int, 32, 64, 96, 128, 192>(K, [&](auto KK) {
+            so_with_const<int, 1, 2, 3>(nt, [&](auto NT) {
+                so_with_const<bool, true, false>(ln, [&](auto LN) {
+                    so_with_const<bool, true, false>(grouped, [&](auto GRP) {
+                        so_launch_lds<linear_fwd16_kernel<KK / 4, LN, NT, 4, GRP>>(dim3((unsigned)nblk), dim3(256), lds_blk,
+                                                                                   (int)lds_blk, st, a);
+                    });
+                });
+            });
+        });
     }
     return so_launch_status();
 }
@@ -1143,41 +1042,16 @@ static int so_linear_dgrad_launch(const float *dy, const float *w, float *dx, in
     long long groups = std::max<long long>(1, 256 * percu / ncb);
     groups = std::min<long long>(groups, (nwt + 3) / 4);
     a.groups = (int)groups;
-    if (grouped) {      // the row blocks dealt to the groups in proportion to their 32-row tiles (see so_linear_fwd_launch)
-        a.gr.n = G;
+    if (grouped) {      // the row blocks dealt to the groups in proportion to their 32-row tiles, as in so_linear_fwd_launch
         a.gr.w_stride = (long long)N * K;
         a.gr.planes_stride = (long long)3 * K * Npad;
-        long long tiles[8], all = 0, acc = 0;
-        for (int g = 0; g < G; ++g) {
-            a.gr.row_start[g + 1] = row_groups->row_start[g + 1];
-            tiles[g] = (row_groups->row_start[g + 1] - row_groups->row_start[g] + 31) / 32;
-            all += tiles[g];
-        }
-        for (int g = 0; g < G; ++g) {
-            long long want = 0;
-            if (tiles[g] > 0) want = std::max(1LL, std::min((tiles[g] + 3) / 4, (groups * tiles[g] + all / 2) / all));
-            a.gr.rc_start[g + 1] = (int)(acc += want);
-        }
-        for (int i = G + 1; i < 9; ++i) { a.gr.rc_start[i] = (int)acc; a.gr.row_start[i] = T; }
-        groups = acc;
+        a.gr.t = so_deal_row_blocks(*row_groups, groups, 32, 4);
+        groups = a.gr.t.unit_start[G];
     }
     const size_t lds = (size_t)3 * 96 * (96 + 8) * 2;
-#define SO_DGRAD(GRP_)                                                                                                \
-    do {                                                                                                             \
-        static std::atomic<unsigned long long> done_mask{0};                                                         \
-        int dev = 0;                                                                                                 \
-        (void)hipGetDevice(&dev);                                                                                    \
-        const unsigned long long bit = 1ull << (dev & 63);                                                           \
-        if (!(done_mask.load(std::memory_order_relaxed) & bit)) {                                                    \
-            (void)hipFuncSetAttribute((const void *)linear_dgrad_b3_kernel<GRP_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      160 * 1024 - 256);                                                             \
-            done_mask.fetch_or(bit, std::memory_order_relaxed);                                                      \
-        }                                                                                                            \
-        hipLaunchKernelGGL(linear_dgrad_b3_kernel<GRP_>, dim3((unsigned)(groups * ncb)), dim3(256), lds, st, a);      \
-    } while (0)
-    if (grouped) SO_DGRAD(true);
-    else SO_DGRAD(false);
-#undef SO_DGRAD
+    so_with_const<bool, true, false>(grouped, [&](auto GRP) {
+        so_launch_lds<linear_dgrad_b3_kernel<GRP>>(dim3((unsigned)(groups * ncb)), dim3(256), lds, 160 * 1024 - 256, st, a);
+    });
     return so_launch_status();
 }
 

@@ -7,6 +7,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include <atomic>
+#include <type_traits>
 #include "../../include/selfocc_hip.h"
 
 #define SO_DEVFN __device__ __forceinline__
@@ -36,6 +39,35 @@ static inline int so_launch_status() {
     return 0;
 }
 
+// ---- launch dispatch (host) -------------------------------------------------------------
+// A runtime value as a compile-time constant: f(std::integral_constant<T, V>) for the first V of the list that equals v, for the
+// last V when none does (a switch's default).  Nested, with generic lambdas, it turns launch flags into template arguments.
+template <int V> using so_int = std::integral_constant<int, V>;
+template <class T, T V0, T... Vs, class F>
+static inline void so_with_const(T v, F &&f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<T, V0>{});
+    else if (v == V0) f(std::integral_constant<T, V0>{});
+    else so_with_const<T, Vs...>(v, f);
+}
+
+// Launch Kernel(a) with `lds` bytes of dynamic LDS.  Above the 48 KB every kernel may use, its limit is raised to `lds_limit`
+// first — once per (device, instantiation): the attribute is per device, and setting it is a driver round trip of tens of
+// microseconds, which at ~45 launches per frame would make the host the bottleneck.
+template <auto Kernel, class Args>
+static inline void so_launch_lds(dim3 grid, dim3 block, size_t lds, int lds_limit, hipStream_t st, const Args &a) {
+    static std::atomic<unsigned long long> done_mask{0};
+    if (lds > 48 * 1024) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        const unsigned long long bit = 1ull << (dev & 63);
+        if (!(done_mask.load(std::memory_order_relaxed) & bit)) {
+            (void)hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
+            done_mask.fetch_or(bit, std::memory_order_relaxed);
+        }
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, a);
+}
+
 // so_row_groups (by value through the C ABI): 1 .. 8 groups, row_start[0] = 0, non-decreasing, row_start[n] = T.  Host logic only.
 static inline int so_check_row_groups(const so_row_groups &g, long long T, const char *who) {
     SO_REQUIRE(g.n_groups >= 1 && g.n_groups <= 8, "%s: n_groups must be in [1, 8] (got %d)", who, g.n_groups);
@@ -43,9 +75,65 @@ static inline int so_check_row_groups(const so_row_groups &g, long long T, const
     for (int i = 0; i < g.n_groups; ++i)
         SO_REQUIRE(g.row_start[i + 1] >= g.row_start[i], "%s: row_start must be non-decreasing (row_start[%d] = %lld < "
                    "row_start[%d] = %lld)", who, i + 1, (long long)g.row_start[i + 1], i, (long long)g.row_start[i]);
-    SO_REQUIRE(g.row_start[g.n_groups] == T, "%s: row_start[n_groups] = %lld must equal the row count %lld", who,
+    SO_REQUIRE(g.row_start[g.n_groups] == T, "%s: row_start[n_groups] = %lld must equal rows = %lld", who,
                (long long)g.row_start[g.n_groups], T);
     return 0;
+}
+
+// ---- row-group table of a grouped launch ------------------------------------------------
+// Group g owns the launch units (row blocks, chunks, workgroups) unit_start[g] .. unit_start[g + 1] - 1, and those units serve
+// the rows row_start[g] .. row_start[g + 1] - 1: a unit belongs to ONE group.  By value in the kernel arguments and indexed
+// with compile-time constants only, so that it stays in scalar registers (no scratch copy).
+struct so_group_table {
+    int n;
+    int unit_start[9];
+    long long row_start[9];
+};
+
+template <class Unit>
+struct so_group_pick {
+    int g, first, units;             // the group, its first unit, its unit count
+    Unit unit;                       // the unit's index inside the group
+    long long row_lo, row_hi;        // the group's rows
+};
+
+// the group that owns unit `key` — or, BY_INDEX, group `key` < n itself (a per-group reduction: `unit` then means nothing)
+template <bool BY_INDEX = false, class Unit>
+SO_DEVFN so_group_pick<Unit> so_group_of(const so_group_table &t, Unit key) {
+    int g = 0, u0 = 0, u1 = t.unit_start[1];
+    long long r0 = 0, r1 = t.row_start[1];
+#pragma unroll
+    for (int i = 1; i < 8; ++i)
+        if (BY_INDEX ? i == key : (i < t.n && key >= t.unit_start[i])) {
+            g = i; u0 = t.unit_start[i]; u1 = t.unit_start[i + 1]; r0 = t.row_start[i]; r1 = t.row_start[i + 1];
+        }
+    return {g, u0, u1 - u0, key - u0, r0, r1};
+}
+
+// Host: the table of a checked so_row_groups, group g getting units_of(its row count) units; the entries past n repeat the last.
+template <class UnitsOf>
+static inline so_group_table so_build_group_table(const so_row_groups &g, UnitsOf units_of) {
+    so_group_table t = {};
+    t.n = g.n_groups;
+    for (int i = 0; i < t.n; ++i) {
+        t.unit_start[i + 1] = t.unit_start[i] + (int)units_of((long long)(g.row_start[i + 1] - g.row_start[i]));
+        t.row_start[i + 1] = g.row_start[i + 1];
+    }
+    for (int i = t.n + 1; i < 9; ++i) { t.unit_start[i] = t.unit_start[t.n]; t.row_start[i] = t.row_start[t.n]; }
+    return t;
+}
+
+// Host: the `total` row blocks (per column block) an ungrouped tall-Linear launch would use, dealt to the groups in proportion
+// to their row tiles — at least one for a group with rows, never more than it has tiles for its waves, none for an empty group.
+static inline so_group_table so_deal_row_blocks(const so_row_groups &g, long long total, long long tile_rows, long long waves) {
+    auto tiles_of = [&](long long rows) { return (rows + tile_rows - 1) / tile_rows; };
+    long long all = 0;
+    for (int i = 0; i < g.n_groups; ++i) all += tiles_of(g.row_start[i + 1] - g.row_start[i]);
+    return so_build_group_table(g, [&](long long rows) -> long long {
+        const long long tiles = tiles_of(rows);
+        if (tiles == 0) return 0;
+        return std::max(1LL, std::min((tiles + waves - 1) / waves, (total * tiles + all / 2) / all));
+    });
 }
 
 // ---- canonical expf / sigmoid -----------------------------------------------------------

@@ -11,8 +11,10 @@ import torch.nn as nn
 
 from ..registry import MODELS
 from ..dropout import dropout_add
+from .._lib import lib, check, ptr, current_stream
 from ..linear import (linear_wgrad, wgrad_supported, linear_fwd, linear_fwd_supported, linear_fwd_heads, linear_dgrad, dgrad_supported,
-                      linear_fwd_heads_supported)
+                      linear_fwd_heads_supported, row_groups, linear_fwd_grouped, linear_fwd_grouped_supported, linear_dgrad_grouped,
+                      linear_dgrad_grouped_supported, linear_wgrad_grouped, linear_wgrad_grouped_supported)
 from ..msda import (MultiScaleDeformableAttnFunction, msda_fused_inference, MSDAFusedFunction,
                     msda_fused_supported, msda_fused_kernels_built, ValueGradSink)
 
@@ -47,41 +49,57 @@ def constant_init(module, val, bias=0):
         nn.init.constant_(module.bias, bias)
 
 
+GROUPED_LN_CALLS = [0]             # forward calls served by the grouped LayerNorm kernel (tests read this)
+
+
 class _LayerNormFunction(torch.autograd.Function):
-    """LayerNorm over the channel dimension through selfocc_layernorm_fwd / _bwd (csrc/layernorm.hip)."""
+    """LayerNorm over the channel dimension (csrc/layernorm.hip).  ``sizes`` None: one (weight, bias), selfocc_layernorm_fwd /
+    _bwd.  ``sizes`` = host integers (no upload, no synchronisation): one (weight, bias) pair per row group — the planes of a
+    MultiPlaneNorm, concatenated — through selfocc_layernorm_fwd_grouped / _bwd_grouped, one launch for all groups in each
+    direction.  ``wb`` = (weight_1, bias_1, weight_2, bias_2, ...)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps):
-        from .._lib import lib, check, ptr, current_stream
+    def forward(ctx, x, sizes, eps, *wb):
         C = x.shape[-1]
         x2 = x.reshape(-1, C).contiguous().float()
         rows = x2.shape[0]
+        assert sizes is None or sum(sizes) == rows, (sizes, rows)
         y = torch.empty_like(x2)
-        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        need = any(ctx.needs_input_grad)
         mean = torch.empty(rows, device=x.device) if need else None
         rstd = torch.empty(rows, device=x.device) if need else None
-        w, b = weight.contiguous().float(), bias.contiguous().float()
-        check(lib().selfocc_layernorm_fwd(ptr(x2), ptr(w), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, C, float(eps),
-                                          current_stream(x.device)), "selfocc_layernorm_fwd")
+        w, b = stack_rows(wb[0::2]).contiguous().float(), stack_rows(wb[1::2]).contiguous().float()      # (G * C,) = [G][C]
+        args = (ptr(x2), ptr(w), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, C, float(eps))
+        if sizes is None:
+            check(lib().selfocc_layernorm_fwd(*args, current_stream(x.device)), "selfocc_layernorm_fwd")
+        else:
+            check(lib().selfocc_layernorm_fwd_grouped(*args, row_groups(sizes), current_stream(x.device)),
+                  "selfocc_layernorm_fwd_grouped")
+            GROUPED_LN_CALLS[0] += 1
         if need:
-            ctx.save_for_backward(x2, w, mean, rstd)
-        ctx.shape = x.shape
+            # the parameters themselves, not the stacked view: autograd's version check catches in-place updates before backward
+            ctx.save_for_backward(x2, mean, rstd, *wb[0::2])
+        ctx.shape, ctx.sizes = x.shape, sizes
         return y.view(x.shape)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        from .._lib import lib, check, ptr, current_stream
-        x2, w, mean, rstd = ctx.saved_tensors
+        x2, mean, rstd, *ws = ctx.saved_tensors
         rows, C = x2.shape
+        G = len(ws)
+        w = stack_rows(ws).contiguous().float()
         dy2 = dy.reshape(rows, C).contiguous().float()
         dx = torch.empty_like(x2)
-        dg, db = torch.empty_like(w), torch.empty_like(w)
-        nbytes = int(lib().selfocc_layernorm_bwd_workspace(rows, C))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x2.device)
-        check(lib().selfocc_layernorm_bwd(ptr(x2), ptr(w), ptr(mean), ptr(rstd), ptr(dy2), ptr(dx), ptr(dg), ptr(db), rows, C,
-                                          ptr(ws), nbytes, current_stream(x2.device)), "selfocc_layernorm_bwd")
-        return dx.view(ctx.shape), dg, db, None
+        dg, db = x2.new_empty(G, C), x2.new_empty(G, C)
+        groups = () if ctx.sizes is None else (row_groups(ctx.sizes),)
+        entry, workspace = ((lib().selfocc_layernorm_bwd, lib().selfocc_layernorm_bwd_workspace) if ctx.sizes is None else
+                            (lib().selfocc_layernorm_bwd_grouped, lib().selfocc_layernorm_bwd_grouped_workspace))
+        nbytes = int(workspace(rows, C, *groups))
+        wsp = torch.empty(nbytes, dtype=torch.uint8, device=x2.device)
+        check(entry(ptr(x2), ptr(w), ptr(mean), ptr(rstd), ptr(dy2), ptr(dx), ptr(dg), ptr(db), rows, C, *groups, ptr(wsp), nbytes,
+                    current_stream(x2.device)), "selfocc_layernorm_bwd" if ctx.sizes is None else "selfocc_layernorm_bwd_grouped")
+        return (dx.view(ctx.shape), None, None, *[t for g in range(G) for t in (dg[g], db[g])])
 
 
 class FastLayerNorm(nn.LayerNorm):
@@ -92,7 +110,7 @@ class FastLayerNorm(nn.LayerNorm):
         C = x.shape[-1]
         if (x.is_cuda and x.dtype == torch.float32 and self.elementwise_affine and self.bias is not None
                 and len(self.normalized_shape) == 1 and C % 4 == 0 and 4 <= C <= 128 and not torch.is_autocast_enabled()):
-            return _LayerNormFunction.apply(x, self.weight, self.bias, self.eps)
+            return _LayerNormFunction.apply(x, None, self.eps, self.weight, self.bias)
         return super().forward(x)
 
 
@@ -227,42 +245,53 @@ def fused_linear(lin, x, relu=False, residual=None, norm=None, out=None):
     return y
 
 
-def _dgrad(dy, weight):
-    if (FUSED_DGRAD and dy.is_cuda and dy.dtype == torch.float32 and dy.shape[0] >= DGRAD_MIN_ROWS
-            and dgrad_supported(dy.shape[0], weight.shape[0], weight.shape[1])):
-        return linear_dgrad(dy, weight)
-    return dy @ weight
+def _dgrad(dy, weight, sizes=None):
+    """dx = dy W — per row group with ``sizes`` (weight [G][N][K]) — on the HIP route where FUSED_DGRAD and the support query
+    allow it, else matmul"""
+    N, K = dy.shape[1], weight.shape[-1]
+    hip = FUSED_DGRAD and dy.is_cuda and dy.dtype == torch.float32
+    if sizes is None:
+        if hip and dy.shape[0] >= DGRAD_MIN_ROWS and dgrad_supported(dy.shape[0], N, K):
+            return linear_dgrad(dy, weight)
+        return dy @ weight
+    if hip and linear_dgrad_grouped_supported(sizes, N, K):
+        return linear_dgrad_grouped(dy, weight, sizes)
+    return torch.cat([d @ w for d, w in zip(torch.split(dy, sizes), weight.view(len(sizes), N, K))])
 
 
-def _tall_linear_backward(x, weight, dy, has_bias, need_dx=True):
-        """(dx, dW, db) of y = x W^T + b for a row-major dy (shared by _TallLinear and _TallLinearHeads)."""
-        dy = dy.contiguous().to(x.dtype)
-        T = x.shape[0]
-        if (FUSED_WGRAD and dy.is_cuda and dy.dtype == torch.float32 and T > 0
-                and wgrad_supported(T, dy.shape[1], x.shape[1])):
-            # one MFMA pass over dy and x for dW and db (csrc/linear.hip) instead of batched GEMMs + two reductions
-            dw, db = linear_wgrad(dy, x, has_bias)
-            return (_dgrad(dy, weight) if need_dx else None), dw, db
-        G = max(1, min(256, T // 2048))  # ~2 k+ rows per batched GEMM: enough workgroups, small partial-sum tensor
-        R = T // G                       # rows per batched GEMM
-        Tp = R * G
-        dw = dy.new_zeros(dy.shape[1], x.shape[1])
-        db = dy.new_zeros(dy.shape[1])
-        if R > 0:
-            dyb = dy[:Tp].view(G, R, dy.shape[1])
-            dw = torch.bmm(dyb.transpose(1, 2), x[:Tp].view(G, R, x.shape[1]))
-            dw = dw[0] if G == 1 else dw.sum(0)
-            # bias gradient in two stages as well: torch's column reduction of a (1.65 M, N) matrix has only
-            # N outputs to parallelise over (~200 GB/s, 3.1 ms per call in profiles/r1_h_train_iteration.txt;
-            # rocBLAS gemv against a ones vector is worse: 16 ms); (G, R, N).sum(1) has G * N
-            db = dyb.sum(1).sum(0) if T > 300000 else None
-        if db is None:
-            db = dy.sum(0)               # moderate row counts: one column reduction is fine
-        elif Tp < T:
-            db = db + dy[Tp:].sum(0)
-        if Tp < T:
-            dw = dw + dy[Tp:].t() @ x[Tp:]
-        return (_dgrad(dy, weight) if need_dx else None), dw, (db if has_bias else None)
+def _tall_linear_backward(x, weight, dy, has_bias, need_dx=True, y=None, sizes=None):
+    """(dx, dW, db) of y = relu?(x W^T + b) for a row-major dy (shared by _TallLinear, _TallLinearHeads and _GroupedTallLinear).
+    ``y``: the saved output of a ReLU epilogue, which masks dy.  ``sizes``: one weight per row group (weight [G][N][K]) through
+    the grouped kernels -> dW (G, N, K), db (G, N); MultiPlaneFFN.forward_cat has asked their support queries."""
+    dy = dy.contiguous().to(x.dtype)
+    if y is not None:
+        dy = torch.ops.aten.threshold_backward(dy, y, 0)
+    T = x.shape[0]
+    if sizes is not None or (FUSED_WGRAD and dy.is_cuda and dy.dtype == torch.float32 and T > 0
+                             and wgrad_supported(T, dy.shape[1], x.shape[1])):
+        # one MFMA pass over dy and x for dW and db (csrc/linear.hip) instead of batched GEMMs + two reductions
+        dw, db = linear_wgrad(dy, x, has_bias) if sizes is None else linear_wgrad_grouped(dy, x, sizes, has_bias)
+        return (_dgrad(dy, weight, sizes) if need_dx else None), dw, db
+    G = max(1, min(256, T // 2048))  # ~2 k+ rows per batched GEMM: enough workgroups, small partial-sum tensor
+    R = T // G                       # rows per batched GEMM
+    Tp = R * G
+    dw = dy.new_zeros(dy.shape[1], x.shape[1])
+    db = dy.new_zeros(dy.shape[1])
+    if R > 0:
+        dyb = dy[:Tp].view(G, R, dy.shape[1])
+        dw = torch.bmm(dyb.transpose(1, 2), x[:Tp].view(G, R, x.shape[1]))
+        dw = dw[0] if G == 1 else dw.sum(0)
+        # bias gradient in two stages as well: torch's column reduction of a (1.65 M, N) matrix has only
+        # N outputs to parallelise over (~200 GB/s, 3.1 ms per call in profiles/r1_h_train_iteration.txt;
+        # rocBLAS gemv against a ones vector is worse: 16 ms); (G, R, N).sum(1) has G * N
+        db = dyb.sum(1).sum(0) if T > 300000 else None
+    if db is None:
+        db = dy.sum(0)               # moderate row counts: one column reduction is fine
+    elif Tp < T:
+        db = db + dy[Tp:].sum(0)
+    if Tp < T:
+        dw = dw + dy[Tp:].t() @ x[Tp:]
+    return (_dgrad(dy, weight) if need_dx else None), dw, (db if has_bias else None)
 
 
 def stacked_view(params):
@@ -343,9 +372,7 @@ class _TallLinear(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type='cuda')
     def backward(ctx, dy):
         x, y, *ws = ctx.saved_tensors
-        if y is not None:
-            dy = torch.ops.aten.threshold_backward(dy.contiguous().to(y.dtype), y, 0)
-        dx, dw, db = _tall_linear_backward(x, stack_rows(ws), dy, ctx.has_bias, ctx.needs_input_grad[0])
+        dx, dw, db = _tall_linear_backward(x, stack_rows(ws), dy, ctx.has_bias, ctx.needs_input_grad[0], y)
         return (dx, None, *_split_rows(dw, db, [w.shape[0] for w in ws]))
 
 
@@ -487,13 +514,6 @@ class FFN(BaseModule):
 # MultiPlaneNorm on the concatenated planes as ONE selfocc_layernorm_*_grouped launch per direction (csrc/layernorm.hip);
 # env SELFOCC_GROUPED_LN=0: one FastLayerNorm call per plane + a cat (A/B)
 GROUPED_LN = os.environ.get('SELFOCC_GROUPED_LN', '1') == '1'
-GROUPED_LN_CALLS = [0]             # forward calls served by the grouped kernel (tests read this)
-
-
-def _row_groups(sizes):
-    from ..linear import row_groups
-    return row_groups(sizes)
-
 
 # MultiPlaneFFN on the concatenated planes through the grouped tall-Linear kernels (selfocc_linear_{fwd,dgrad,wgrad}_grouped): one
 # launch per Linear and direction for the three planes; env SELFOCC_GROUPED_FFN=0: one FFN call per plane (A/B)
@@ -509,7 +529,6 @@ class _GroupedTallLinear(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
     def forward(ctx, x, sizes, relu, *wb):
-        from ..linear import linear_fwd_grouped
         w, b = stack_rows(wb[0::2]), stack_rows(wb[1::2])
         y = linear_fwd_grouped(x, sizes, w, b, relu=relu)
         # the parameters themselves, not the stacked view: autograd's version check catches in-place updates before backward
@@ -520,66 +539,9 @@ class _GroupedTallLinear(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_bwd(device_type='cuda')
     def backward(ctx, dy):
-        from ..linear import linear_dgrad_grouped, linear_dgrad_grouped_supported, linear_wgrad_grouped
         x, y, *ws = ctx.saved_tensors
-        G, (N, K) = len(ws), ws[0].shape
-        dy = dy.contiguous().to(x.dtype)
-        if y is not None:
-            dy = torch.ops.aten.threshold_backward(dy, y, 0)
-        dw, db = linear_wgrad_grouped(dy, x, ctx.sizes)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if FUSED_DGRAD and linear_dgrad_grouped_supported(ctx.sizes, N, K):
-                dx = linear_dgrad_grouped(dy, stack_rows(ws), ctx.sizes)
-            else:
-                dx = torch.cat([d @ w for d, w in zip(torch.split(dy, ctx.sizes), ws)])
-        return (dx, None, None, *[t for g in range(G) for t in (dw[g], db[g])])
-
-
-class _GroupedLayerNormFunction(torch.autograd.Function):
-    """LayerNorm of (rows, C) with one (weight, bias) pair per row group — the planes of a MultiPlaneNorm, concatenated —
-    through selfocc_layernorm_fwd_grouped / _bwd_grouped: one launch for all groups in each direction.  ``sizes`` are host
-    integers (the plane sizes): no upload, no synchronisation.  ``wb`` = (weight_1, bias_1, weight_2, bias_2, ...)."""
-
-    @staticmethod
-    def forward(ctx, x, sizes, eps, *wb):
-        from .._lib import lib, check, ptr, current_stream
-        C = x.shape[-1]
-        x2 = x.reshape(-1, C).contiguous().float()
-        rows = x2.shape[0]
-        assert sum(sizes) == rows, (sizes, rows)
-        y = torch.empty_like(x2)
-        need = any(ctx.needs_input_grad)
-        mean = torch.empty(rows, device=x.device) if need else None
-        rstd = torch.empty(rows, device=x.device) if need else None
-        w, b = stack_rows(wb[0::2]), stack_rows(wb[1::2])          # (G * C,) = [G][C]
-        check(lib().selfocc_layernorm_fwd_grouped(ptr(x2), ptr(w), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, C, float(eps),
-                                                  _row_groups(sizes), current_stream(x.device)), "selfocc_layernorm_fwd_grouped")
-        if need:
-            # the parameters themselves, not the stacked view: autograd's version check catches in-place updates before backward
-            ctx.save_for_backward(x2, mean, rstd, *wb[0::2])
-        ctx.shape, ctx.sizes = x.shape, list(sizes)
-        GROUPED_LN_CALLS[0] += 1
-        return y.view(x.shape)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        from .._lib import lib, check, ptr, current_stream
-        x2, mean, rstd, *ws = ctx.saved_tensors
-        rows, C = x2.shape
-        G = len(ws)
-        w = stack_rows(ws)
-        dy2 = dy.reshape(rows, C).contiguous().float()
-        dx = torch.empty_like(x2)
-        dg, db = x2.new_empty(G, C), x2.new_empty(G, C)
-        groups = _row_groups(ctx.sizes)
-        nbytes = int(lib().selfocc_layernorm_bwd_grouped_workspace(rows, C, groups))
-        wsp = torch.empty(nbytes, dtype=torch.uint8, device=x2.device)
-        check(lib().selfocc_layernorm_bwd_grouped(ptr(x2), ptr(w), ptr(mean), ptr(rstd), ptr(dy2), ptr(dx), ptr(dg), ptr(db), rows,
-                                                  C, groups, ptr(wsp), nbytes, current_stream(x2.device)),
-              "selfocc_layernorm_bwd_grouped")
-        return (dx.view(ctx.shape), None, None, *[t for g in range(G) for t in (dg[g], db[g])])
+        dx, dw, db = _tall_linear_backward(x, stack_rows(ws), dy, True, ctx.needs_input_grad[0], y, ctx.sizes)
+        return (dx, None, None, *[t for g in range(len(ws)) for t in (dw[g], db[g])])
 
 
 @MODELS.register_module()
@@ -610,7 +572,7 @@ class MultiPlaneNorm(BaseModule):
         assert len(sizes) == len(self.norms) and sum(sizes) == x.shape[1], (sizes, tuple(x.shape))
         if x.shape[0] == 1 and self._grouped_ok(x):
             wb = [t for n in self.norms for t in (n.weight, n.bias)]
-            return _GroupedLayerNormFunction.apply(x, list(sizes), self.norms[0].eps, *wb)
+            return _LayerNormFunction.apply(x, list(sizes), self.norms[0].eps, *wb)
         return torch.cat([n(p) for n, p in zip(self.norms, torch.split(x, list(sizes), 1))], 1)
 
     def forward(self, tpv):
@@ -641,7 +603,6 @@ class MultiPlaneFFN(BaseModule):
         training = Linear + ReLU, Linear (one _GroupedTallLinear node each), torch dropout on the hidden rows, dropout_add for
         the last dropout + identity; inference = Linear + ReLU, then Linear + identity + the per-plane LayerNorm of ``post_norm``
         in the epilogue: two launches for all planes."""
-        from ..linear import linear_fwd_grouped, linear_fwd_grouped_supported, linear_wgrad_grouped_supported
         f0 = self.ffns[0]
         if not (GROUPED_FFN and FUSED_LINEAR_FWD and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 1
                 and not torch.is_autocast_enabled() and len(sizes) == len(self.ffns) and sum(sizes) == x.shape[1]

@@ -283,6 +283,24 @@ def test_grouped_linear_argument_checks_are_pure_host_logic():
     assert l.selfocc_linear_wgrad_grouped_workspace(78899, 192, 96, _groups(3, [0, 5, 2, 0])) == 0
 
 
+def test_group_table_unit_counts_at_the_group_edges():
+    """the shared table builder through the workspace queries (host logic): one group takes the chunks of the ungrouped plan
+    at row counts around the 64-row minimum of a chunk and at odd sizes; a group's LayerNorm blocks are what an ungrouped launch
+    of its rows takes (an empty group none, 2 048 at the most)"""
+    from selfocc_amd import abi
+    from selfocc_amd._lib import lib
+    l = lib()
+    for T in (1, 63, 64, 65, 2467, 78899):
+        for N, K in ((192, 96), (96, 192), (64, 32)):
+            one = abi.SoRowGroups.from_sizes([T])
+            want = l.selfocc_linear_wgrad_workspace(T, N, K)
+            assert want > 0 and l.selfocc_linear_wgrad_grouped_workspace(T, N, K, one) == want, (T, N, K)
+    per = lambda r: min((r + 7) // 8, 2048)
+    for sizes in ((0, 5, 0), (8, 9, 16385), (66049, 6425, 6425)):
+        got = l.selfocc_layernorm_bwd_grouped_workspace(sum(sizes), 96, abi.SoRowGroups.from_sizes(list(sizes)))
+        assert got == sum(per(r) for r in sizes) * 2 * 96 * 4, (sizes, got)
+
+
 def test_grouped_linear_kernels_need_no_more_scratch_than_their_ungrouped_twins():
     """-Rpass-analysis=kernel-resource-usage: every grouped instantiation (last template argument true) against the ungrouped
     one with the same other arguments"""
