@@ -105,7 +105,12 @@ enum {
 };
 enum { SO_SAMPLE_AT_START = 0, SO_SAMPLE_AT_MID = 1 };
 enum { SO_BKGD_NONE = 0, SO_BKGD_CONST = 1, SO_BKGD_PER_RAY = 2 };
-enum { SO_JITTER_NONE = 0, SO_JITTER_SINGLE = 1, SO_JITTER_PER_BIN = 2 };
+enum {
+    SO_JITTER_NONE = 0, SO_JITTER_SINGLE = 1, SO_JITTER_PER_BIN = 2,
+    SO_JITTER_EDGES = 3 /* no uniform bins: t_rand is (n_rays, n_samples + 1) NORMALISED edges b in [0, 1], non-decreasing along
+                           a ray, and edge j lies at b * tfar + (1 - b) * tnear (selfocc_render_upsample writes such rows).
+                           Always the canonical march; the edges are constants (no gradient). */
+};
 enum {
     SO_FLAG_DEPTH_DIV_NORM = 1, /* depth /= ||K^-1 (u,v,1)|| (z-depth, as the fork does) */
     SO_FLAG_CLAMP_RGB = 2,      /* eval: clamp rgb to [0,1]                              */
@@ -190,7 +195,8 @@ typedef struct so_render_args {
     int32_t n_samples;
     int32_t sample_pos;     /* SO_SAMPLE_AT_* : where the field is evaluated            */
     int32_t jitter_mode;    /* SO_JITTER_*                                              */
-    const float *t_rand;    /* (n_rays) or (n_rays, n_samples + 1) uniform [0,1)        */
+    const float *t_rand;    /* (n_rays) or (n_rays, n_samples + 1) uniform [0,1);
+                               SO_JITTER_EDGES: the (n_rays, n_samples + 1) edges        */
     /* --- NeuS -------------------------------------------------------------------- */
     float inv_s;
     /* --- compositing ------------------------------------------------------------- */
@@ -290,6 +296,41 @@ typedef struct so_render_median_args {
     int32_t *median_index;     /* (n_rays) or NULL */
 } so_render_median_args;
 int selfocc_render_median(const so_render_median_args *args, void *stream);
+
+/* NeuS hierarchical up-sampling: the coarse-to-fine sampler of NeuS (a declared restatement of upstream sdfstudio's NeuSSampler
+ * + nerfstudio's PDFSampler).  Per ray, with the collider's tnear / tfar, S0 = fwd.n_samples,
+ * M = n_importance, K = n_steps, m = M / K (integer division), one number r_k in [0, 1) per step (0.5 when u_rand is NULL):
+ *   state: normalised edges b[0..n], non-decreasing, n samples.  Start: n = S0, b[j] = the uniform bin edge j with the
+ *          SO_JITTER_SINGLE / SO_JITTER_PER_BIN jitter when asked (what the march itself uses).  Metric position of an edge,
+ *          everywhere: t = b * tfar + (1 - b) * tnear.
+ *   for k = 0 .. K - 1, s = base_variance * 2^k:
+ *     1. f_i = trilinear SDF at o + d * t_i, i = 0 .. n - 1 (always the sample start, whatever sample_pos says)
+ *     2. for i = 0 .. n - 2:  delta_i = t_{i+1} - t_i,  mid = (f_i + f_{i+1}) * 0.5,  cos_i = (f_{i+1} - f_i) / (delta_i + 1e-5),
+ *        c_i = clip(min(cos_{i-1}, cos_i), -1e3, 0) with cos_{-1} = 0,  e- = mid - c_i delta_i * 0.5,  e+ = mid + c_i delta_i * 0.5,
+ *        alpha_i = (sigmoid(e- s) - sigmoid(e+ s) + 1e-5) / (sigmoid(e- s) + 1e-5)
+ *     3. w_i = alpha_i prod_{j<i} (1 - alpha_j + 1e-7) for i <= n - 2,  w_{n-1} = 0
+ *     4. w_i += 1e-5;  W = sum w;  pad = max(0, 1e-5 - W);  w_i += pad / n;  W += pad;
+ *        cdf_0 = 0,  cdf_{i+1} = min(1, cdf_i + w_i / W)
+ *     5. u_j = lin_j + r_k / (m + 1), j = 0 .. m, lin = linspace(0, 1 - 1 / (m + 1), m + 1) in float32;
+ *        idx = number of cdf entries <= u_j;  lo = clamp(idx - 1, 0, n),  hi = clamp(idx, 0, n);
+ *        q = (u_j - cdf_lo) / (cdf_hi - cdf_lo), 0 when the denominator is 0, clipped to [0, 1];  p_j = b_lo + q (b_hi - b_lo)
+ *     6. the new edges are sort(b[0..n-1] U p[0..m-1]) followed by max(b[n], p[m]);  n <- n + m
+ * Result: S_tot = S0 + K m samples, S_tot + 1 edges per ray in `edges`, to be marched with SO_JITTER_EDGES.  With M = 0, K = 0
+ * or m = 0 no step runs and `edges` receives the S0 + 1 start edges.  One wave per ray, no atomics: the same inputs give the
+ * same bits on every launch.  Of `fwd`, the mapping, sdf_vol, the ray fields, aabb, near_plane, n_samples, jitter_mode and
+ * t_rand are read; feature fields, inv_s and outputs are ignored.  Refused by name: edges NULL, n_samples < 1, negative
+ * n_importance / n_steps, n_steps > 8, S_tot > 256 (what the per-sample forward and the backward take), base_variance not
+ * positive, SO_JITTER_EDGES as the start, and what selfocc_render_fwd refuses among the fields read.  n_rays == 0 succeeds
+ * without a launch.  A new entry point: SELFOCC_ABI_VERSION is unchanged. */
+typedef struct so_render_upsample_args {
+    so_render_args fwd;        /* inputs as for selfocc_render_fwd; outputs and feature fields ignored */
+    int32_t n_importance;      /* M */
+    int32_t n_steps;           /* K */
+    float base_variance;       /* inv_s of step 0; doubled every step */
+    const float *u_rand;       /* (n_steps, n_rays) uniform [0, 1), or NULL: 0.5 */
+    float *edges;              /* (n_rays, S_tot + 1) normalised edges */
+} so_render_upsample_args;
+int selfocc_render_upsample(const so_render_upsample_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Multi-scale deformable attention.  Replaces mmcv==2.0.1

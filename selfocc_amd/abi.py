@@ -12,7 +12,7 @@ ABI_VERSION = 35
 RAYS_EXPLICIT, RAYS_PIXEL_GRID = 0, 1
 SAMPLE_AT_START, SAMPLE_AT_MID = 0, 1
 BKGD_NONE, BKGD_CONST, BKGD_PER_RAY = 0, 1, 2
-JITTER_NONE, JITTER_SINGLE, JITTER_PER_BIN = 0, 1, 2
+JITTER_NONE, JITTER_SINGLE, JITTER_PER_BIN, JITTER_EDGES = 0, 1, 2, 3
 FLAG_DEPTH_DIV_NORM, FLAG_CLAMP_RGB, FLAG_EXACT, FLAG_NO_SKIP, FLAG_NO_FACE_SAFE, FLAG_NO_AHEAD, FLAG_RAY_PER_LANE = 1, 2, 4, 8, 16, 32, 64
 MSDA_PLAIN, MSDA_FUSED, MSDA_CROSS = 0, 1, 2
 # selfocc_msda_plan: indices into its SO_MSDA_PLAN_INTS outputs
@@ -78,6 +78,11 @@ class SoRenderBwdArgs(C.Structure):
 
 class SoRenderMedianArgs(C.Structure):
     _fields_ = [("fwd", SoRenderArgs), ("median_depth", _p), ("median_index", _p)]
+
+
+class SoRenderUpsampleArgs(C.Structure):
+    _fields_ = [("fwd", SoRenderArgs), ("n_importance", _i), ("n_steps", _i), ("base_variance", _f),
+                ("u_rand", _p), ("edges", _p)]
 
 
 class SoMsdaArgs(C.Structure):
@@ -207,6 +212,7 @@ SYMBOLS = {
     "selfocc_render_bwd": (C.c_int, [C.POINTER(SoRenderBwdArgs), _p]),
     "selfocc_render_bwd_ws_bytes": (C.c_size_t, [C.POINTER(SoRenderBwdArgs)]),
     "selfocc_render_median": (C.c_int, [C.POINTER(SoRenderMedianArgs), _p]),
+    "selfocc_render_upsample": (C.c_int, [C.POINTER(SoRenderUpsampleArgs), _p]),
     "selfocc_msda_fwd": (C.c_int, [C.POINTER(SoMsdaArgs), _p]),
     "selfocc_msda_bwd": (C.c_int, [C.POINTER(SoMsdaArgs), _p]),
     "selfocc_msda_ws_bytes": (C.c_size_t, [C.POINTER(SoMsdaArgs)]),

@@ -1,5 +1,5 @@
 // ray_device.h — the ray geometry of the render kernels: ONE definition for render_fwd.hip (per-ray march), render_train.hip
-// (sample-parallel forward) and render_bwd.hip (backward + its counting pre-pass).
+// (sample-parallel forward), render_bwd.hip (backward + its counting pre-pass), render_median.hip and render_upsample.hip.
 //
 // Ray construction, the box collider and the bin edges decide which voxel cell a sample lands in, so the three translation
 // units must agree on them operation for operation, and with oracle/oracle_render.c (-ffp-contract=off, every
@@ -62,9 +62,11 @@ SO_DEVFN float so_bin(int j, int n) {
     return (j < (n + 1) / 2) ? step * (float)j : fmaf(-step, (float)(n - j), 1.0f);
 }
 
-// UniformSampler bin edge j of a ray (spaced sampler, train_stratified jitter optional)
-SO_DEVFN float so_edge(const so_render_args &a, int ray, int j, float tnear, float tfar) {
+// normalised bin edge j of a ray, in [0, 1]: UniformSampler (spaced sampler, train_stratified jitter optional), or, with
+// SO_JITTER_EDGES, the caller's own edge read back from t_rand (n_rays, n_samples + 1) (render_upsample.hip writes such rows)
+SO_DEVFN float so_edge_unit(const so_render_args &a, int ray, int j) {
     const int n = a.n_samples;
+    if (a.jitter_mode == SO_JITTER_EDGES) return a.t_rand[(size_t)ray * (n + 1) + j];
     float b = so_bin(j, n);
     if (a.jitter_mode != SO_JITTER_NONE) {
         const float lo = (j == 0) ? b : (b + so_bin(j - 1, n)) / 2.0f;
@@ -72,7 +74,15 @@ SO_DEVFN float so_edge(const so_render_args &a, int ray, int j, float tnear, flo
         const float tr = (a.jitter_mode == SO_JITTER_SINGLE) ? a.t_rand[ray] : a.t_rand[(size_t)ray * (n + 1) + j];
         b = lo + (hi - lo) * tr;
     }
-    return b * tfar + (1.0f - b) * tnear;
+    return b;
+}
+
+// metric position of a normalised edge, everywhere
+SO_DEVFN float so_edge_metric(float b, float tnear, float tfar) { return b * tfar + (1.0f - b) * tnear; }
+
+// bin edge j of a ray in metres along it
+SO_DEVFN float so_edge(const so_render_args &a, int ray, int j, float tnear, float tfar) {
+    return so_edge_metric(so_edge_unit(a, ray, j), tnear, tfar);
 }
 
 // 64-lane butterfly sums, every lane gets the total.  Two orders, named for the lane distances they pair: float addition is

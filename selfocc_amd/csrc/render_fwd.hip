@@ -1613,7 +1613,8 @@ int so_validate_render(const so_render_args &a) {
     } else {
         SO_REQUIRE(false, "bad ray_mode %d", a.ray_mode);
     }
-    SO_REQUIRE(a.jitter_mode == SO_JITTER_NONE || a.t_rand, "jitter requested but t_rand is NULL");
+    SO_REQUIRE(a.jitter_mode >= SO_JITTER_NONE && a.jitter_mode <= SO_JITTER_EDGES, "bad jitter_mode %d", (int)a.jitter_mode);
+    SO_REQUIRE(a.jitter_mode == SO_JITTER_NONE || a.t_rand, "jitter or explicit edges requested but t_rand is NULL");
     SO_REQUIRE(a.bkgd_mode != SO_BKGD_PER_RAY || a.bkgd_rays, "per-ray background but bkgd_rays is NULL");
     SO_REQUIRE(a.sample_pos == SO_SAMPLE_AT_START || a.sample_pos == SO_SAMPLE_AT_MID, "bad sample_pos");
     return 0;

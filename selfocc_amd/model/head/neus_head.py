@@ -29,7 +29,8 @@ from ...mapping import GridMeterMapping
 from ...occ import field_query, field_query_autograd, uniform_lattice
 from ...field import field_volume, field_volume_supported, field_volume_train_supported, FieldVolumeFunction
 from ...registry import HEADS
-from ...render import SDFVolume, RaySet, RenderConfig, render_rays, render_rays_autograd, render_median_depth
+from ...render import (SDFVolume, RaySet, RenderConfig, render_rays, render_rays_autograd, render_median_depth, upsample_edges,
+                       upsample_plan)
 from ..bricks import BaseModule, _TallLinear
 
 
@@ -358,8 +359,7 @@ class NeuSHead(BaseModule):
                  sample_pos='start', single_jitter=True, feat_dtype=torch.float32, exact_render=False,
                  ray_shard=False, render_normal=False, return_median_depth=False, **kwargs):
         super().__init__(init_cfg)
-        for name, on in dict(num_samples_importance=num_samples_importance > 0, num_up_sample_steps=num_up_sample_steps > 0,
-                             use_numerical_gradients=use_numerical_gradients, estimate_flow=estimate_flow,
+        for name, on in dict(use_numerical_gradients=use_numerical_gradients, estimate_flow=estimate_flow,
                              anneal_aabb=anneal_aabb, disp_sampler=disp_sampler, using_2d_img_feats=using_2d_img_feats,
                              beta_hand_tune=beta_hand_tune, return_surface_sdf=return_surface_sdf).items():
             if on:
@@ -376,6 +376,18 @@ class NeuSHead(BaseModule):
                          not beta_hand_tune, return_sem, feat_dtype)
         self.model = _NeuSModel(field)
         self.num_samples, self.near_plane = num_samples, near_plane
+        # NeuS hierarchical up-sampling (render.upsample_edges): num_up_sample_steps rounds of
+        # num_samples_importance // num_up_sample_steps new samples each, on top of the num_samples uniform ones
+        try:
+            self.up_m, self.up_steps, self.total_samples = upsample_plan(num_samples, num_samples_importance, num_up_sample_steps)
+        except ValueError as e:
+            raise NotImplementedError(f"NeuSHead: {e}") from None
+        if self.up_steps > 0 and ray_shard:
+            raise NotImplementedError("NeuSHead(ray_shard=True) together with up-sampling (num_samples_importance > 0, "
+                                      "num_up_sample_steps > 0) is not built")
+        self.num_samples_importance, self.num_up_sample_steps = num_samples_importance, num_up_sample_steps
+        self.base_variance = float(base_variance)
+        self.up_edge_bytes = 256 << 20      # render(): the frame is up-sampled in row-block chunks whose edge buffer stays below this
         self.render_bkgd = render_bkgd
         self.print_freq, self.resolution, self.aabb = print_freq, resolution, roi_aabb
         self.return_uniform_sdf, self.return_max_depth = return_uniform_sdf, return_max_depth
@@ -464,6 +476,9 @@ class NeuSHead(BaseModule):
             return False
         if not rays.pixel_grid:
             raise NotImplementedError("ray_shard needs a lattice ray mode ('fixed' / 'cellular')")
+        if self.up_steps > 0:
+            raise NotImplementedError("NeuSHead: ray sharding together with up-sampling (num_samples_importance > 0, "
+                                      "num_up_sample_steps > 0) is not built")
         return True
 
     @staticmethod
@@ -577,6 +592,8 @@ class NeuSHead(BaseModule):
             if want_median:
                 loc['median_depth'] = render_median_depth(vol, rays, cfg)['median_depth']
             out = {k: sdist.gather_rays(v, full).reshape(-1, *v.shape[1:]) for k, v in loc.items()}
+        elif self.up_steps > 0:
+            out = self._render_upsampled(vol, rays, cfg, want_median)
         else:
             bk = torch.rand(rays.n_rays, 3, device=device) if cfg.bkgd_mode == abi.BKGD_PER_RAY else None
             out = render_rays(vol, rays, cfg, bkgd_rays=bk)
@@ -599,6 +616,43 @@ class NeuSHead(BaseModule):
             outputs['sem'] = [out['sem'].reshape(*shp, -1)]
         return outputs
 
+    def _upsample(self, vol, rays, cfg, t_rand=None):
+        """the (N, S_tot + 1) edges of this head's up-sampling for ``rays``: the r_k are drawn in training, 0.5 otherwise"""
+        u = torch.rand(self.num_up_sample_steps, rays.n_rays, device=vol.sdf.device) if self.training else None
+        return upsample_edges(vol, rays, cfg, self.num_samples_importance, self.num_up_sample_steps, self.base_variance,
+                              t_rand=t_rand, u_rand=u)
+
+    @staticmethod
+    def _row_chunks(rays, n_chunks):
+        """``rays`` cut into ``n_chunks`` row blocks (dist.shard_rays) and the function that puts per-ray results of the
+        chunks back into frame order"""
+        from ... import dist as sdist
+        n_chunks = max(1, min(n_chunks, rays.ny if rays.pixel_grid else max(rays.n_rays, 1)))
+        subs = [sdist.shard_rays(rays, k, n_chunks) for k in range(n_chunks)]
+
+        def stitch(parts):
+            if rays.pixel_grid and n_chunks > 1:      # chunks are row blocks of every camera: back to (cam, row, col) order
+                n_cams = rays.img2lidar.shape[0]
+                return torch.cat([p.reshape(n_cams, s.ny, rays.nx, *p.shape[1:]) for p, s in zip(parts, subs)], 1) \
+                    .reshape(-1, *parts[0].shape[1:])
+            return torch.cat(parts, 0)
+        return subs, stitch
+
+    def _render_upsampled(self, vol, rays, cfg, want_median):
+        """render() with up-sampling: edges + march per row-block chunk, so that the edge buffer (4 (S_tot + 1) bytes per
+        ray: 1.1 GB for the nuscenes_depth frame at 129 edges) stays below ``up_edge_bytes``"""
+        n_chunks = -(-(rays.n_rays * (self.total_samples + 1) * 4) // self.up_edge_bytes)
+        subs, stitch = self._row_chunks(rays, n_chunks)
+        parts = []
+        for sub in subs:
+            edges = self._upsample(vol, sub, cfg)
+            bk = torch.rand(sub.n_rays, 3, device=vol.sdf.device) if cfg.bkgd_mode == abi.BKGD_PER_RAY else None
+            o = render_rays(vol, sub, cfg, bkgd_rays=bk, edges=edges)
+            if want_median:
+                o['median_depth'] = render_median_depth(vol, sub, cfg, edges=edges)['median_depth']
+            parts.append(o)
+        return {k: stitch([p[k] for p in parts]) for k in parts[0]}
+
     def _normal_vis(self, vol, rays, cfg, chunk_rays=90000):
         """sdfstudio's `normal_vis` of the reference's render dicts (neus_head.py:379, 414, 463): the weighted sum of
         the unit SDF gradients along each ray, mapped to [0, 1].  Per-sample weights / gradients come from the
@@ -613,7 +667,8 @@ class NeuSHead(BaseModule):
         parts = []
         for k in range(n_chunks):
             sub = sdist.shard_rays(rays, k, n_chunks)
-            o = render_rays(vol, sub, cfg, per_sample=True, want_grad_samples=True)
+            o = render_rays(vol, sub, cfg, per_sample=True, want_grad_samples=True,
+                            edges=self._upsample(vol, sub, cfg) if self.up_steps > 0 else None)
             g = o['grad']
             nrm = g / g.norm(dim=-1, keepdim=True).clamp_min(1e-12)          # F.normalize(p=2, eps=1e-12)
             parts.append((o['weights'].unsqueeze(-1) * nrm).sum(1))
@@ -647,17 +702,21 @@ class NeuSHead(BaseModule):
         t_rand = None
         if cfg.jitter_mode != abi.JITTER_NONE:
             t_rand = torch.rand((N,) if cfg.jitter_mode == abi.JITTER_SINGLE else (N, S + 1), device=device)
+        edges = None
+        if self.up_steps > 0:
+            # the jitter goes into the start edges; from here on the S_tot samples between the edges are what is rendered
+            edges, t_rand, S = self._upsample(vol.detached(), rays, cfg, t_rand), None, self.total_samples
         bk = torch.rand(N, 3, device=device) if cfg.bkgd_mode == abi.BKGD_PER_RAY else None
         inv_s = field.inv_s()
         if full_rays is not None:
             inv_s = sdist.replicate_grad_sum(inv_s)       # d/d(variance) is a sum over all rays as well
-        out = render_rays_autograd(vol, inv_s, rays, cfg, want_grad_samples=True, t_rand=t_rand, bkgd_rays=bk)
+        out = render_rays_autograd(vol, inv_s, rays, cfg, want_grad_samples=True, t_rand=t_rand, bkgd_rays=bk, edges=edges)
         self.last_inv_s = inv_s.detach()          # device tensor (the reference logs output['inv_s'], neus_head.py:631-633)
         median = None
         if self.return_median_depth:
             # the same rays, jitter and inv_s as the render above; detached (an index into ts carries no gradient)
             mcfg = dataclasses.replace(cfg, inv_s_dev=inv_s.detach().reshape(1).float().contiguous())
-            median = render_median_depth(vol.detached(), rays, mcfg, t_rand=t_rand)['median_depth']
+            median = render_median_depth(vol.detached(), rays, mcfg, t_rand=t_rand, edges=edges)['median_depth']
             if full_rays is not None:
                 median = sdist.gather_rays(median, full_rays)
         shard = None

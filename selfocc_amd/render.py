@@ -5,6 +5,7 @@ replaces what the reference obtains from the sdfstudio fork's
 ``NeuSCustomModel.__call__(RayBundle)`` (model/head/neus_head/neus_head.py:353,394,531).
 Tensors are only device-memory handles here: the arithmetic is in csrc/render_*.hip.
 """
+import dataclasses
 import os
 from dataclasses import dataclass, field
 from typing import Optional
@@ -194,7 +195,7 @@ def marshal_render_args(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, per_
     a.sample_pos = cfg.sample_pos
     a.jitter_mode = cfg.jitter_mode
     if cfg.jitter_mode != abi.JITTER_NONE:
-        exp = (N,) if cfg.jitter_mode == abi.JITTER_SINGLE else (N, S + 1)
+        exp = (N,) if cfg.jitter_mode == abi.JITTER_SINGLE else (N, S + 1)       # JITTER_EDGES: the (N, S + 1) edges themselves
         assert t_rand is not None and tuple(t_rand.shape) == exp, f"t_rand must be {exp}"
         a.t_rand = ptr(_c(t_rand))
     a.inv_s = float(cfg.inv_s)
@@ -236,13 +237,26 @@ def marshal_render_args(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, per_
     return a, out, keep
 
 
+def _with_edges(cfg, edges, t_rand, n_rays):
+    """``edges=`` of the render calls: (N, S + 1) normalised, non-decreasing edges per ray (``upsample_edges``) replace the
+    uniform bins.  They set the mode and the sample count and travel in the ``t_rand`` slot; they are constants (upstream
+    samples them under no_grad)."""
+    if edges is None:
+        return cfg, t_rand
+    assert t_rand is None, "edges= replaces the uniform bins: t_rand does not apply (the jitter is in the edges)"
+    assert edges.dim() == 2 and edges.shape[0] == n_rays and edges.shape[1] >= 2, \
+        f"edges must be (n_rays = {n_rays}, n_samples + 1), got {tuple(edges.shape)}"
+    return dataclasses.replace(cfg, n_samples=edges.shape[1] - 1, jitter_mode=abi.JITTER_EDGES), edges.detach()
+
+
 def render_rays(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, per_sample=False,
-                want_grad_samples=False, t_rand=None, bkgd_rays=None, outputs=None):
+                want_grad_samples=False, t_rand=None, bkgd_rays=None, outputs=None, edges=None):
     """Forward render on the GPU (no autograd).  Returns a dict of per-ray tensors
     (depth, acc, rgb, sem, max_depth, nears, fars) and, with ``per_sample``, the
-    (N, S) tensors weights / ts / deltas (/ sdf / grad)."""
+    (N, S) tensors weights / ts / deltas (/ sdf / grad).  ``edges``: see ``_with_edges`` (S = edges.shape[1] - 1)."""
     if not vol.sdf.is_cuda:
         raise RuntimeError("selfocc_amd.render_rays needs CUDA(HIP) tensors: there is no CPU fallback")
+    cfg, t_rand = _with_edges(cfg, edges, t_rand, rays.n_rays)
     a, out, _keep = marshal_render_args(vol, rays, cfg, per_sample=per_sample,
                                         want_grad_samples=want_grad_samples, t_rand=t_rand,
                                         bkgd_rays=bkgd_rays, outputs=outputs)
@@ -253,7 +267,7 @@ def render_rays(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, per_sample=F
     return out
 
 
-def render_median_depth(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, t_rand=None, want_index=False):
+def render_median_depth(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, t_rand=None, want_index=False, edges=None):
     """Median depth of every ray in ONE launch (selfocc_render_median, csrc/render_median.hip): nerfstudio's
     DepthRenderer(method="median"), the ``ms_depths_median`` of eval_depth.py.  Equal, bit for bit, to
     ``median_depth_reference`` applied to the ``weights`` / ``ts`` of ``render_rays(vol, rays, cfg, per_sample=True)``,
@@ -262,6 +276,7 @@ def render_median_depth(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, t_ra
     Returns {'median_depth': (N,) float32[, 'median_index': (N,) int32]}."""
     if not vol.sdf.is_cuda:
         raise RuntimeError("selfocc_amd.render_median_depth needs CUDA(HIP) tensors: there is no CPU fallback")
+    cfg, t_rand = _with_edges(cfg, edges, t_rand, rays.n_rays)
     # geometry only: the sampling fields and inv_s of `cfg`; its background, colour and march switches do not apply
     geo = RenderConfig(aabb=cfg.aabb, n_samples=cfg.n_samples, inv_s=cfg.inv_s, inv_s_dev=cfg.inv_s_dev, near_plane=cfg.near_plane,
                        sample_pos=cfg.sample_pos, jitter_mode=cfg.jitter_mode)
@@ -301,6 +316,117 @@ def median_depth_reference(weights, ts):
     if as_tensor:
         return torch.from_numpy(np.ascontiguousarray(depth)), torch.from_numpy(np.ascontiguousarray(j))
     return depth, j
+
+
+UPSAMPLE_MAX_SAMPLES, UPSAMPLE_MAX_STEPS = 256, 8
+
+
+def upsample_plan(n_samples, n_importance, n_steps):
+    """(m, K, S_tot) of NeuS up-sampling: m = n_importance // n_steps new samples in each of K steps, K = 0 (nothing runs,
+    S_tot = n_samples) unless n_importance > 0, n_steps > 0 and m >= 1.  Refuses, by name, what the kernels do not take."""
+    if n_importance < 0 or n_steps < 0:
+        raise ValueError(f"num_samples_importance = {n_importance} / num_up_sample_steps = {n_steps} must be >= 0")
+    if n_steps > UPSAMPLE_MAX_STEPS:
+        raise ValueError(f"num_up_sample_steps = {n_steps} is not built (built: <= {UPSAMPLE_MAX_STEPS})")
+    m = n_importance // n_steps if n_steps > 0 else 0
+    K = n_steps if m >= 1 else 0
+    s_tot = n_samples + K * m
+    if K > 0 and s_tot > UPSAMPLE_MAX_SAMPLES:
+        raise ValueError(f"num_samples + num_up_sample_steps * (num_samples_importance // num_up_sample_steps) = {s_tot} samples "
+                         f"is not built (built: <= {UPSAMPLE_MAX_SAMPLES}, what the per-sample forward and the backward take)")
+    return m, K, s_tot
+
+
+def upsample_edges(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, n_importance, n_steps, base_variance, t_rand=None, u_rand=None):
+    """NeuS hierarchical up-sampling in ONE launch (selfocc_render_upsample, csrc/render_upsample.hip; the definition is in
+    that file's header and in DESIGN.md section 3.20): from the ``cfg.n_samples`` uniform (or jittered: ``cfg.jitter_mode`` /
+    ``t_rand``) bins, ``n_steps`` rounds that each place ``n_importance // n_steps`` new samples by the inverse CDF of
+    fixed-variance NeuS weights (``base_variance * 2^k``).  ``u_rand`` (n_steps, N) uniform [0, 1) or None (0.5).
+    Returns the (N, S_tot + 1) normalised edges for the ``edges=`` argument of the render calls; with nothing to add
+    (``upsample_plan``: K = 0) they are the start edges.  Reads the SDF volume only; no gradient."""
+    if not vol.sdf.is_cuda:
+        raise RuntimeError("selfocc_amd.upsample_edges needs CUDA(HIP) tensors: there is no CPU fallback")
+    m, K, s_tot = upsample_plan(cfg.n_samples, int(n_importance), int(n_steps))
+    if s_tot > UPSAMPLE_MAX_SAMPLES:
+        raise ValueError(f"n_samples = {s_tot} is not built for upsample_edges (built: <= {UPSAMPLE_MAX_SAMPLES})")
+    assert cfg.jitter_mode != abi.JITTER_EDGES, "upsample_edges starts from the uniform bins"
+    geo = RenderConfig(aabb=cfg.aabb, n_samples=cfg.n_samples, near_plane=cfg.near_plane, jitter_mode=cfg.jitter_mode)
+    a, _out, _keep = marshal_render_args(SDFVolume(vol.mapping, vol.sdf.detach()), rays, geo, t_rand=t_rand, inputs_only=True)
+    N, dev = rays.n_rays, vol.sdf.device
+    edges = torch.empty(N, s_tot + 1, dtype=torch.float32, device=dev)
+    if N == 0:
+        return edges
+    ua = abi.SoRenderUpsampleArgs()
+    ua.fwd = a
+    ua.n_importance, ua.n_steps, ua.base_variance = int(n_importance), int(n_steps), float(base_variance)
+    if u_rand is not None and K > 0:
+        assert tuple(u_rand.shape) == (int(n_steps), N), f"u_rand must be {(int(n_steps), N)}"
+        ua.u_rand = ptr(_c(u_rand))
+    ua.edges = ptr(edges)
+    check(lib().selfocc_render_upsample(ua, current_stream(dev)), "selfocc_render_upsample")
+    return edges
+
+
+def uniform_edges_reference(n_samples, jitter_mode=abi.JITTER_NONE, t_rand=None, n_rays=1):
+    """(n_rays, n_samples + 1) float32: the normalised edges the kernels start from (so_edge before its last line), operation
+    for operation: torch.linspace(0, 1, n + 1) in its symmetric-halves form, then the optional stratified jitter."""
+    n = int(n_samples)
+    j = torch.arange(n + 1)
+    step = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(n), dtype=torch.float32)
+    upper = (1.0 - step.double() * (n - j).double()).float()          # fmaf(-step, n - j, 1): the product is exact in float64
+    b = torch.where(j < (n + 1) // 2, step * j.float(), upper)
+    if jitter_mode != abi.JITTER_NONE:
+        tr = t_rand.float().cpu()
+        tr = tr[:, None] if jitter_mode == abi.JITTER_SINGLE else tr
+        lo = torch.cat([b[:1], (b[1:] + b[:-1]) / 2.0])
+        hi = torch.cat([(b[1:] + b[:-1]) / 2.0, b[-1:]])
+        return (lo[None] + (hi - lo)[None] * tr).contiguous()
+    return b[None].repeat(n_rays, 1)
+
+
+def neus_upsample_reference(sdf_at, origins, dirs, nears, fars, n_samples, n_importance, n_steps, base_variance, *,
+                            jitter_mode=abi.JITTER_NONE, t_rand=None, u_rand=None, dtype=torch.float32):
+    """The definition of NeuS up-sampling on CPU tensors, in ``dtype`` (float32, or float64 on
+    request).  ``sdf_at``: callable (n, 3) positions in ``dtype`` -> (n,) SDF, the lookup of the field.  origins / dirs (N, 3),
+    nears / fars (N,): the rays and what the box collider gives them.  The start edges are part of the inputs: float32
+    (``uniform_edges_reference``) whatever ``dtype``.  Returns (N, S_tot + 1) normalised edges in ``dtype``."""
+    N = origins.shape[0]
+    m, K, _ = upsample_plan(int(n_samples), int(n_importance), int(n_steps))
+    b = uniform_edges_reference(n_samples, jitter_mode, t_rand, N).to(dtype)
+    o, d = origins.cpu().to(dtype), dirs.cpu().to(dtype)
+    tn, tf = nears.cpu().to(dtype)[:, None], fars.cpu().to(dtype)[:, None]
+    n = int(n_samples)
+    for k in range(K):
+        s = float(base_variance) * 2.0 ** k
+        t = b * tf + (1 - b) * tn                                                      # (N, n + 1)
+        f = sdf_at((o[:, None, :] + d[:, None, :] * t[:, :n, None]).reshape(-1, 3)).reshape(N, n).to(dtype)
+        delta = t[:, 1:n] - t[:, :n - 1]                                               # i = 0 .. n - 2
+        mid = (f[:, :-1] + f[:, 1:]) * 0.5
+        cos = (f[:, 1:] - f[:, :-1]) / (delta + 1e-5)
+        prev = torch.cat([torch.zeros(N, 1, dtype=dtype), cos[:, :-1]], 1)[:, :n - 1]       # cos_{i-1}, cos_{-1} = 0
+        c = torch.minimum(prev, cos).clamp(-1e3, 0.0)
+        half = c * delta * 0.5
+        pc, nc = torch.sigmoid((mid - half) * s), torch.sigmoid((mid + half) * s)
+        alpha = (pc - nc + 1e-5) / (pc + 1e-5)
+        trans = torch.cumprod(torch.cat([torch.ones(N, 1, dtype=dtype), 1.0 - alpha + 1e-7], 1), 1)[:, :-1]
+        w = torch.cat([alpha * trans, torch.zeros(N, 1, dtype=dtype)], 1) + 1e-5       # (N, n)
+        W = w.sum(-1, keepdim=True)
+        pad = torch.relu(1e-5 - W)
+        w, W = w + pad / n, W + pad
+        cdf = torch.cat([torch.zeros(N, 1, dtype=dtype), torch.cumsum(w / W, -1).clamp(max=1.0)], 1).contiguous()   # (N, n + 1)
+        lin = torch.linspace(0.0, 1.0 - 1.0 / (m + 1), m + 1, dtype=torch.float32).to(dtype)
+        r = torch.full((N,), 0.5, dtype=dtype) if u_rand is None else u_rand[k].cpu().to(dtype)
+        u = (lin[None] + r[:, None] / (m + 1)).contiguous()                            # (N, m + 1)
+        idx = torch.searchsorted(cdf, u, right=True)
+        lo, hi = (idx - 1).clamp(0, n), idx.clamp(0, n)
+        c_lo, c_hi = torch.gather(cdf, 1, lo), torch.gather(cdf, 1, hi)
+        den = c_hi - c_lo
+        q = torch.where(den == 0, torch.zeros_like(den), (u - c_lo) / torch.where(den == 0, torch.ones_like(den), den)).clamp(0.0, 1.0)
+        b_lo, b_hi = torch.gather(b, 1, lo), torch.gather(b, 1, hi)
+        p = b_lo + q * (b_hi - b_lo)
+        b = torch.cat([torch.sort(torch.cat([b[:, :n], p[:, :m]], 1), -1).values, torch.maximum(b[:, n:], p[:, m:])], 1)
+        n += m
+    return b
 
 
 _BRICK_WS = {}
@@ -402,10 +528,11 @@ class _RenderFunction(torch.autograd.Function):
 
 
 def render_rays_autograd(vol: SDFVolume, inv_s: torch.Tensor, rays: RaySet, cfg: RenderConfig, *,
-                         want_grad_samples=True, t_rand=None, bkgd_rays=None):
+                         want_grad_samples=True, t_rand=None, bkgd_rays=None, edges=None):
     """Training-time render: returns the same dict as ``render_rays(per_sample=True)`` with
     depth / acc / rgb / sem / weights / sdf / grad attached to the autograd graph of
-    ``vol.sdf``, ``vol.feat`` and ``inv_s``."""
+    ``vol.sdf``, ``vol.feat`` and ``inv_s``.  ``edges``: see ``_with_edges``; they carry no gradient."""
+    cfg, t_rand = _with_edges(cfg, edges, t_rand, rays.n_rays)
     res = _RenderFunction.apply(vol.sdf, vol.feat, inv_s, vol.mapping, vol.n_rgb, vol.n_sem, rays, cfg,
                                 t_rand, bkgd_rays, want_grad_samples, vol.sh_deg, vol.sh_act)
     keys = ['depth', 'acc'] + (['rgb'] if vol.n_rgb else []) + (['sem'] if vol.n_sem else []) + ['weights'] + \
