@@ -875,8 +875,9 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
 //                  position of step i + 1, issue its 1-byte code load
 //                  only if not skipping: the two 16-byte record loads of step i, then interpolate + alpha
 //                  composite
-// A skipped step moves 1 byte per lane through the L1 instead of 33.  Nothing is software-pipelined beyond
-// that: measurements showed the march insensitive to load/compute overlap inside a wave (8 waves / SIMD hide it).
+// A skipped step moves 1 byte per lane through the L1 instead of 33.  The general step is not software-pipelined beyond
+// that: measurements showed it insensitive to load/compute overlap inside a wave (8 waves / SIMD hide it).  The one loop
+// that is pipelined is low mode's (`low` below), whose steps know their successor's cell ten instructions into the trip.
 //
 // Free-space steps come in long runs (mean 33 steps at inv_s 20), and inside a run three tests of the general
 // step have a known outcome, so a run loop (`run` below) composites the steps after a skipped one without them:
@@ -899,6 +900,13 @@ constexpr int kSureScan = 8;   // steps tried from either end of the march for t
 constexpr bool kLowMode = false;
 #else
 constexpr bool kLowMode = true;
+#endif
+// Low mode loads the records of the next low step under the current one; -DSO_NO_LOW_PREFETCH builds the loop that loads a
+// step's records at the top of its own trip, for A/B runs.
+#ifdef SO_NO_LOW_PREFETCH
+constexpr bool kLowPrefetch = false;
+#else
+constexpr bool kLowPrefetch = true;
 #endif
 // kLowC lies 15 * 2^-24 relative below kSkipArg * log2(e) = 25.2471632...: see the proof in `low`
 constexpr float kLowC = 25.24714f;
@@ -1141,21 +1149,39 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
     // the march is over (returns true).
     auto low = [&](int &i, AheadStep &st) __attribute__((always_inline)) {
         // One loop, one exit: every reason to leave is folded into `go` (a loop with several exits gets an exit number from
-        // the compiler, made in a VGPR and read back with v_readfirstlane on every trip).  The next step's fractions and
-        // near-face test are taken at the end of a trip, for the same reason.
-        float fh = __builtin_amdgcn_fractf(st.gh), fw = __builtin_amdgcn_fractf(st.gw), fd = __builtin_amdgcn_fractf(st.gd);
+        // the compiler, made in a VGPR and read back with v_readfirstlane on every trip).  The next step's near-face test is
+        // taken at the end of a trip, for the same reason.
+        //   The loop is software-pipelined.  A trip used to issue its two record loads first and wait
+        // for them nine instructions later: one vector-L1 round trip per step with nothing of the wave's own under it.  Now a
+        // trip places step i + 1 first and issues ITS records into a second register set, then interpolates step i from the
+        // set the trip before loaded: every pair has a whole trip to arrive.  The loads of step i + 1 are unconditional; a
+        // trip runs only with i + 1 < i_hi, so the cell is an interior one of the sure range whatever becomes of the step.
+        // -DSO_NO_LOW_PREFETCH builds the loop that loads a step's records in its own trip.
+        struct so_f3 { float h, w, d; };
+        using so_f3r = so_f3 &;
+        auto fractions = [&]() __attribute__((always_inline)) {
+            return so_f3{__builtin_amdgcn_fractf(st.gh), __builtin_amdgcn_fractf(st.gw), __builtin_amdgcn_fractf(st.gd)};
+        };
+        so_f3 f0 = fractions(), f1;
         bool coded = false;                  // st.code is on its way
-        bool go = i + 1 < i_hi && !(FACE_SAFE && __any(near_face(fh, fw, fd)));
-#pragma nounroll
-        while (go) {
-            const so_f4v lo = so_bload4(rb, st.cell * 16u, 0u), hi = so_bload4(rb, st.cell * 16u, row_off);
+        bool go = i + 1 < i_hi && !(FACE_SAFE && __any(near_face(f0.h, f0.w, f0.d)));
+        // One trip: step i from its records (lo, hi); with kLowPrefetch the records of step i + 1 are issued into (nlo, nhi)
+        // as soon as its cell is placed, ahead of the first use of (lo, hi).
+        auto trip = [&](so_f4v &lo, so_f4v &hi, so_f4v &nlo, so_f4v &nhi, so_f3r f, so_f3r nf) __attribute__((always_inline)) {
+            if constexpr (!kLowPrefetch) { lo = so_bload4(rb, st.cell * 16u, 0u); hi = so_bload4(rb, st.cell * 16u, row_off); }
             float t_mid = fmaf(st.fi, dt, tnear + hdt);
             asm volatile("" : "+v"(t_mid));      // here, while st.fi is the step's: computed later it keeps a copy of st.fi alive
             ++i;
             place(i, st);
+            if constexpr (kLowPrefetch) {
+                // i <= i_hi - 1 here: an interior cell of the sure range, whatever becomes of the step
+                nlo = so_bload4(rb, st.cell * 16u, 0u); nhi = so_bload4(rb, st.cell * 16u, row_off);
+                __builtin_amdgcn_sched_barrier(0);      // the scheduler otherwise sinks the pair under this step's arithmetic
+                nf = fractions();                       // here: the coordinates need not outlive the loads (see the exit)
+            }
             const bool proven = __any(lo.x <= low_thr);
             float sdf, dh0, gvw, gvd;
-            so_trilerp_fast_pk(lo.xy, lo.zw, hi.xy, hi.zw, fh, fw, fd, sdf, dh0, gvw, gvd);
+            so_trilerp_fast_pk(lo.xy, lo.zw, hi.xy, hi.zw, f.h, f.w, f.d, sdf, dh0, gvw, gvd);
             const float cosv = fmaf(gvd, Gdd, fmaf(gvw, Gdw, dh0 * Gdh));
             float alpha = so_alpha_fast(sdf * s2, fminf(cosv, 0.0f) * hdt_s2);
             if (__builtin_expect(!proven, 0)) {
@@ -1164,8 +1190,16 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
                 AheadStep was;
                 place(i - 1, was);
                 const unsigned code = __builtin_amdgcn_raw_buffer_load_b8(rb, was.cell, codes_off, 0);
-                st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, codes_off, 0);
-                if (so_all((int)code >= rcode)) alpha = kAlphaFree;     // skipped: the constant alpha, as step() composites it
+                unsigned next_cell = st.cell;
+                if constexpr (kLowPrefetch) {       // placed once more as well: the hot path keeps no cell past its loads
+                    int ia = i;
+                    asm volatile("" : "+s"(ia));
+                    AheadStep now;
+                    place(ia, now);
+                    next_cell = now.cell;
+                }
+                st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, next_cell, codes_off, 0);
+                if (so_all((int)code >= rcode)) alpha = kAlphaFree;    // skipped: the constant alpha, as step() composites it
                 coded = true;
             }
             const float w = alpha * T;
@@ -1173,10 +1207,34 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
             acc = acc + w;
             dsum = fmaf(w, t_mid, dsum);
             if (w > best_w) { best_w = w; best_t = t_mid; }
-            fh = __builtin_amdgcn_fractf(st.gh); fw = __builtin_amdgcn_fractf(st.gw); fd = __builtin_amdgcn_fractf(st.gd);
-            go = !coded && !so_all(T < 1e-10f) && i + 1 < i_hi && !(FACE_SAFE && __any(near_face(fh, fw, fd)));
+            if constexpr (!kLowPrefetch) nf = fractions();
+            go = !coded && !so_all(T < 1e-10f) && i + 1 < i_hi && !(FACE_SAFE && __any(near_face(nf.h, nf.w, nf.d)));
+        };
+        so_f4v lo0, hi0, lo1, hi1;
+        if constexpr (kLowPrefetch) {
+            // The body twice, the two record sets ping-ponged: no register copies, and the wait in front of a trip's first
+            // use is a counted one that leaves the younger pair in flight.  One exit test per half, both to the same place;
+            // the pair in flight at the exit is dropped (the sure loop loads the step's records itself if it interpolates).
+            if (go) {
+                lo0 = so_bload4(rb, st.cell * 16u, 0u); hi0 = so_bload4(rb, st.cell * 16u, row_off);
+#pragma nounroll
+                for (;;) {
+                    trip(lo0, hi0, lo1, hi1, f0, f1);
+                    if (!go) break;
+                    trip(lo1, hi1, lo0, hi0, f1, f0);
+                    if (!go) break;
+                }
+                // `st` is step i's again from its index alone (an operand the optimiser cannot see through): nothing of a
+                // placed step but its cell and fi stays in a register across a trip, and the two halves need no copies
+                int ii = i;
+                asm volatile("" : "+s"(ii));
+                place(ii, st);
+            }
+        } else {
+#pragma nounroll
+            while (go) trip(lo0, hi0, lo1, hi1, f0, f0);
         }
-        if (so_all(T < 1e-10f)) return true;    // false on entry: the caller has just tested it
+        if (so_all(T < 1e-10f)) return true;   // false on entry: the caller has just tested it
         if (!coded) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, codes_off, 0);
         return false;
     };
