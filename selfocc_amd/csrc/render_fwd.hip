@@ -890,10 +890,60 @@ SO_DEVFN void so_march_fast(const so_render_args &a, int ray, GeomFn geom, bool 
 // scalar work and branches of a step whose outcome is known there).
 // What a lane computes at a step, and every wave-wide decision, is what the step-by-step form computes: same outputs, bit for bit.
 // ---------------------------------------------------------------------------------------
+// The exit: a wave leaves the march once no later step can change a bit of what it stores.
+// so_march_fast leaves when every lane has T < 1e-10, "whatever comes adds less than 1e-10 to any output", which is far
+// below what float32 registers: next to acc ~ 1 a weight under 2^-25 is already lost.  A lane is SPENT at the end of a step
+// when every later step of its march leaves acc, dsum, best_w and best_t as they are, and the wave leaves when all its lanes
+// are spent (or the old test holds, so the rule is a superset of the old one by construction).  With u = 2^-24, at the end
+// of a step with the lane's T, acc, dsum, best_w, the lane is spent if
+//     (a) T * 2^25 < acc,   (b) fl((T * 2^26) * tb) < |dsum|,   (c) T <= best_w,
+// tb = max(|t_mid(0)|, |t_mid(S - 1)|).  The proof:
+//   * T does not grow and stays >= 0.  A step multiplies T by fl(fl(1 - alpha) + 1e-7f).  so_alpha_fast never returns NaN
+//     (its fminf's drop a NaN operand: a NaN corner or slope gives alpha ~ 1) and returns alpha in [~0.99e-5, 1]: eb >= ea up
+//     to an ulp of v_exp_f32, so num >= 1e-5 p - 6e-8 and den = 1 + 1e-5 p, and the final fminf caps it.  A free step has
+//     alpha = kAlphaFree ~ 1e-5.  Either way the factor lies in [1e-7, 1 - 9e-6]: below 1, so the rounded product is <= T,
+//     and not negative.  Every later weight is w = fl(alpha * T') <= T' <= T, with T' the T of that later step.
+//   * acc: (a) in real numbers is T < acc * 2^-25 (the scaling of T <= 1 by 2^25 is exact, for a subnormal T as well), and
+//     acc * 2^-25 is less than half an ulp of acc (acc < 2^(e + 1), half an ulp is 2^(e - 24)).  So 0 <= w < ulp(acc) / 2 and
+//     fl(acc + w) == acc.  (acc * 2^-25 rather than the exponent of acc: one multiply instead of an and / or pair, and it
+//     costs at most a factor 2 of T, 0.7 of the ~17 e-foldings.)
+//   * dsum: fma(w, t_mid, dsum) rounds dsum + w * t_mid once.  t_mid(fi) = fma(fi, dt, tnear + hdt) is monotone in fi
+//     (dt > 0: so_collide makes tfar > tnear), so |t_mid| <= tb at every step, and |w * t_mid| <= T * tb.  T * 2^26 is exact
+//     and the product with tb is rounded once, so (b) gives T * tb < |dsum| 2^-26 (1 + 2 u): half of |dsum| 2^-25, which is
+//     itself under half an ulp of dsum; the factor 2 carries the rounding of the product and the case t_mid < 0 < dsum with
+//     dsum a power of two, where the spacing below dsum is half the spacing above.  A product that underflows has
+//     T * tb < 2^-152, which no fma registers.  (b) is false at dsum == 0.
+//   * best weight: w <= T <= best_w, so `w > best_w` stays false and neither best_w nor best_t is written.
+//     (In practice (b) is the condition that decides: dsum <= ~acc * tb makes it imply (a) with its factor 2 to spare, and
+//     best_w >= acc / S makes (a) imply (c) for any S below 2^25.  (a) and (c) cost three instructions of the rare block and
+//     keep the proof free of both estimates.)
+//   * monotonicity: while (a) - (c) hold nothing on their right-hand sides changes and T only falls, so they hold at every
+//     later step too: the induction goes through, and the test may be made at any step, or late.
+//   * NaN or inf in acc, dsum, tb or best_w (T itself is finite, see above): a NaN makes its compare false, so the lane is
+//     not spent and the wave stays; an infinite acc or dsum stays what it is under a finite addend.  The old test does not
+//     look at them at all.
+//   * Nothing stored reads T: depth, acc, max_depth come from acc, dsum, best_t; nears / fars from the collider.
+// (a) needs T < acc * 2^-25 < 2^-24 = kSpentPre (acc < 2: it is 1 - T up to the 1e-7 per step that the factor adds), and
+// 1e-10 < kSpentPre, so the hot path keeps ONE compare against one wave-uniform constant, `all lanes T < kSpentPre`, where it
+// had `all lanes T < 1e-10`; (a) - (c) are evaluated, in a block laid out behind the loops, on the few closing steps of a wave
+// at which that pre-test holds.  -DSO_NO_SPENT_EXIT builds the 1e-10 rule alone, for A/B runs.
+//
 // A run of n free steps multiplies T by ((1 - kAlphaFree) + 1e-7f) n times, each product rounded: by more than
-// (1 - 1e-5)^n, which is > 0.54 for n <= 60 000.  A lane that enters a run of at most that many steps with T >= 2e-10
-// therefore stays above 1e-10 to its end, and the wave-wide exit test `all lanes T < 1e-10` is false throughout.
+// (1 - 1e-5)^n, which is > 0.54 for n <= 60 000 (a normal T: each rounding costs at most 1 - 2^-24), and adds n weights of at
+// most kAlphaFree * T each to acc, 0.6 T in all, each sum rounded (at most 1 + 60 000 * 2^-24 < 1.004 in all).  Take a lane
+// that enters a run of at most that many steps with T >= 2e-10 and T * 2^24 >= acc.  To its end T' >= 0.54 T > 1e-10, and
+// acc' <= 1.004 (acc + 0.6 T) <= 1.004 (2^24 + 0.6) T < 0.54 * 2^25 T <= T' * 2^25: condition (a) fails, the lane is not
+// spent.  Neither the old nor the new test can hold while the wave has such a lane, so the run needs no exit test.  (With
+// acc < 2 every lane at or above 2 * kSpentPre is such a lane, and so are the lanes within a factor 2 above the level at
+// which (a) begins to hold.  With SO_NO_SPENT_EXIT the lane is one with T >= 2e-10, as in the parent.)
 constexpr int kRunExitFreeSteps = 60000;
+#ifdef SO_NO_SPENT_EXIT
+constexpr bool kSpentExit = false;
+constexpr float kSpentPre = 1e-10f;
+#else
+constexpr bool kSpentExit = true;
+constexpr float kSpentPre = 0x1p-24f;
+#endif
 constexpr int kSureScan = 8;   // steps tried from either end of the march for the sure-interior range
 // Low mode of the sure loop (see `low` in so_march_fast_ahead); -DSO_NO_LOW_MODE builds the marcher without it, for A/B runs.
 #ifdef SO_NO_LOW_MODE
@@ -954,6 +1004,20 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
     float T = 1.0f, acc = 0.0f, dsum = 0.0f, best_w = -1.0f, best_t = 0.0f;
     bool low_hint_a = false, low_hint_b = false;     // wave-uniform: set by the two steps of the sure loop's body (low mode)
     const float low_thr = kLowC * so_fast_rcp(s2);   // low mode: a corner at or under it is under the brick pass's 17.5 / inv_s
+
+    // The exit test of every loop (wave-uniform): see kSpentPre.  The bound on |t_mid| is made inside the rare block from
+    // what the loops keep live anyway; nothing of the test stays in a register across a step.
+    auto over_now = [&]() __attribute__((always_inline)) {
+        if (__builtin_expect(!so_all(T < kSpentPre), 1)) return false;
+        if constexpr (!kSpentExit) return true;
+        // the last step's index through an operand the optimiser cannot see through: the bound is loop-invariant, and
+        // hoisted in front of the loops it costs a VGPR across all of them
+        int last = S - 1;
+        asm volatile("" : "+s"(last));
+        const float t_first = tnear + hdt;
+        const float tb = fmaxf(fabsf(t_first), fabsf(fmaf((float)last, dt, t_first)));
+        return so_all3(T * 0x1p25f < acc, (T * 0x1p26f) * tb < fabsf(dsum), T <= best_w) || so_all(T < 1e-10f);
+    };
 
     // position and cell of step i
     auto place = [&](const int i, AheadStep &st) __attribute__((always_inline)) {
@@ -1208,7 +1272,7 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
             dsum = fmaf(w, t_mid, dsum);
             if (w > best_w) { best_w = w; best_t = t_mid; }
             if constexpr (!kLowPrefetch) nf = fractions();
-            go = !coded && !so_all(T < 1e-10f) && i + 1 < i_hi && !(FACE_SAFE && __any(near_face(nf.h, nf.w, nf.d)));
+            go = !coded && !over_now() && i + 1 < i_hi && !(FACE_SAFE && __any(near_face(nf.h, nf.w, nf.d)));
         };
         so_f4v lo0, hi0, lo1, hi1;
         if constexpr (kLowPrefetch) {
@@ -1234,7 +1298,7 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
 #pragma nounroll
             while (go) trip(lo0, hi0, lo1, hi1, f0, f0);
         }
-        if (so_all(T < 1e-10f)) return true;   // false on entry: the caller has just tested it
+        if (over_now()) return true;   // false on entry: the caller has just tested it
         if (!coded) st.code = __builtin_amdgcn_raw_buffer_load_b8(rb, st.cell, codes_off, 0);
         return false;
     };
@@ -1254,12 +1318,15 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
             acc = acc + w;
             dsum = fmaf(w, t_mid, dsum);
         };
-        if (S <= kRunExitFreeSteps && !so_all(T < 2e-10f)) {   // some lane keeps the wave's exit test false: kRunExitFreeSteps
+        // some lane keeps the wave's exit test false: kRunExitFreeSteps
+        const bool kept = kSpentExit ? (__builtin_amdgcn_ballot_w64(T * 0x1p24f >= acc) & __builtin_amdgcn_ballot_w64(T >= 2e-10f)) != 0
+                                     : !so_all(T < 2e-10f);
+        if (S <= kRunExitFreeSteps && kept) {
             while (i < i_hi && so_all((int)st.code >= rcode)) free_step();
         } else {
             while (i < i_hi && so_all((int)st.code >= rcode)) {
                 free_step();
-                if (so_all(T < 1e-10f)) return true;
+                if (over_now()) return true;
             }
         }
         return false;
@@ -1284,7 +1351,7 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
 #pragma nounroll
             while (i < end) {
                 step(i, A, B, general, unused_hint);
-                if (++i >= S || so_all(T < 1e-10f)) { over = true; break; }
+                if (++i >= S || over_now()) { over = true; break; }
                 A = B;
             }
         };
@@ -1293,11 +1360,11 @@ SO_DEVFN void so_march_fast_ahead(const so_render_args &a, const so_launch_const
             while (i < i_hi) {
                 const bool sa = step(i, A, B, in_sure, low_hint_a);
                 ++i;
-                if (so_all(T < 1e-10f) || (sa && run(i, B))) { over = true; break; }
+                if (over_now() || (sa && run(i, B))) { over = true; break; }
                 if (i >= i_hi) { A = B; break; }        // the tail takes its located step from A
                 const bool sb = step(i, B, A, in_sure, low_hint_b);
                 ++i;
-                if (so_all(T < 1e-10f) || (sb && run(i, A))) { over = true; break; }
+                if (over_now() || (sb && run(i, A))) { over = true; break; }
                 // Low mode opens here only, on A, so that the loop has one copy of it, and after two steps in a row in which
                 // no lane could skip (the hint of step()).  A low step that the code skipped hands the skipping step back,
                 // and the step above takes it to the run loop.
