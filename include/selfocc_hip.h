@@ -717,7 +717,25 @@ int selfocc_linear_wgrad(const float *dy, const float *x, float *dw, float *db, 
  * float32 (MFMA f32 = exact fmaf chains; only the summation order differs from a BLAS).  K must be 32, 64, 96, 128
  * or 192 (selfocc_linear_fwd_supported).
  * ---------------------------------------------------------------------------------- */
-enum { SO_LINEAR_RELU = 1 };
+enum { SO_LINEAR_RELU = 1, SO_LINEAR_BF16X1 = 2 };
+/* SO_LINEAR_BF16X1 — the opt-in one-product bfloat16 mode of every tall-Linear pass (off by default; Python: LINEAR_BF16).
+ * Definition: with the flag a pass computes exactly what it computes without it on the operands bf16_rne(a), bf16_rne(b) taken
+ * as float32 values (bf16_rne = round to nearest even, the (__bf16) conversion so_split3 uses for its first plane):
+ *     forward  y  = LN?( relu?( x^ W^^T + bias ) + residual )
+ *     dgrad    dx = dy^ W^
+ *     wgrad    dW = dy^^T x^,   db = the column sums of the ROUNDED dy^
+ * bias, residual, gamma and beta stay float32 and unrounded; outputs are float32; accumulation is float32 in the kernel's own
+ * order; the epilogues are the default's.  ONE bf16 MFMA per 32 k instead of the six of the exact three-way split, one
+ * conversion per loaded value instead of the split, one W plane in LDS (forward) or in the workspace (dgrad): about three
+ * decimal digits (2^-9 relative per operand) for less arithmetic.  What the flag computes does not depend on the shape through
+ * the dispatch: a flagged launch ALWAYS runs a one-product kernel — the f32-MFMA kernels (linear_fwd16_kernel,
+ * linear_wgrad_kernel) never serve it, SELFOCC_LINEAR_B3=0 does not apply to it, and the wgrad at K = 128, which the default
+ * leaves to the f32-MFMA kernel, has one-product instances of its own (the decision taken for K = 128: built, not refused; K = 192
+ * runs as two halves of three column tiles with the default's one tile row).  So every *_supported query answers the same for both
+ * modes and has no flagged twin.  The flag is bit 2 of the `flags` of selfocc_linear_fwd / _fwd_heads / _fwd_grouped; the
+ * backward passes take it through the *_flags twins below (the entries without `flags` are those with flags = 0).  The twins
+ * refuse any other bit ("unknown flags"); the *_workspace_flags queries then return 0.  Workspaces: dgrad a third of the
+ * default's; wgrad never more than the default's (the default sizes are valid upper bounds). */
 int selfocc_linear_fwd_supported(int64_t T, int32_t N, int32_t K);
 int selfocc_linear_fwd(const float *x, const float *w, const float *bias, const float *residual, int32_t ldr,
                        const float *ln_gamma, const float *ln_beta, float ln_eps, float *y, int32_t ldy, float *y_pre,
@@ -742,6 +760,22 @@ int selfocc_linear_dgrad_supported(int64_t T, int32_t N, int32_t K);
 size_t selfocc_linear_dgrad_workspace(int32_t N, int32_t K);   /* bytes: the three bf16 planes of W^T, 16-byte aligned */
 int selfocc_linear_dgrad(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K, void *workspace,
                          int64_t workspace_bytes, void *stream);
+
+/* The backward passes with `flags` (0 or SO_LINEAR_BF16X1, see there): the entries above and the grouped ones are these with
+ * flags = 0.  workspace: the matching *_workspace_flags(..., flags) bytes.  Every argument check — unknown flag bits, shape,
+ * NULL pointers, workspace size — happens on the host before anything touches the device. */
+size_t selfocc_linear_dgrad_workspace_flags(int32_t N, int32_t K, uint32_t flags);
+int selfocc_linear_dgrad_flags(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K, void *workspace,
+                               int64_t workspace_bytes, uint32_t flags, void *stream);
+size_t selfocc_linear_dgrad_grouped_workspace_flags(int32_t N, int32_t K, so_row_groups groups, uint32_t flags);
+int selfocc_linear_dgrad_grouped_flags(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K,
+                                       so_row_groups groups, void *workspace, int64_t workspace_bytes, uint32_t flags, void *stream);
+size_t selfocc_linear_wgrad_workspace_flags(int64_t T, int32_t N, int32_t K, uint32_t flags);
+int selfocc_linear_wgrad_flags(const float *dy, const float *x, float *dw, float *db, int64_t T, int32_t N, int32_t K,
+                               void *workspace, size_t workspace_bytes, uint32_t flags, void *stream);
+size_t selfocc_linear_wgrad_grouped_workspace_flags(int64_t T, int32_t N, int32_t K, so_row_groups groups, uint32_t flags);
+int selfocc_linear_wgrad_grouped_flags(const float *dy, const float *x, float *dw, float *db, int64_t T, int32_t N, int32_t K,
+                                       so_row_groups groups, void *workspace, size_t workspace_bytes, uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Fused temporal reprojection photometric term.  Replaces the per-sample part of

@@ -19,7 +19,7 @@ MSDA_PLAIN, MSDA_FUSED, MSDA_CROSS = 0, 1, 2
 MSDA_PLAN_LOG2_GROUP, MSDA_PLAN_BANDED, MSDA_PLAN_COUNT_HERE, MSDA_PLAN_BIN_VIS, MSDA_PLAN_BANDS, MSDA_PLAN_ROWS, MSDA_PLAN_INTS = 0, 1, 2, 3, 4, 12, 20
 VALUE_PIXEL_MAJOR, VALUE_HEAD_MAJOR = 0, 1
 DTYPE_F32, DTYPE_BF16 = 0, 1
-LINEAR_RELU = 1
+LINEAR_RELU, LINEAR_BF16X1 = 1, 2
 LBL_F32, LBL_U8, LBL_I32, LBL_I64 = 0, 1, 2, 3
 MAP_LINEAR, MAP_UPSCALE = 0, 1
 SH_RELU, SH_SIGMOID = 0, 1
@@ -255,6 +255,14 @@ SYMBOLS = {
     "selfocc_linear_dgrad_supported": (C.c_int, [C.c_int64, _i, _i]),
     "selfocc_linear_dgrad_workspace": (C.c_size_t, [_i, _i]),
     "selfocc_linear_dgrad": (C.c_int, [_p] * 3 + [C.c_int64, _i, _i, _p, C.c_int64, _p]),
+    "selfocc_linear_dgrad_workspace_flags": (C.c_size_t, [_i, _i, C.c_uint32]),
+    "selfocc_linear_dgrad_flags": (C.c_int, [_p] * 3 + [C.c_int64, _i, _i, _p, C.c_int64, C.c_uint32, _p]),
+    "selfocc_linear_dgrad_grouped_workspace_flags": (C.c_size_t, [_i, _i, SoRowGroups, C.c_uint32]),
+    "selfocc_linear_dgrad_grouped_flags": (C.c_int, [_p] * 3 + [C.c_int64, _i, _i, SoRowGroups, _p, C.c_int64, C.c_uint32, _p]),
+    "selfocc_linear_wgrad_workspace_flags": (C.c_size_t, [C.c_int64, _i, _i, C.c_uint32]),
+    "selfocc_linear_wgrad_flags": (C.c_int, [_p] * 4 + [C.c_int64, _i, _i, _p, C.c_size_t, C.c_uint32, _p]),
+    "selfocc_linear_wgrad_grouped_workspace_flags": (C.c_size_t, [C.c_int64, _i, _i, SoRowGroups, C.c_uint32]),
+    "selfocc_linear_wgrad_grouped_flags": (C.c_int, [_p] * 4 + [C.c_int64, _i, _i, SoRowGroups, _p, C.c_size_t, C.c_uint32, _p]),
     "selfocc_second_diff_size": (C.c_size_t, [_i, _i, _i]),
     "selfocc_second_diff_fwd": (C.c_int, [_p, _p, _i, _i, _i, _p]),
     "selfocc_second_diff_bwd": (C.c_int, [_p, _p, _i, _i, _i, _p]),

@@ -181,10 +181,23 @@ SO_DEVFN void so_wsplit3(const float (&x)[8], bf16x8w &a1, bf16x8w &a2, bf16x8w 
     }
 }
 
-template <int KT, int NTW, bool GRP = false>
+// P = planes per operand: 3 = the exact split; 1 = SO_LINEAR_BF16X1 (LINEAR_BF16), ONE product of the round-to-nearest-even
+// bfloat16 of dY and X — one conversion per loaded value instead of the split, one MFMA instead of six, and the bias gradient is
+// the float32 running sum of the ROUNDED dY (the mode computes what the default would on the rounded operands).  The 16-row
+// walk, the tiles, the block reduction and the stores are P = 3's.  P = 1 also has the K = 128 instances (KT = 4) that P = 3
+// leaves to the f32-MFMA kernel: a flagged launch never runs on that one.  Two things are P = 1's own (measured):
+// it prefetches the next step wherever <= 6 accumulator tiles leave the registers (with a sixth of the matrix work nothing else
+// hides a load: without it the NTW = 2 shapes ran 2 x slower than the default), and K = 192 runs as two blocks of three column
+// tiles (grid z) instead of KT = 6, which has no registers for the prefetch.
+template <int KT, int NTW, bool GRP = false, int P = 3>
 __global__ __launch_bounds__(256, 2) void linear_wgrad_b3_kernel(const float *__restrict__ dy, const float *__restrict__ x,
                                                                  float *__restrict__ part_w, float *__restrict__ part_b,
                                                                  long long T, int N, int K, long long rows_per_block, so_group_table gr) {
+    static_assert(P == 3 || P == 1, "planes per operand");
+    // P = 1: blockIdx.z selects a block of KT * 32 input columns (K = 192 runs as two halves of three tiles: six tiles and a
+    // prefetch do not fit the registers, and without the prefetch the one-product loop only waits for its loads)
+    int k0 = 0;
+    if constexpr (P == 1) k0 = blockIdx.z * (KT * 32);
     __shared__ float red[NTW * KT * 1024];
     __shared__ float red_b[4][NTW * 32];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -210,7 +223,9 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_b3_kernel(const float *__
 
     // the operands of step r + 16 are loaded before the MFMAs of step r (NTW = 1: the registers are there): a wave has
     // 2 - 3 neighbours on its SIMD, not enough to cover the HBM latency of 16 rows by themselves
-    constexpr bool PF = NTW == 1 && KT <= 3;      // (NTW = 2 with the second operand set: 255 registers, measured 58 -> 74 us)
+    // (NTW = 2 with the second operand set: 255 registers, measured 58 -> 74 us).  P = 1 has one plane per operand instead of three and
+    // a sixth of the matrix work to hide a load behind: it prefetches wherever <= 6 accumulator tiles leave the registers.
+    constexpr bool PF = (NTW == 1 && KT <= 3) || (P == 1 && NTW * KT <= 6 && KT <= 4);
     float a[NTW][8], b[KT][8], an[PF ? NTW : 1][8], bn[PF ? KT : 1][8];
     auto load_step = [&](long long r, float (&da)[NTW][8], float (&db)[KT][8]) {
 #pragma unroll
@@ -218,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_b3_kernel(const float *__
             const long long rr = r + 8 * half + j;
             const bool ok = rr < r1;
             const float *dyr = dy + rr * N + n0 + i;
-            const float *xr = x + rr * K + i;
+            const float *xr = x + rr * K + k0 + i;
 #pragma unroll
             for (int t = 0; t < NTW; ++t) da[t][j] = (ok && ncol[t]) ? dyr[t * 32] : 0.0f;
 #pragma unroll
@@ -232,23 +247,42 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_b3_kernel(const float *__
         } else {
             load_step(r, a, b);
         }
-        bf16x8w b1[KT], b2[KT], b3[KT];
+        if constexpr (P == 3) {
+            bf16x8w b1[KT], b2[KT], b3[KT];
 #pragma unroll
-        for (int u = 0; u < KT; ++u) so_wsplit3(b[u], b1[u], b2[u], b3[u]);
+            for (int u = 0; u < KT; ++u) so_wsplit3(b[u], b1[u], b2[u], b3[u]);
 #pragma unroll
-        for (int t = 0; t < NTW; ++t) {
+            for (int t = 0; t < NTW; ++t) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) bsum[t] += a[t][j];
-            bf16x8w a1, a2, a3;
-            so_wsplit3(a[t], a1, a2, a3);
+                for (int j = 0; j < 8; ++j) bsum[t] += a[t][j];
+                bf16x8w a1, a2, a3;
+                so_wsplit3(a[t], a1, a2, a3);
 #pragma unroll
-            for (int u = 0; u < KT; ++u) {
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1[u], acc[t][u], 0, 0, 0);
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3[u], acc[t][u], 0, 0, 0);
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2[u], acc[t][u], 0, 0, 0);
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1[u], acc[t][u], 0, 0, 0);
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2[u], acc[t][u], 0, 0, 0);
-                acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1[u], acc[t][u], 0, 0, 0);
+                for (int u = 0; u < KT; ++u) {
+                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1[u], acc[t][u], 0, 0, 0);
+                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3[u], acc[t][u], 0, 0, 0);
+                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2[u], acc[t][u], 0, 0, 0);
+                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1[u], acc[t][u], 0, 0, 0);
+                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2[u], acc[t][u], 0, 0, 0);
+                    acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1[u], acc[t][u], 0, 0, 0);
+                }
+            }
+        } else {
+            bf16x8w b1[KT];
+#pragma unroll
+            for (int u = 0; u < KT; ++u)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) b1[u][j] = (__bf16)b[u][j];
+#pragma unroll
+            for (int t = 0; t < NTW; ++t) {
+                bf16x8w a1;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    a1[j] = (__bf16)a[t][j];
+                    bsum[t] += (float)a1[j];
+                }
+#pragma unroll
+                for (int u = 0; u < KT; ++u) acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1[u], acc[t][u], 0, 0, 0);
             }
         }
         if constexpr (PF) {
@@ -298,9 +332,9 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_b3_kernel(const float *__
             const int n = n0 + t * 32 + (v & 3) + 8 * (v >> 2) + 4 * half;
             if (n >= N) continue;
 #pragma unroll
-            for (int u = 0; u < KT; ++u) pw[(size_t)n * K + u * 32 + i] = acc[t][u][v];
+            for (int u = 0; u < KT; ++u) pw[(size_t)n * K + k0 + u * 32 + i] = acc[t][u][v];
         }
-        if (half == 0 && ncol[t])
+        if (half == 0 && ncol[t] && k0 == 0)
             part_b[(size_t)chunk * N + n0 + t * 32 + i] =
                 (red_b[0][t * 32 + i] + red_b[1][t * 32 + i]) + (red_b[2][t * 32 + i] + red_b[3][t * 32 + i]);
     }
@@ -348,7 +382,9 @@ __global__ __launch_bounds__(256) void linear_wgrad_reduce_kernel(const float *_
 
 struct WgradPlan {
     int kt, ntw, ngroups, chunks;
+    int kz;       // blocks of kt * 32 input columns (grid z): 1, or 2 for the one-product K = 192 plan
     long long rows_per_block;
+    bool x1;      // SO_LINEAR_BF16X1: the one-product (P = 1) instance of the bf16 kernel
 };
 
 // round 3: the bf16 three-way-split kernels (same results to float32 rounding); SELFOCC_LINEAR_B3=0 keeps the f32-MFMA ones
@@ -357,17 +393,28 @@ bool so_wgrad_b3() {
     return on;
 }
 
-bool so_wgrad_plan(long long T, int N, int K, WgradPlan &p) {
+bool so_wgrad_flags_ok(uint32_t flags) { return !(flags & ~(uint32_t)SO_LINEAR_BF16X1); }
+
+bool so_wgrad_plan(long long T, int N, int K, WgradPlan &p, uint32_t flags = 0) {
     static const int env_chunks = getenv("SELFOCC_WGRAD_CHUNKS") ? atoi(getenv("SELFOCC_WGRAD_CHUNKS")) : 0;     // dev A/B
-    const bool b3 = so_wgrad_b3();
+    // SO_LINEAR_BF16X1: always the bf16 kernel (its P = 1 instance), whatever SELFOCC_LINEAR_B3 says and at K = 128 too — the
+    // f32-MFMA kernel never serves a flagged launch.  Its tile rows are the default bf16 plan's; K = 128 takes K = 96's rule.
+    // NTW is never above the default plan's for the same shape, so the plan never has more chunks: selfocc_linear_wgrad_workspace
+    // is a valid upper bound for a flagged launch (tests/test_linear_bf16_cpu.py sweeps it).
+    p.x1 = (flags & SO_LINEAR_BF16X1) != 0;
+    p.kz = 1;
+    const bool b3 = p.x1 || so_wgrad_b3();
     // tile rows of dY per wave (NTW).  bf16x3 kernels, K = 96: one or two (round 3, scripts/micro/wgrad_bench.py: N <= 96 had
     // 128 blocks = one wave on half of the SIMDs with three; 40 -> 28 us at 66 049 x 96 x 96, 108 -> 84 us at 153 000 x 288 x 96
     // with two); K = 192: one (222 registers; 66 -> 44 us at 78 899 x 96 x 192); K = 128 stays on the f32-MFMA kernel
     if (K == 96) { p.kt = 3; p.ntw = b3 ? ((N <= 96 || T < 16384) ? 1 : 2) : 3; }
+    // one-product K = 192: two halves of three column tiles (grid z), one tile row as the default's K = 192 plan has — so the
+    // chunks, and with them the workspace, are the default plan's
+    else if (K == 192 && p.x1) { p.kt = 3; p.ntw = 1; p.kz = 2; }
     else if (K == 192) { p.kt = 6; p.ntw = b3 ? 1 : 2; }
     else if (K == 32) { p.kt = 1; p.ntw = 4; }
     else if (K == 64) { p.kt = 2; p.ntw = b3 ? 2 : 4; }
-    else if (K == 128) { p.kt = 4; p.ntw = 3; }
+    else if (K == 128) { p.kt = 4; p.ntw = p.x1 ? ((N <= 96 || T < 16384) ? 1 : 2) : 3; }
     else return false;
     if (T < 1 || N < 1 || (long long)N * K >= (1LL << 30)) return false;
     const int nt = (N + 31) / 32;
@@ -391,10 +438,14 @@ extern "C" int selfocc_linear_wgrad_supported(int64_t T, int32_t N, int32_t K) {
     return so_wgrad_plan(T, N, K, p) ? 1 : 0;
 }
 
-extern "C" size_t selfocc_linear_wgrad_workspace(int64_t T, int32_t N, int32_t K) {
+extern "C" size_t selfocc_linear_wgrad_workspace_flags(int64_t T, int32_t N, int32_t K, uint32_t flags) {
     WgradPlan p;
-    if (!so_wgrad_plan(T, N, K, p)) return 0;
+    if (!so_wgrad_flags_ok(flags) || !so_wgrad_plan(T, N, K, p, flags)) return 0;
     return (size_t)p.chunks * ((size_t)N * K + N) * sizeof(float);
+}
+
+extern "C" size_t selfocc_linear_wgrad_workspace(int64_t T, int32_t N, int32_t K) {
+    return selfocc_linear_wgrad_workspace_flags(T, N, K, 0);
 }
 
 // the chunk table: group g's rows in ceil(rows_g / rows_per_block) chunks of the plan's rows_per_block (none for an empty group)
@@ -411,20 +462,29 @@ static int so_wgrad_launch(const float *dy, const float *x, float *dw, float *db
                workspace_bytes, need);
     float *part_w = (float *)workspace, *part_b = part_w + (size_t)chunks * N * K;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)chunks, (unsigned)p.ngroups);
-    const bool b3 = so_wgrad_b3() && p.kt != 4;      // K = 128 stays on the f32-MFMA kernel
+    const dim3 grid((unsigned)chunks, (unsigned)p.ngroups, (unsigned)p.kz);
+    const bool b3 = p.x1 || (so_wgrad_b3() && p.kt != 4);      // default: K = 128 stays on the f32-MFMA kernel
     bool launched = chunks == 0;
     // one (kernel, KT, NTW) of the list below: launched when it is the plan's
     auto pass = [&](auto B3, auto KT, auto NTW) {
-        if (launched || b3 != B3 || p.kt != KT || p.ntw != NTW) return;
+        if (launched || p.x1 || b3 != B3 || p.kt != KT || p.ntw != NTW) return;
         launched = true;
         so_with_const<bool, true, false>(grouped, [&](auto GRP) {
             if constexpr (B3)
-                hipLaunchKernelGGL((linear_wgrad_b3_kernel<KT, NTW, GRP>), grid, dim3(256), 0, st, dy, x, part_w, part_b, T, N, K,
+                hipLaunchKernelGGL((linear_wgrad_b3_kernel<KT, NTW, GRP, 3>), grid, dim3(256), 0, st, dy, x, part_w, part_b, T, N, K,
                                    p.rows_per_block, gr);
             else
                 hipLaunchKernelGGL((linear_wgrad_kernel<KT, NTW, GRP>), grid, dim3(256), 0, st, dy, x, part_w, part_b, T, N, K,
                                    p.rows_per_block, gr);
+        });
+    };
+    // ... and of the one-product instances (SO_LINEAR_BF16X1)
+    auto pass1 = [&](auto KT, auto NTW) {
+        if (launched || !p.x1 || p.kt != KT || p.ntw != NTW) return;
+        launched = true;
+        so_with_const<bool, true, false>(grouped, [&](auto GRP) {
+            hipLaunchKernelGGL((linear_wgrad_b3_kernel<KT, NTW, GRP, 1>), grid, dim3(256), 0, st, dy, x, part_w, part_b, T, N, K,
+                               p.rows_per_block, gr);
         });
     };
     // the (KT, NTW) pairs so_wgrad_plan can produce; only these are instantiated (the b3 kernel at 3 x 3 / 4 x 3 / 6 x 2
@@ -435,6 +495,8 @@ static int so_wgrad_launch(const float *dy, const float *x, float *dw, float *db
     pass(B3, so_int<3>{}, so_int<2>{}); pass(B3, so_int<6>{}, so_int<1>{});
     pass(F32, so_int<1>{}, so_int<4>{}); pass(F32, so_int<2>{}, so_int<4>{}); pass(F32, so_int<3>{}, so_int<3>{});
     pass(F32, so_int<4>{}, so_int<3>{}); pass(F32, so_int<6>{}, so_int<2>{});
+    pass1(so_int<1>{}, so_int<4>{}); pass1(so_int<2>{}, so_int<2>{}); pass1(so_int<3>{}, so_int<1>{}); pass1(so_int<3>{}, so_int<2>{});
+    pass1(so_int<4>{}, so_int<1>{}); pass1(so_int<4>{}, so_int<2>{});
     SO_REQUIRE(launched, "linear_wgrad: no kernel for the plan's KT = %d, NTW = %d", p.kt, p.ntw);
     const int NK = N * K;
     hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((unsigned)((NK + N + 63) / 64), (unsigned)gr.n), dim3(256), 0, st, part_w,
@@ -442,10 +504,11 @@ static int so_wgrad_launch(const float *dy, const float *x, float *dw, float *db
     return so_launch_status();
 }
 
-extern "C" int selfocc_linear_wgrad(const float *dy, const float *x, float *dw, float *db, int64_t T, int32_t N,
-                                    int32_t K, void *workspace, size_t workspace_bytes, void *stream) {
+extern "C" int selfocc_linear_wgrad_flags(const float *dy, const float *x, float *dw, float *db, int64_t T, int32_t N, int32_t K,
+                                          void *workspace, size_t workspace_bytes, uint32_t flags, void *stream) {
     WgradPlan p;
-    SO_REQUIRE(so_wgrad_plan(T, N, K, p), "linear_wgrad: unsupported shape (T = %lld rows, N = %d, K = %d; K must be 32, 64, "
+    SO_REQUIRE(so_wgrad_flags_ok(flags), "linear_wgrad: unknown flags 0x%x (SO_LINEAR_BF16X1 is the only one)", flags);
+    SO_REQUIRE(so_wgrad_plan(T, N, K, p, flags), "linear_wgrad: unsupported shape (T = %lld rows, N = %d, K = %d; K must be 32, 64, "
                "96, 128 or 192)", (long long)T, N, K);
     so_group_table gr = {};
     gr.n = 1;
@@ -454,11 +517,18 @@ extern "C" int selfocc_linear_wgrad(const float *dy, const float *x, float *dw, 
     return so_wgrad_launch(dy, x, dw, db, T, N, K, p, gr, false, workspace, workspace_bytes, stream);
 }
 
+extern "C" int selfocc_linear_wgrad(const float *dy, const float *x, float *dw, float *db, int64_t T, int32_t N,
+                                    int32_t K, void *workspace, size_t workspace_bytes, void *stream) {
+    return selfocc_linear_wgrad_flags(dy, x, dw, db, T, N, K, workspace, workspace_bytes, 0, stream);
+}
+
 // the plan of the grouped pass: the ungrouped plan of all T rows (kernel choice, rows per chunk), chunks cut per group
-static int so_wgrad_grouped_plan(long long T, int N, int K, const so_row_groups &groups, WgradPlan &p, so_group_table &gr) {
+static int so_wgrad_grouped_plan(long long T, int N, int K, const so_row_groups &groups, WgradPlan &p, so_group_table &gr,
+                                 uint32_t flags) {
+    SO_REQUIRE(so_wgrad_flags_ok(flags), "linear_wgrad_grouped: unknown flags 0x%x (SO_LINEAR_BF16X1 is the only one)", flags);
     if (so_check_row_groups(groups, T, "linear_wgrad_grouped") < 0) return -1;
-    SO_REQUIRE(so_wgrad_plan(T > 0 ? T : 1, N, K, p), "linear_wgrad_grouped: unsupported shape (T = %lld rows, N = %d, K = %d; K must "
-               "be 32, 64, 96, 128 or 192)", T, N, K);
+    SO_REQUIRE(so_wgrad_plan(T > 0 ? T : 1, N, K, p, flags), "linear_wgrad_grouped: unsupported shape (T = %lld rows, N = %d, K = %d; "
+               "K must be 32, 64, 96, 128 or 192)", T, N, K);
     gr = so_wgrad_groups(groups, p);
     return 0;
 }
@@ -469,18 +539,29 @@ extern "C" int selfocc_linear_wgrad_grouped_supported(int64_t T, int32_t N, int3
     return so_wgrad_plan(T > 0 ? T : 1, N, K, p) ? 1 : 0;
 }
 
-extern "C" size_t selfocc_linear_wgrad_grouped_workspace(int64_t T, int32_t N, int32_t K, so_row_groups groups) {
+extern "C" size_t selfocc_linear_wgrad_grouped_workspace_flags(int64_t T, int32_t N, int32_t K, so_row_groups groups, uint32_t flags) {
     WgradPlan p;
     so_group_table gr;
-    if (so_wgrad_grouped_plan(T, N, K, groups, p, gr) < 0) return 0;
+    if (so_wgrad_grouped_plan(T, N, K, groups, p, gr, flags) < 0) return 0;
     const size_t chunks = (size_t)std::max(1, gr.unit_start[gr.n]);
     return chunks * ((size_t)N * K + N) * sizeof(float);
 }
 
-extern "C" int selfocc_linear_wgrad_grouped(const float *dy, const float *x, float *dw, float *db, int64_t T, int32_t N, int32_t K,
-                                            so_row_groups groups, void *workspace, size_t workspace_bytes, void *stream) {
+extern "C" size_t selfocc_linear_wgrad_grouped_workspace(int64_t T, int32_t N, int32_t K, so_row_groups groups) {
+    return selfocc_linear_wgrad_grouped_workspace_flags(T, N, K, groups, 0);
+}
+
+extern "C" int selfocc_linear_wgrad_grouped_flags(const float *dy, const float *x, float *dw, float *db, int64_t T, int32_t N, int32_t K,
+                                                  so_row_groups groups, void *workspace, size_t workspace_bytes, uint32_t flags,
+                                                  void *stream) {
     WgradPlan p;
     so_group_table gr;
-    if (so_wgrad_grouped_plan(T, N, K, groups, p, gr) < 0) return -1;
+    if (so_wgrad_grouped_plan(T, N, K, groups, p, gr, flags) < 0) return -1;
     return so_wgrad_launch(dy, x, dw, db, T, N, K, p, gr, true, workspace, workspace_bytes, stream);
 }
+
+extern "C" int selfocc_linear_wgrad_grouped(const float *dy, const float *x, float *dw, float *db, int64_t T, int32_t N, int32_t K,
+                                            so_row_groups groups, void *workspace, size_t workspace_bytes, void *stream) {
+    return selfocc_linear_wgrad_grouped_flags(dy, x, dw, db, T, N, K, groups, workspace, workspace_bytes, 0, stream);
+}
+

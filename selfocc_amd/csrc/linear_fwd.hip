@@ -348,6 +348,13 @@ SO_DEVFN void so_split3(const float (&x)[8], bf16x8 &a1, bf16x8 &a2, bf16x8 &a3)
     }
 }
 
+// LINEAR_BF16 (SO_LINEAR_BF16X1, P = 1 below): the ONE plane of the opt-in one-product mode — the round-to-nearest-even bfloat16
+// of every value, the same (__bf16) conversion that makes the first plane of so_split3
+SO_DEVFN void so_round1(const float (&x)[8], bf16x8 &a1) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a1[j] = (__bf16)x[j];
+}
+
 // Epilogues of the b3 kernel.  Its MFMAs take the W fragment as the A operand and the x fragment as B, so the accumulator tile
 // is the TRANSPOSE of the one above: lane (r = l % 16, kq = l / 16) holds row r of the 16-row half and the four CONSECUTIVE
 // columns 16 t + 4 kq + j — a float4 per (lane, tile).  Twelve 16-byte stores per 32-row tile instead of forty-eight 4-byte
@@ -457,12 +464,15 @@ SO_DEVFN void so_linear_epilogue_t_hm(f32x4 (&acc)[NT16], const f32x4 (&bv)[NT16
     }
 }
 
+// P = planes per operand: 3 = the exact split above (six products); 1 = SO_LINEAR_BF16X1, ONE product of the bf16 roundings of
+// x and W (one conversion instead of the split, one MFMA instead of six, one W plane in LDS); k-walk, tiles and epilogues are P = 3's.
 template <int KS /* K / 32 */, bool LN, int NT /* 32-column tiles per block */, int WAVES, int H = 2 /* 16-row halves per wave tile */,
-          bool GRP = false>
+          bool GRP = false, int P = 3>
 __global__ __launch_bounds__(WAVES * 64, 2) void linear_fwd_b3_kernel(LinearFwdArgs a) {
+    static_assert(P == 3 || P == 1, "planes per operand");
     constexpr int TR = 16 * H;
     constexpr int K = 32 * KS, KPB = K + 8, NT16 = 2 * NT, THREADS = WAVES * 64, NCOL = 32 * NT;
-    extern __shared__ __attribute__((aligned(16))) __bf16 wb[];    // [3][NCOL][KPB]
+    extern __shared__ __attribute__((aligned(16))) __bf16 wb[];    // [P][NCOL][KPB]
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int n = lane & 15, kb = lane >> 4;
     const unsigned logical = so_lin_xcd_block();
@@ -482,11 +492,17 @@ __global__ __launch_bounds__(WAVES * 64, 2) void linear_fwd_b3_kernel(LinearFwdA
                 const float4 lo = ((const float4 *)(a.w + (size_t)(n0 + r) * K))[2 * k8], hi = ((const float4 *)(a.w + (size_t)(n0 + r) * K))[2 * k8 + 1];
                 v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
             }
-            bf16x8 w1, w2, w3;
-            so_split3(v, w1, w2, w3);
-            *(bf16x8 *)(wb + (size_t)r * KPB + 8 * k8) = w1;
-            *(bf16x8 *)(wb + (size_t)(NCOL + r) * KPB + 8 * k8) = w2;
-            *(bf16x8 *)(wb + (size_t)(2 * NCOL + r) * KPB + 8 * k8) = w3;
+            if constexpr (P == 3) {
+                bf16x8 w1, w2, w3;
+                so_split3(v, w1, w2, w3);
+                *(bf16x8 *)(wb + (size_t)r * KPB + 8 * k8) = w1;
+                *(bf16x8 *)(wb + (size_t)(NCOL + r) * KPB + 8 * k8) = w2;
+                *(bf16x8 *)(wb + (size_t)(2 * NCOL + r) * KPB + 8 * k8) = w3;
+            } else {
+                bf16x8 w1;
+                so_round1(v, w1);
+                *(bf16x8 *)(wb + (size_t)r * KPB + 8 * k8) = w1;
+            }
         }
     }
     __syncthreads();
@@ -560,37 +576,49 @@ __global__ __launch_bounds__(WAVES * 64, 2) void linear_fwd_b3_kernel(LinearFwdA
         // stamps: with the three ds_read_b128 of a group issued right in front of its MFMAs and the next k-step's ~100 split
         // instructions between the groups, the phase took >= 5 600 cycles for 216 MFMAs x 16 cycles
         const __bf16 *bbase = wb + (size_t)n * KPB + 8 * kb;
-        bf16x8 a1[KS][H], a2[KS][H], a3[KS][H];
+        bf16x8 a1[KS][H], a2[P == 3 ? KS : 1][H], a3[P == 3 ? KS : 1][H];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
-            for (int h = 0; h < H; ++h) so_split3(xr[h][ks], a1[ks][h], a2[ks][h], a3[ks][h]);
+            for (int h = 0; h < H; ++h) {
+                if constexpr (P == 3) so_split3(xr[h][ks], a1[ks][h], a2[ks][h], a3[ks][h]);
+                else so_round1(xr[h][ks], a1[ks][h]);
+            }
         }
         if (wt + wt_step < nwt) load_tile(wt + wt_step);
-        bf16x8 wq[2][3];
-        auto wfrag = [&](int g, bf16x8 (&dst)[3]) __attribute__((always_inline)) {
+        bf16x8 wq[2][P];
+        auto wfrag = [&](int g, bf16x8 (&dst)[P]) __attribute__((always_inline)) {
             const int ks = g / NT16, t = g - ks * NT16;
             const __bf16 *bp = bbase + (size_t)(16 * t) * KPB + 32 * ks;
-            dst[0] = *(const bf16x8 *)bp; dst[1] = *(const bf16x8 *)(bp + (size_t)NCOL * KPB);
-            dst[2] = *(const bf16x8 *)(bp + (size_t)2 * NCOL * KPB);
+            dst[0] = *(const bf16x8 *)bp;
+            if constexpr (P == 3) {
+                dst[1] = *(const bf16x8 *)(bp + (size_t)NCOL * KPB);
+                dst[2] = *(const bf16x8 *)(bp + (size_t)2 * NCOL * KPB);
+            }
         };
         wfrag(0, wq[0]);
 #pragma unroll
         for (int g = 0; g < KS * NT16; ++g) {
             const int ks = g / NT16, t = g - ks * NT16;
             if (g + 1 < KS * NT16) wfrag(g + 1, wq[(g + 1) & 1]);
-            const bf16x8 b1 = wq[g & 1][0], b2 = wq[g & 1][1], b3 = wq[g & 1][2];
+            if constexpr (P == 3) {
+                const bf16x8 b1 = wq[g & 1][0], b2 = wq[g & 1][1], b3 = wq[g & 1][2];
 #pragma unroll
-            for (int h = 0; h < H; ++h) {      // small terms first
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1, a3[ks][h], acc[h][t], 0, 0, 0);
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b3, a1[ks][h], acc[h][t], 0, 0, 0);
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b2, a2[ks][h], acc[h][t], 0, 0, 0);
-            }
+                for (int h = 0; h < H; ++h) {      // small terms first
+                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1, a3[ks][h], acc[h][t], 0, 0, 0);
+                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b3, a1[ks][h], acc[h][t], 0, 0, 0);
+                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b2, a2[ks][h], acc[h][t], 0, 0, 0);
+                }
 #pragma unroll
-            for (int h = 0; h < H; ++h) {
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1, a2[ks][h], acc[h][t], 0, 0, 0);
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b2, a1[ks][h], acc[h][t], 0, 0, 0);
-                acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1, a1[ks][h], acc[h][t], 0, 0, 0);
+                for (int h = 0; h < H; ++h) {
+                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1, a2[ks][h], acc[h][t], 0, 0, 0);
+                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b2, a1[ks][h], acc[h][t], 0, 0, 0);
+                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1, a1[ks][h], acc[h][t], 0, 0, 0);
+                }
+            } else {
+                const bf16x8 b1 = wq[g & 1][0];
+#pragma unroll
+                for (int h = 0; h < H; ++h) acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1, a1[ks][h], acc[h][t], 0, 0, 0);
             }
         }
 #ifdef SO_LIN_TRACE
@@ -646,9 +674,11 @@ __global__ __launch_bounds__(WAVES * 64, 2) void linear_fwd_b3_kernel(LinearFwdA
 //      the MFMAs of the step leave room for).  No staging, no barriers: the first version of this kernel staged 96-wide chunks
 //      of W through LDS and was a chain of load -> barrier -> stage -> barrier -> MFMA latencies (63 us at 66 049 x 384 x 96
 //      where the dy stream takes 16).
+// P = 1 (SO_LINEAR_BF16X1): the one plane [column c < K][k < Npad] of bf16-rounded W^T, a third of the workspace.
+template <int P = 3>
 __global__ __launch_bounds__(256) void linear_dgrad_split_kernel(const float *w, __bf16 *planes, int N, int K, int Npad) {
     w += (size_t)blockIdx.y * N * K;                          // blockIdx.y: row group (its own W and planes)
-    planes += (size_t)blockIdx.y * 3 * K * Npad;
+    planes += (size_t)blockIdx.y * P * K * Npad;
     const int nk8 = Npad / 8;
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < K * nk8; idx += gridDim.x * 256) {
         const int k8 = idx / K, c = idx - k8 * K;                 // consecutive threads: consecutive columns (coalesced reads)
@@ -658,12 +688,18 @@ __global__ __launch_bounds__(256) void linear_dgrad_split_kernel(const float *w,
             const int kk = 8 * k8 + j;
             v[j] = kk < N ? w[(size_t)kk * K + c] : 0.0f;
         }
-        bf16x8 w1, w2, w3;
-        so_split3(v, w1, w2, w3);
         const size_t o = (size_t)c * Npad + 8 * k8, ps = (size_t)K * Npad;
-        *(bf16x8 *)(planes + o) = w1;
-        *(bf16x8 *)(planes + ps + o) = w2;
-        *(bf16x8 *)(planes + 2 * ps + o) = w3;
+        if constexpr (P == 3) {
+            bf16x8 w1, w2, w3;
+            so_split3(v, w1, w2, w3);
+            *(bf16x8 *)(planes + o) = w1;
+            *(bf16x8 *)(planes + ps + o) = w2;
+            *(bf16x8 *)(planes + 2 * ps + o) = w3;
+        } else {
+            bf16x8 w1;
+            so_round1(v, w1);
+            *(bf16x8 *)(planes + o) = w1;
+        }
     }
 }
 
@@ -681,11 +717,14 @@ struct LinearDgradArgs {
 // Before the MFMAs of item i every lane issues the dy loads of item i + 1, so that the HBM stream and the matrix pipe overlap
 // inside one wave; the chunk's planes are copied from L2 between two barriers, which the CU's other block (60 KB of LDS each)
 // covers with its MFMAs.
-template <bool GRP>
+template <bool GRP, int P = 3>
 __global__ __launch_bounds__(256) void linear_dgrad_b3_kernel(LinearDgradArgs a) {
+    static_assert(P == 3 || P == 1, "planes per operand");
     constexpr int KC = 96, KS = 3, KPB = KC + 8, NT16 = 6, NCOL = 96, WAVES = 4, THREADS = 256;
-    constexpr int NST = (3 * NCOL * (KC / 8) + THREADS - 1) / THREADS;     // 16-byte staging copies per thread and chunk: 14
-    extern __shared__ __attribute__((aligned(16))) __bf16 wb[];            // [3][NCOL][KPB]
+    constexpr int NRUN = P * NCOL * (KC / 8);                              // 16-byte runs of a chunk's planes
+    constexpr int NST = (NRUN + THREADS - 1) / THREADS;                    // staging copies per thread and chunk: 14 (P = 1: 5)
+    constexpr int NB = P == 3 ? 7 : NST;                                   // ... in flight together
+    extern __shared__ __attribute__((aligned(16))) __bf16 wb[];            // [P][NCOL][KPB]
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int n = lane & 15, kb = lane >> 4;
     const unsigned logical = so_lin_xcd_block();
@@ -745,28 +784,34 @@ __global__ __launch_bounds__(256) void linear_dgrad_b3_kernel(LinearDgradArgs a)
                         const int kk = 8 * k8 + j;
                         v[j] = kk < a.N ? a.w[(size_t)kk * a.K + n0 + r] : 0.0f;
                     }
-                    bf16x8 w1, w2, w3;
-                    so_split3(v, w1, w2, w3);
-                    *(bf16x8 *)(wb + (size_t)r * KPB + 8 * k8) = w1;
-                    *(bf16x8 *)(wb + (size_t)(NCOL + r) * KPB + 8 * k8) = w2;
-                    *(bf16x8 *)(wb + (size_t)(2 * NCOL + r) * KPB + 8 * k8) = w3;
+                    if constexpr (P == 3) {
+                        bf16x8 w1, w2, w3;
+                        so_split3(v, w1, w2, w3);
+                        *(bf16x8 *)(wb + (size_t)r * KPB + 8 * k8) = w1;
+                        *(bf16x8 *)(wb + (size_t)(NCOL + r) * KPB + 8 * k8) = w2;
+                        *(bf16x8 *)(wb + (size_t)(2 * NCOL + r) * KPB + 8 * k8) = w3;
+                    } else {
+                        bf16x8 w1;
+                        so_round1(v, w1);
+                        *(bf16x8 *)(wb + (size_t)r * KPB + 8 * k8) = w1;
+                    }
                 }
             } else
-            // the chunk's planes: 3 x 96 x 12 16-byte runs, straight copies (L2 hits: every block of the chip reads the same)
+            // the chunk's planes: P x 96 x 12 16-byte runs, straight copies (L2 hits: every block of the chip reads the same)
 #pragma unroll 2
-            for (int j0 = 0; j0 < NST; j0 += 7) {
-                bf16x8 sv[7];
-                int so[7];
+            for (int j0 = 0; j0 < NST; j0 += NB) {
+                bf16x8 sv[NB];
+                int so[NB];
 #pragma unroll
-                for (int j = 0; j < 7; ++j) {
-                    const int idx = min((int)threadIdx.x + (j0 + j) * THREADS, 3 * NCOL * (KC / 8) - 1);
+                for (int j = 0; j < NB; ++j) {
+                    const int idx = min((int)threadIdx.x + (j0 + j) * THREADS, NRUN - 1);
                     const int pl = idx / (NCOL * (KC / 8)), rem = idx - pl * (NCOL * (KC / 8));
                     const int r = rem / (KC / 8), k8 = rem - r * (KC / 8);
                     sv[j] = *(const bf16x8 *)(a.planes + pl * ps + (size_t)(n0 + r) * a.Npad + c * KC + 8 * k8);
                     so[j] = (pl * NCOL + r) * KPB + 8 * k8;
                 }
 #pragma unroll
-                for (int j = 0; j < 7; ++j) *(bf16x8 *)(wb + so[j]) = sv[j];      // (the clamped tail rewrites the last run)
+                for (int j = 0; j < NB; ++j) *(bf16x8 *)(wb + so[j]) = sv[j];      // (the clamped tail rewrites the last run)
             }
             __syncthreads();
         }
@@ -788,25 +833,37 @@ __global__ __launch_bounds__(256) void linear_dgrad_b3_kernel(LinearDgradArgs a)
         const __bf16 *bbase = wb + (size_t)n * KPB + 8 * kb;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            bf16x8 a1[2], a2[2], a3[2];
-            so_split3(xc[0][ks], a1[0], a2[0], a3[0]);
-            so_split3(xc[1][ks], a1[1], a2[1], a3[1]);
+            if constexpr (P == 3) {
+                bf16x8 a1[2], a2[2], a3[2];
+                so_split3(xc[0][ks], a1[0], a2[0], a3[0]);
+                so_split3(xc[1][ks], a1[1], a2[1], a3[1]);
 #pragma unroll
-            for (int t = 0; t < NT16; ++t) {
-                const __bf16 *bp = bbase + (size_t)(16 * t) * KPB + 32 * ks;
-                const bf16x8 b1 = *(const bf16x8 *)bp, b2 = *(const bf16x8 *)(bp + (size_t)NCOL * KPB),
-                             b3 = *(const bf16x8 *)(bp + (size_t)2 * NCOL * KPB);
+                for (int t = 0; t < NT16; ++t) {
+                    const __bf16 *bp = bbase + (size_t)(16 * t) * KPB + 32 * ks;
+                    const bf16x8 b1 = *(const bf16x8 *)bp, b2 = *(const bf16x8 *)(bp + (size_t)NCOL * KPB),
+                                 b3 = *(const bf16x8 *)(bp + (size_t)2 * NCOL * KPB);
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {      // small terms first
-                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3[h], b1, acc[h][t], 0, 0, 0);
-                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[h], b3, acc[h][t], 0, 0, 0);
-                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2[h], b2, acc[h][t], 0, 0, 0);
+                    for (int h = 0; h < 2; ++h) {      // small terms first
+                        acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3[h], b1, acc[h][t], 0, 0, 0);
+                        acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[h], b3, acc[h][t], 0, 0, 0);
+                        acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2[h], b2, acc[h][t], 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2[h], b1, acc[h][t], 0, 0, 0);
+                        acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[h], b2, acc[h][t], 0, 0, 0);
+                        acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[h], b1, acc[h][t], 0, 0, 0);
+                    }
                 }
+            } else {
+                bf16x8 a1[2];
+                so_round1(xc[0][ks], a1[0]);
+                so_round1(xc[1][ks], a1[1]);
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2[h], b1, acc[h][t], 0, 0, 0);
-                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[h], b2, acc[h][t], 0, 0, 0);
-                    acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[h], b1, acc[h][t], 0, 0, 0);
+                for (int t = 0; t < NT16; ++t) {
+                    const bf16x8 b1 = *(const bf16x8 *)(bbase + (size_t)(16 * t) * KPB + 32 * ks);
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[h], b1, acc[h][t], 0, 0, 0);
                 }
             }
         }
@@ -895,6 +952,41 @@ static int so_linear_fwd_launch(const float *x, const float *w, const float *bia
         // round 3: the bf16 three-way-split kernel (same results to float32 rounding, 2.67 x fewer matrix-pipe cycles);
         // SELFOCC_LINEAR_B3=0 keeps the f32-MFMA kernel (A/B)
         static const bool b3_env = !(getenv("SELFOCC_LINEAR_B3") && atoi(getenv("SELFOCC_LINEAR_B3")) == 0);
+        // SO_LINEAR_BF16X1: ALWAYS a one-product (P = 1) instance of the b3 kernel, whatever the shape and SELFOCC_LINEAR_B3 say —
+        // what the flag computes must not depend on the shape through the dispatch, so the f32-MFMA kernel never serves it.  The
+        // tiles are the default's where the default runs the b3 kernel (K = 192: eight waves, 16 rows; else four waves, 16 rows
+        // for N <= 192 and 32 above); the shapes it sends to the f32-MFMA kernel take the same rule.  One plane is 13 - 38 KB of
+        // LDS, so two blocks per CU fit at every K.
+        if (flags & SO_LINEAR_BF16X1) {
+            const size_t lds_x1 = (size_t)nt * 32 * (K + 8) * 2;
+            const bool k192 = K == 192, half_tiles = k192 || N <= 192;
+            const int waves = k192 ? 8 : 4;
+            const long long nwt1 = half_tiles ? (T + 15) / 16 : (T + 31) / 32;
+            long long groups1 = std::max(1LL, 256LL * (k192 ? 1 : 2) / a.ncb);
+            groups1 = std::min(groups1, (nwt1 + waves - 1) / waves);
+            a.groups = (int)groups1;
+            const long long nblk1 = deal(groups1, half_tiles ? 16 : 32, waves) * a.ncb;
+            so_with_const<int, 1, 2, 3>(nt, [&](auto NT) {
+                so_with_const<bool, true, false>(ln, [&](auto LN) {
+                    so_with_const<bool, true, false>(grouped, [&](auto GRP) {
+                        if (k192) {
+                            so_launch_lds<linear_fwd_b3_kernel<6, LN, NT, 8, 1, GRP, 1>>(dim3((unsigned)nblk1), dim3(512), lds_x1,
+                                                                                         160 * 1024 - 2048, st, a);
+                            return;
+                        }
+                        so_with_const<int, 32, 64, 96, 128>(K, [&](auto KK) {
+                            if (half_tiles)
+                                so_launch_lds<linear_fwd_b3_kernel<KK / 32, LN, NT, 4, 1, GRP, 1>>(dim3((unsigned)nblk1), dim3(256), lds_x1,
+                                                                                                   160 * 1024 - 2048, st, a);
+                            else if constexpr (!LN)      // (the LayerNorm epilogue is one column block: N <= 96, half tiles)
+                                so_launch_lds<linear_fwd_b3_kernel<KK / 32, LN, NT, 4, 2, GRP, 1>>(dim3((unsigned)nblk1), dim3(256), lds_x1,
+                                                                                                   160 * 1024 - 2048, st, a);
+                        });
+                    });
+                });
+            });
+            continue;
+        }
         // where it pays (measured inside the eval encoder, profiles/r3_h_*): enough 32-row tiles per block to amortise the
         // three-plane split of W at block start (the 6 - 8 k-row zh / wz planes at N = 96 ran 17 vs 9 us); K = 192 has its own
         // launch above (round 6: 78 899 x 192 -> 96 with residual + LayerNorm 50.2 -> 37.3 us, plain 39.4 -> 31.0 us against
@@ -1020,22 +1112,33 @@ extern "C" size_t selfocc_linear_dgrad_workspace(int32_t N, int32_t K) {
     return (size_t)3 * K * ((N + 95) / 96 * 96) * 2;
 }
 
+// SO_LINEAR_BF16X1: one plane of W^T instead of three
+extern "C" size_t selfocc_linear_dgrad_workspace_flags(int32_t N, int32_t K, uint32_t flags) {
+    if (flags & ~(uint32_t)SO_LINEAR_BF16X1) return 0;
+    return selfocc_linear_dgrad_workspace(N, K) / ((flags & SO_LINEAR_BF16X1) ? 3 : 1);
+}
+
 static int so_linear_dgrad_launch(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K, void *workspace,
-                                  int64_t workspace_bytes, void *stream, const so_row_groups *row_groups) {
+                                  int64_t workspace_bytes, void *stream, const so_row_groups *row_groups, uint32_t flags = 0) {
     const bool grouped = row_groups != nullptr;
     const int G = grouped ? row_groups->n_groups : 1;
+    const bool x1 = (flags & SO_LINEAR_BF16X1) != 0;
+    const int64_t need = (int64_t)(G * selfocc_linear_dgrad_workspace_flags(N, K, flags));
     SO_REQUIRE(dy && w && dx && workspace, "linear_dgrad: NULL pointer");
-    SO_REQUIRE(workspace_bytes >= (int64_t)(G * selfocc_linear_dgrad_workspace(N, K)), "linear_dgrad: workspace of %lld bytes, need %lld",
-               (long long)workspace_bytes, (long long)(G * selfocc_linear_dgrad_workspace(N, K)));
+    SO_REQUIRE(workspace_bytes >= need, "linear_dgrad: workspace of %lld bytes, need %lld", (long long)workspace_bytes, (long long)need);
     SO_REQUIRE(((uintptr_t)workspace & 15) == 0, "linear_dgrad: workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int Npad = (N + 95) / 96 * 96;
+    const int planes = x1 ? 1 : 3;
     LinearDgradArgs a;
     a.gr = LinGroups{};
     a.dy = dy; a.planes = (const __bf16 *)workspace; a.w = w; a.dx = dx; a.T = T; a.N = N; a.K = K; a.Npad = Npad;
     if (Npad == 96) a.planes = nullptr;        // one chunk: the main kernel splits W while it stages it (one launch less)
-    else hipLaunchKernelGGL(linear_dgrad_split_kernel, dim3((unsigned)std::min(256, (K * (Npad / 8) + 255) / 256), (unsigned)G),
-                            dim3(256), 0, st, w, (__bf16 *)workspace, N, K, Npad);
+    else {
+        const dim3 sgrid((unsigned)std::min(256, (K * (Npad / 8) + 255) / 256), (unsigned)G);
+        if (x1) hipLaunchKernelGGL(linear_dgrad_split_kernel<1>, sgrid, dim3(256), 0, st, w, (__bf16 *)workspace, N, K, Npad);
+        else hipLaunchKernelGGL(linear_dgrad_split_kernel<3>, sgrid, dim3(256), 0, st, w, (__bf16 *)workspace, N, K, Npad);
+    }
     const int ncb = K / 96;
     const long long nwt = (T + 31) / 32;
     static const int percu = getenv("SELFOCC_DGRAD_PERCU") ? atoi(getenv("SELFOCC_DGRAD_PERCU")) : 2;      // dev A/B
@@ -1044,22 +1147,29 @@ static int so_linear_dgrad_launch(const float *dy, const float *w, float *dx, in
     a.groups = (int)groups;
     if (grouped) {      // the row blocks dealt to the groups in proportion to their 32-row tiles, as in so_linear_fwd_launch
         a.gr.w_stride = (long long)N * K;
-        a.gr.planes_stride = (long long)3 * K * Npad;
+        a.gr.planes_stride = (long long)planes * K * Npad;
         a.gr.t = so_deal_row_blocks(*row_groups, groups, 32, 4);
         groups = a.gr.t.unit_start[G];
     }
-    const size_t lds = (size_t)3 * 96 * (96 + 8) * 2;
+    const size_t lds = (size_t)planes * 96 * (96 + 8) * 2;
     so_with_const<bool, true, false>(grouped, [&](auto GRP) {
-        so_launch_lds<linear_dgrad_b3_kernel<GRP>>(dim3((unsigned)(groups * ncb)), dim3(256), lds, 160 * 1024 - 256, st, a);
+        if (x1) so_launch_lds<linear_dgrad_b3_kernel<GRP, 1>>(dim3((unsigned)(groups * ncb)), dim3(256), lds, 160 * 1024 - 256, st, a);
+        else so_launch_lds<linear_dgrad_b3_kernel<GRP, 3>>(dim3((unsigned)(groups * ncb)), dim3(256), lds, 160 * 1024 - 256, st, a);
     });
     return so_launch_status();
 }
 
-extern "C" int selfocc_linear_dgrad(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K, void *workspace,
-                                    int64_t workspace_bytes, void *stream) {
+extern "C" int selfocc_linear_dgrad_flags(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K, void *workspace,
+                                          int64_t workspace_bytes, uint32_t flags, void *stream) {
+    SO_REQUIRE(!(flags & ~(uint32_t)SO_LINEAR_BF16X1), "linear_dgrad: unknown flags 0x%x (SO_LINEAR_BF16X1 is the only one)", flags);
     SO_REQUIRE(so_linear_dgrad_ok(T, N, K), "linear_dgrad: unsupported shape (T = %lld rows, N = %d reduced features (multiple of 8, "
                "<= 4096), K = %d input features (96, 192, 288 or 384))", (long long)T, N, K);
-    return so_linear_dgrad_launch(dy, w, dx, T, N, K, workspace, workspace_bytes, stream, nullptr);
+    return so_linear_dgrad_launch(dy, w, dx, T, N, K, workspace, workspace_bytes, stream, nullptr, flags);
+}
+
+extern "C" int selfocc_linear_dgrad(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K, void *workspace,
+                                    int64_t workspace_bytes, void *stream) {
+    return selfocc_linear_dgrad_flags(dy, w, dx, T, N, K, workspace, workspace_bytes, 0, stream);
 }
 
 extern "C" int selfocc_linear_dgrad_grouped_supported(int64_t T, int32_t N, int32_t K, so_row_groups groups) {
@@ -1072,11 +1182,23 @@ extern "C" size_t selfocc_linear_dgrad_grouped_workspace(int32_t N, int32_t K, s
     return (size_t)groups.n_groups * selfocc_linear_dgrad_workspace(N, K);
 }
 
-extern "C" int selfocc_linear_dgrad_grouped(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K,
-                                            so_row_groups groups, void *workspace, int64_t workspace_bytes, void *stream) {
+extern "C" size_t selfocc_linear_dgrad_grouped_workspace_flags(int32_t N, int32_t K, so_row_groups groups, uint32_t flags) {
+    if (groups.n_groups < 1 || groups.n_groups > 8) return 0;
+    return (size_t)groups.n_groups * selfocc_linear_dgrad_workspace_flags(N, K, flags);
+}
+
+extern "C" int selfocc_linear_dgrad_grouped_flags(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K,
+                                                  so_row_groups groups, void *workspace, int64_t workspace_bytes, uint32_t flags,
+                                                  void *stream) {
+    SO_REQUIRE(!(flags & ~(uint32_t)SO_LINEAR_BF16X1), "linear_dgrad_grouped: unknown flags 0x%x (SO_LINEAR_BF16X1 is the only one)", flags);
     if (so_check_row_groups(groups, T, "linear_dgrad_grouped") < 0) return -1;
     SO_REQUIRE(so_linear_dgrad_ok(T > 0 ? T : 1, N, K), "linear_dgrad_grouped: unsupported shape (T = %lld rows, N = %d reduced features "
                "(multiple of 8, <= 4096), K = %d input features (96, 192, 288 or 384))", (long long)T, N, K);
     if (T == 0) return 0;
-    return so_linear_dgrad_launch(dy, w, dx, T, N, K, workspace, workspace_bytes, stream, &groups);
+    return so_linear_dgrad_launch(dy, w, dx, T, N, K, workspace, workspace_bytes, stream, &groups, flags);
+}
+
+extern "C" int selfocc_linear_dgrad_grouped(const float *dy, const float *w, float *dx, int64_t T, int32_t N, int32_t K,
+                                            so_row_groups groups, void *workspace, int64_t workspace_bytes, void *stream) {
+    return selfocc_linear_dgrad_grouped_flags(dy, w, dx, T, N, K, groups, workspace, workspace_bytes, 0, stream);
 }

@@ -141,6 +141,25 @@ DGRAD_MIN_ROWS = 32768      # below: too few 32-row tiles for 1 024 SIMDs, the v
 # selfocc_linear_fwd (csrc/linear_fwd.hip); False: torch.addmm + separate elementwise kernels (A/B)
 FUSED_LINEAR_FWD = os.environ.get('SELFOCC_FUSED_LINEAR', '1') == '1'
 LINEAR_FWD_MIN_ROWS = 1024
+# True: every tall-Linear pass that takes the HIP route (forward, input gradient, weight / bias gradient; ungrouped, head-major
+# and grouped) computes ONE bf16 product of the round-to-nearest-even bfloat16 of its two operands instead of the exact
+# three-way split — float32 accumulation, bias / residual / LayerNorm and outputs (C ABI: SO_LINEAR_BF16X1; csrc/linear_fwd.hip,
+# csrc/linear.hip).  A sixth of the MFMAs and no split arithmetic for about three digits (2^-9 relative per operand), so it is
+# opt-in like VALUE_BF16 below: the default reproduces the reference to 1e-4.  It changes supported HIP launches only — a
+# projection that stays on torch (few rows, an unsupported K, CPU, autocast) stays what it is.  env SELFOCC_LINEAR_BF16=1 sets it;
+# read at call time.  An autograd Function records the mode at forward time and its backward runs in that mode.
+LINEAR_BF16 = os.environ.get('SELFOCC_LINEAR_BF16', '0') == '1'
+LINEAR_BF16_CALLS = [0]            # tall-Linear launches made in the one-product mode (tests read this)
+
+
+def _bf16(mode=None):
+    """The mode keyword of ONE tall-Linear launch — from the switch, or from the mode a Function recorded at forward time: nothing
+    when it is off (the call is the one it always was), ``bf16=True`` when it is on, counted in LINEAR_BF16_CALLS."""
+    on = LINEAR_BF16 if mode is None else bool(mode)
+    if not on:
+        return {}
+    LINEAR_BF16_CALLS[0] += 1
+    return {'bf16': True}
 
 
 # inference: value_proj writes the head-major layout the MSDA kernels gather fastest from (selfocc_linear_fwd_heads: no
@@ -178,7 +197,7 @@ def value_proj_head_major(lins, value2d, nv, num_heads):
             for g, o in enumerate(outs):
                 o._so_grad_sink = (sink, g)
         return outs
-    return linear_fwd_heads(value2d, stack_rows(wb[0::2]), stack_rows(wb[1::2]), nv)
+    return linear_fwd_heads(value2d, stack_rows(wb[0::2]), stack_rows(wb[1::2]), nv, **_bf16())
 
 
 # training: the MSDA backward writes grad_value pixel-major straight into the row-major gradient of the (stacked) value
@@ -197,10 +216,11 @@ def _linear_fwd_ok(x2d, weight):
             and x2d.shape[0] >= LINEAR_FWD_MIN_ROWS and linear_fwd_supported(x2d.shape[0], weight.shape[0], x2d.shape[1]))
 
 
-def _tall_fwd(x, w, b, relu=False):
-    """relu?(x W^T + b) for (T, K) rows: one selfocc_linear_fwd launch when the shape qualifies, else torch.addmm"""
+def _tall_fwd(x, w, b, relu=False, bf16=None):
+    """relu?(x W^T + b) for (T, K) rows: one selfocc_linear_fwd launch when the shape qualifies, else torch.addmm.
+    ``bf16``: the mode of the launch (None: the LINEAR_BF16 switch)"""
     if FUSED_LINEAR_FWD and _linear_fwd_ok(x, w):
-        return linear_fwd(x, w, b, relu=relu)
+        return linear_fwd(x, w, b, relu=relu, **_bf16(bf16))
     y = torch.addmm(b, x, w.t()) if b is not None else x @ w.t()
     return torch.relu(y) if relu else y
 
@@ -224,7 +244,7 @@ def fused_linear(lin, x, relu=False, residual=None, norm=None, out=None):
         if out is not None and out.stride(-1) == 1:
             o2 = out.view(rows, N) if out.is_contiguous() else (out[0] if out.dim() == 3 and out.shape[0] == 1 else None)
         ln = (norm.weight, norm.bias, norm.eps) if norm is not None else None
-        y = linear_fwd(x2, lin.weight, lin.bias, relu=relu, residual=r2, ln=ln, out=o2)
+        y = linear_fwd(x2, lin.weight, lin.bias, relu=relu, residual=r2, ln=ln, out=o2, **_bf16())
         if o2 is not None:
             return out
         y = y.view(*lead, N)
@@ -245,24 +265,25 @@ def fused_linear(lin, x, relu=False, residual=None, norm=None, out=None):
     return y
 
 
-def _dgrad(dy, weight, sizes=None):
+def _dgrad(dy, weight, sizes=None, bf16=False):
     """dx = dy W — per row group with ``sizes`` (weight [G][N][K]) — on the HIP route where FUSED_DGRAD and the support query
-    allow it, else matmul"""
+    allow it (``bf16``: in the one-product mode), else matmul"""
     N, K = dy.shape[1], weight.shape[-1]
     hip = FUSED_DGRAD and dy.is_cuda and dy.dtype == torch.float32
     if sizes is None:
         if hip and dy.shape[0] >= DGRAD_MIN_ROWS and dgrad_supported(dy.shape[0], N, K):
-            return linear_dgrad(dy, weight)
+            return linear_dgrad(dy, weight, **_bf16(bf16))
         return dy @ weight
     if hip and linear_dgrad_grouped_supported(sizes, N, K):
-        return linear_dgrad_grouped(dy, weight, sizes)
+        return linear_dgrad_grouped(dy, weight, sizes, **_bf16(bf16))
     return torch.cat([d @ w for d, w in zip(torch.split(dy, sizes), weight.view(len(sizes), N, K))])
 
 
-def _tall_linear_backward(x, weight, dy, has_bias, need_dx=True, y=None, sizes=None):
+def _tall_linear_backward(x, weight, dy, has_bias, need_dx=True, y=None, sizes=None, bf16=False):
     """(dx, dW, db) of y = relu?(x W^T + b) for a row-major dy (shared by _TallLinear, _TallLinearHeads and _GroupedTallLinear).
     ``y``: the saved output of a ReLU epilogue, which masks dy.  ``sizes``: one weight per row group (weight [G][N][K]) through
-    the grouped kernels -> dW (G, N, K), db (G, N); MultiPlaneFFN.forward_cat has asked their support queries."""
+    the grouped kernels -> dW (G, N, K), db (G, N); MultiPlaneFFN.forward_cat has asked their support queries.  ``bf16``: the
+    mode the Function recorded at forward time — the HIP passes then run in the one-product mode (LINEAR_BF16)."""
     dy = dy.contiguous().to(x.dtype)
     if y is not None:
         dy = torch.ops.aten.threshold_backward(dy, y, 0)
@@ -270,8 +291,9 @@ def _tall_linear_backward(x, weight, dy, has_bias, need_dx=True, y=None, sizes=N
     if sizes is not None or (FUSED_WGRAD and dy.is_cuda and dy.dtype == torch.float32 and T > 0
                              and wgrad_supported(T, dy.shape[1], x.shape[1])):
         # one MFMA pass over dy and x for dW and db (csrc/linear.hip) instead of batched GEMMs + two reductions
-        dw, db = linear_wgrad(dy, x, has_bias) if sizes is None else linear_wgrad_grouped(dy, x, sizes, has_bias)
-        return (_dgrad(dy, weight, sizes) if need_dx else None), dw, db
+        dw, db = (linear_wgrad(dy, x, has_bias, **_bf16(bf16)) if sizes is None else
+                  linear_wgrad_grouped(dy, x, sizes, has_bias, **_bf16(bf16)))
+        return (_dgrad(dy, weight, sizes, bf16) if need_dx else None), dw, db
     G = max(1, min(256, T // 2048))  # ~2 k+ rows per batched GEMM: enough workgroups, small partial-sum tensor
     R = T // G                       # rows per batched GEMM
     Tp = R * G
@@ -291,7 +313,7 @@ def _tall_linear_backward(x, weight, dy, has_bias, need_dx=True, y=None, sizes=N
         db = db + dy[Tp:].sum(0)
     if Tp < T:
         dw = dw + dy[Tp:].t() @ x[Tp:]
-    return (_dgrad(dy, weight) if need_dx else None), dw, (db if has_bias else None)
+    return (_dgrad(dy, weight, None, bf16) if need_dx else None), dw, (db if has_bias else None)
 
 
 def stacked_view(params):
@@ -357,12 +379,15 @@ class _TallLinear(torch.autograd.Function):
     projection's epilogue and backward masks dy with the saved output (nn.ReLU(inplace=True) on the view returned here
     costs autograd a CopySlices: four extra 60 MB copies and a fill per layer)."""
 
-    # under torch.autocast (the reference's env amp=true) the op runs in float32 like the HIP ops around it
+    # under torch.autocast (the reference's env amp=true) the op takes float32 inputs like the HIP ops around it; mixed precision
+    # on these projections is the LINEAR_BF16 switch (SELFOCC_LINEAR_BF16=1: one bf16 product, float32 accumulation), which is
+    # independent of autocast.  The mode is recorded here, and backward runs in it whatever the switch says by then.
     @staticmethod
     @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
     def forward(ctx, x, relu, *wb):
         w, b = stack_rows(wb[0::2]), stack_rows(wb[1::2])
-        y = _tall_fwd(x, w, b, relu)
+        ctx.bf16 = LINEAR_BF16
+        y = _tall_fwd(x, w, b, relu, ctx.bf16)
         # the parameters themselves, not the stacked view: autograd's version check catches in-place updates before backward
         ctx.save_for_backward(x, y if relu else None, *wb[0::2])
         ctx.has_bias = b is not None
@@ -372,7 +397,7 @@ class _TallLinear(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type='cuda')
     def backward(ctx, dy):
         x, y, *ws = ctx.saved_tensors
-        dx, dw, db = _tall_linear_backward(x, stack_rows(ws), dy, ctx.has_bias, ctx.needs_input_grad[0], y)
+        dx, dw, db = _tall_linear_backward(x, stack_rows(ws), dy, ctx.has_bias, ctx.needs_input_grad[0], y, bf16=ctx.bf16)
         return (dx, None, *_split_rows(dw, db, [w.shape[0] for w in ws]))
 
 
@@ -389,7 +414,8 @@ class _TallLinearHeads(torch.autograd.Function):
         w, b = stack_rows(wb[0::2]), stack_rows(wb[1::2])
         ctx.save_for_backward(x, *wb[0::2])
         ctx.has_bias, ctx.sink = b is not None, sink
-        return tuple(linear_fwd_heads(x, w, b, nv).unbind(0))
+        ctx.bf16 = LINEAR_BF16                                     # backward runs in the mode of the forward
+        return tuple(linear_fwd_heads(x, w, b, nv, **_bf16(ctx.bf16)).unbind(0))
 
     @staticmethod
     @torch.amp.custom_bwd(device_type='cuda')
@@ -408,7 +434,7 @@ class _TallLinearHeads(torch.autograd.Function):
                 else:
                     dy[:, :, g].copy_(gy.permute(0, 2, 1, 3))      # one transposing copy per group
             dy2 = dy.view(B * nv, G * H * d)
-        dx, dw, db = _tall_linear_backward(x, stack_rows(ws), dy2, ctx.has_bias, ctx.needs_input_grad[0])
+        dx, dw, db = _tall_linear_backward(x, stack_rows(ws), dy2, ctx.has_bias, ctx.needs_input_grad[0], bf16=ctx.bf16)
         return (dx, None, None, *_split_rows(dw, db, [w.shape[0] for w in ws]))
 
 
@@ -451,7 +477,7 @@ class TallLinear(nn.Linear):
         if not torch.is_grad_enabled() and FUSED_LINEAR_FWD and x.is_cuda and not torch.is_autocast_enabled():
             x2 = x.reshape(rows, x.shape[-1])
             if _linear_fwd_ok(x2, self.weight):
-                return linear_fwd(x2, self.weight, self.bias).view(*x.shape[:-1], self.weight.shape[0])
+                return linear_fwd(x2, self.weight, self.bias, **_bf16()).view(*x.shape[:-1], self.weight.shape[0])
         return super().forward(x)
 
 
@@ -530,7 +556,8 @@ class _GroupedTallLinear(torch.autograd.Function):
     @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
     def forward(ctx, x, sizes, relu, *wb):
         w, b = stack_rows(wb[0::2]), stack_rows(wb[1::2])
-        y = linear_fwd_grouped(x, sizes, w, b, relu=relu)
+        ctx.bf16 = LINEAR_BF16                                     # backward runs in the mode of the forward
+        y = linear_fwd_grouped(x, sizes, w, b, relu=relu, **_bf16(ctx.bf16))
         # the parameters themselves, not the stacked view: autograd's version check catches in-place updates before backward
         ctx.save_for_backward(x, y if relu else None, *wb[0::2])
         ctx.sizes = list(sizes)
@@ -540,7 +567,7 @@ class _GroupedTallLinear(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type='cuda')
     def backward(ctx, dy):
         x, y, *ws = ctx.saved_tensors
-        dx, dw, db = _tall_linear_backward(x, stack_rows(ws), dy, True, ctx.needs_input_grad[0], y, ctx.sizes)
+        dx, dw, db = _tall_linear_backward(x, stack_rows(ws), dy, True, ctx.needs_input_grad[0], y, ctx.sizes, ctx.bf16)
         return (dx, None, None, *[t for g in range(len(ws)) for t in (dw[g], db[g])])
 
 
@@ -642,11 +669,12 @@ class MultiPlaneFFN(BaseModule):
         if torch.is_grad_enabled() or (self.training and (drop0.p > 0 or drop1.p > 0)):
             return None
         GROUPED_FFN_CALLS[0] += 1
-        h = linear_fwd_grouped(x2, sizes, stack_rows(wb0[0::2]), stack_rows(wb0[1::2]), relu=True)
+        h = linear_fwd_grouped(x2, sizes, stack_rows(wb0[0::2]), stack_rows(wb0[1::2]), relu=True, **_bf16())
         ln = None
         if norms is not None:
             ln = (stack_rows([n.weight for n in norms]), stack_rows([n.bias for n in norms]), norms[0].eps)
-        return linear_fwd_grouped(h, sizes, stack_rows(wb1[0::2]), stack_rows(wb1[1::2]), residual=idt, ln=ln).view(x.shape)
+        return linear_fwd_grouped(h, sizes, stack_rows(wb1[0::2]), stack_rows(wb1[1::2]), residual=idt, ln=ln,
+                                  **_bf16()).view(x.shape)
 
     def forward(self, tpv, identity=None, post_norm=None):
         """``post_norm``: the layer's next MultiPlaneNorm; plane p's result then goes through ``post_norm.norms[p]``"""
