@@ -297,6 +297,27 @@ typedef struct so_render_median_args {
 } so_render_median_args;
 int selfocc_render_median(const so_render_median_args *args, void *stream);
 
+/* Rendered surface normal of the march: sdfstudio's `normal_vis`, the `vis_normal` of the reference's render dicts
+ * (neus_head.py:358, 379, 414, 463).  Per ray, with w_i the per-sample `weights` and g_i = (gx, gy, gz)_i the per-sample `grad`
+ * selfocc_render_fwd writes for the same inputs (the same bits; `grad` is the trilinear SDF gradient of the sample's cell):
+ *     r_i  = sqrtf((gx*gx + gy*gy) + gz*gz)            float32, this order
+ *     d_i  = fmaxf(r_i, 1e-12f)                        F.normalize(p=2, eps=1e-12)
+ *     n_i  = (gx / d_i, gy / d_i, gz / d_i)            three IEEE divisions
+ *     N    = 0;  for i = 0 .. n_samples - 1 in sample order:  N = N + w_i * n_i     multiply, then add; no fused multiply-add
+ *     normal_vis = (N + 1.0f) / 2.0f                   (n_rays, 3)
+ * One launch of a kernel of its own (csrc/render_normal.hip): one ray per lane, canonical arithmetic whatever SO_FLAG_EXACT
+ * says, every ray marches all n_samples samples; a ray that misses the box by more than a cell (corners outside the volume read
+ * as 0: zero gradients) gives (0.5, 0.5, 0.5).  It reads the SDF volume only: of `fwd`, the mapping, sdf_vol, the ray fields, the sampling fields (aabb,
+ * near_plane, n_samples, sample_pos, jitter_mode, t_rand), inv_s and inv_s_dev are used; feat_vol, feat_dtype, feat_stride,
+ * n_rgb, n_sem, sh_deg, sh_act, bkgd_*, flags, sdf_brick and every output pointer of `fwd` are ignored.  Refused by name:
+ * args NULL, normal_vis NULL, n_samples < 1, n_rays < 0, and what selfocc_render_fwd refuses among the fields that are read.
+ * n_rays == 0 succeeds without a launch.  A new entry point: SELFOCC_ABI_VERSION is unchanged. */
+typedef struct so_render_normal_args {
+    so_render_args fwd;        /* inputs as for selfocc_render_fwd; outputs and feature fields ignored */
+    float *normal_vis;         /* (n_rays, 3) */
+} so_render_normal_args;
+int selfocc_render_normal(const so_render_normal_args *args, void *stream);
+
 /* NeuS hierarchical up-sampling: the coarse-to-fine sampler of NeuS (a declared restatement of upstream sdfstudio's NeuSSampler
  * + nerfstudio's PDFSampler).  Per ray, with the collider's tnear / tfar, S0 = fwd.n_samples,
  * M = n_importance, K = n_steps, m = M / K (integer division), one number r_k in [0, 1) per step (0.5 when u_rand is NULL):

@@ -80,6 +80,10 @@ class SoRenderMedianArgs(C.Structure):
     _fields_ = [("fwd", SoRenderArgs), ("median_depth", _p), ("median_index", _p)]
 
 
+class SoRenderNormalArgs(C.Structure):
+    _fields_ = [("fwd", SoRenderArgs), ("normal_vis", _p)]
+
+
 class SoRenderUpsampleArgs(C.Structure):
     _fields_ = [("fwd", SoRenderArgs), ("n_importance", _i), ("n_steps", _i), ("base_variance", _f),
                 ("u_rand", _p), ("edges", _p)]
@@ -212,6 +216,7 @@ SYMBOLS = {
     "selfocc_render_bwd": (C.c_int, [C.POINTER(SoRenderBwdArgs), _p]),
     "selfocc_render_bwd_ws_bytes": (C.c_size_t, [C.POINTER(SoRenderBwdArgs)]),
     "selfocc_render_median": (C.c_int, [C.POINTER(SoRenderMedianArgs), _p]),
+    "selfocc_render_normal": (C.c_int, [C.POINTER(SoRenderNormalArgs), _p]),
     "selfocc_render_upsample": (C.c_int, [C.POINTER(SoRenderUpsampleArgs), _p]),
     "selfocc_msda_fwd": (C.c_int, [C.POINTER(SoMsdaArgs), _p]),
     "selfocc_msda_bwd": (C.c_int, [C.POINTER(SoMsdaArgs), _p]),

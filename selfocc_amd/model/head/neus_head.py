@@ -29,7 +29,7 @@ from ...mapping import GridMeterMapping
 from ...occ import field_query, field_query_autograd, uniform_lattice
 from ...field import field_volume, field_volume_supported, field_volume_train_supported, FieldVolumeFunction
 from ...registry import HEADS
-from ...render import (SDFVolume, RaySet, RenderConfig, render_rays, render_rays_autograd, render_median_depth, upsample_edges,
+from ...render import (SDFVolume, RaySet, RenderConfig, render_rays, render_rays_autograd, render_median_depth, render_normal_vis, upsample_edges,
                        upsample_plan)
 from ..bricks import BaseModule, _TallLinear
 
@@ -400,8 +400,9 @@ class NeuSHead(BaseModule):
         self.exact_render = exact_render
         self.ray_shard = ray_shard          # shard the ray lattice over the ranks (selfocc_amd/dist.py)
         # render(): fill `vis_normal` (the fork's "normal_vis" = (sum_i w_i grad_i / |grad_i| + 1) / 2, consumed by the
-        # vis_* scripts only) from a chunked per-sample pass; off by default (zeros): eval_depth.py never reads it and
-        # the pass costs ~25 x the depth render
+        # vis_* scripts only) from one extra SDF-only launch (render_normal_vis); off by default
+        # (zeros, no launch): eval_depth.py never reads it, and the launch marches every sample canonically, which costs
+        # several times the skip-marched depth render
         self.render_normal = render_normal
         # render() / forward(): add `ms_depths_median` (nerfstudio's DepthRenderer(method="median"), the third depth target of
         # eval_depth.py) from one extra SDF-only launch (render_median_depth); off by default: no key, no launch
@@ -570,6 +571,7 @@ class NeuSHead(BaseModule):
         neus_head.py:329-385) is accepted and ignored — no per-sample tensor is materialised.
         ``median_depth`` (None: the head's ``return_median_depth``) adds ``ms_depths_median`` from one more launch."""
         want_median = self.return_median_depth if median_depth is None else bool(median_depth)
+        want_normal = bool(kwargs.get('vis_normal', self.render_normal))
         vol = self.model.field.volume
         assert vol is not None, "call prepare() (or forward) before render()"
         device = vol.sdf.device
@@ -591,20 +593,21 @@ class NeuSHead(BaseModule):
             loc = render_rays(vol, rays, cfg, bkgd_rays=bk)
             if want_median:
                 loc['median_depth'] = render_median_depth(vol, rays, cfg)['median_depth']
+            if want_normal:
+                loc['normal'] = render_normal_vis(vol, rays, cfg)
             out = {k: sdist.gather_rays(v, full).reshape(-1, *v.shape[1:]) for k, v in loc.items()}
         elif self.up_steps > 0:
-            out = self._render_upsampled(vol, rays, cfg, want_median)
+            out = self._render_upsampled(vol, rays, cfg, want_median, want_normal)
         else:
             bk = torch.rand(rays.n_rays, 3, device=device) if cfg.bkgd_mode == abi.BKGD_PER_RAY else None
             out = render_rays(vol, rays, cfg, bkgd_rays=bk)
             if want_median:
                 out['median_depth'] = render_median_depth(vol, rays, cfg)['median_depth']
+            if want_normal:
+                out['normal'] = render_normal_vis(vol, rays, cfg)
         shp = (1, num_cams, num_rays)
         rgb = out['rgb'].reshape(*shp, 3) if 'rgb' in out else torch.empty(*shp, 0, device=device)
-        if kwargs.get('vis_normal', self.render_normal) and not self._sharding(rays):
-            normal = self._normal_vis(vol, rays, cfg).reshape(*shp, 3)
-        else:
-            normal = torch.zeros(*shp, 3, device=device)
+        normal = out['normal'].reshape(*shp, 3) if want_normal else torch.zeros(*shp, 3, device=device)
         outputs = {'ms_depths': [out['depth'].reshape(shp)], 'ms_colors': [rgb],
                    'vis_normal': [normal], 'ms_accs': [out['acc'].reshape(shp)],
                    'ms_rays': pix}
@@ -638,7 +641,7 @@ class NeuSHead(BaseModule):
             return torch.cat(parts, 0)
         return subs, stitch
 
-    def _render_upsampled(self, vol, rays, cfg, want_median):
+    def _render_upsampled(self, vol, rays, cfg, want_median, want_normal=False):
         """render() with up-sampling: edges + march per row-block chunk, so that the edge buffer (4 (S_tot + 1) bytes per
         ray: 1.1 GB for the nuscenes_depth frame at 129 edges) stays below ``up_edge_bytes``"""
         n_chunks = -(-(rays.n_rays * (self.total_samples + 1) * 4) // self.up_edge_bytes)
@@ -650,6 +653,8 @@ class NeuSHead(BaseModule):
             o = render_rays(vol, sub, cfg, bkgd_rays=bk, edges=edges)
             if want_median:
                 o['median_depth'] = render_median_depth(vol, sub, cfg, edges=edges)['median_depth']
+            if want_normal:
+                o['normal'] = render_normal_vis(vol, sub, cfg, edges=edges)
             parts.append(o)
         return {k: stitch([p[k] for p in parts]) for k in parts[0]}
 

@@ -318,6 +318,59 @@ def median_depth_reference(weights, ts):
     return depth, j
 
 
+def render_normal_vis(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, t_rand=None, edges=None):
+    """Rendered surface normal of every ray in ONE launch (selfocc_render_normal, csrc/render_normal.hip): sdfstudio's
+    ``normal_vis``, the ``vis_normal`` of the reference's render dicts.  Equal, bit for bit, to ``normal_vis_reference``
+    applied to the ``weights`` / ``grad`` of ``render_rays(vol, rays, cfg, per_sample=True, want_grad_samples=True)``,
+    without materialising them.  Reads the SDF volume only (``vol.feat`` is not looked at), marches every sample in the
+    canonical order whatever ``cfg.exact``, and never reads anything back to the host (``cfg.inv_s_dev`` is honoured).
+    Returns (N, 3) float32; a ray that misses the box by more than a cell (zero gradients) gives (0.5, 0.5, 0.5)."""
+    if not vol.sdf.is_cuda:
+        raise RuntimeError("selfocc_amd.render_normal_vis needs CUDA(HIP) tensors: there is no CPU fallback")
+    cfg, t_rand = _with_edges(cfg, edges, t_rand, rays.n_rays)
+    # geometry only: the sampling fields and inv_s of `cfg`; its background, colour and march switches do not apply
+    geo = RenderConfig(aabb=cfg.aabb, n_samples=cfg.n_samples, inv_s=cfg.inv_s, inv_s_dev=cfg.inv_s_dev, near_plane=cfg.near_plane,
+                       sample_pos=cfg.sample_pos, jitter_mode=cfg.jitter_mode)
+    a, _out, _keep = marshal_render_args(SDFVolume(vol.mapping, vol.sdf), rays, geo, t_rand=t_rand, inputs_only=True)
+    na = abi.SoRenderNormalArgs()
+    na.fwd = a
+    N, dev = rays.n_rays, vol.sdf.device
+    out = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    if N == 0:          # nothing to launch (and an empty tensor has no address to pass)
+        return out
+    na.normal_vis = ptr(out)
+    check(lib().selfocc_render_normal(na, current_stream(dev)), "selfocc_render_normal")
+    return out
+
+
+def normal_vis_reference(weights, grad):
+    """The definition of the rendered normal, on CPU tensors or arrays: ``weights`` (n, S),
+    ``grad`` (n, S, 3), every step one float32 operation, the sum in sample order:
+        r_i = sqrt((gx*gx + gy*gy) + gz*gz);  d_i = max(r_i, 1e-12);  n_i = g_i / d_i
+        N = 0;  N = N + w_i * n_i  for i = 0 .. S - 1;   normal_vis = (N + 1) / 2
+    Returns (n, 3) float32, a tensor when ``weights`` is one.  A plain loop over the samples on purpose: a library sum adds in
+    another order.  numpy float32 on purpose: its square root and division are the correctly rounded ones, as the kernel's
+    are; torch.sqrt on the CPU is not on every build."""
+    import numpy as np
+    as_tensor = isinstance(weights, torch.Tensor)
+    host = lambda t: (t.detach().numpy() if isinstance(t, torch.Tensor) else np.asarray(t))
+    if as_tensor and (weights.is_cuda or grad.is_cuda):
+        raise RuntimeError("normal_vis_reference is the CPU definition: pass CPU tensors or arrays")
+    w, g = host(weights).astype(np.float32, copy=False), host(grad).astype(np.float32, copy=False)
+    assert w.ndim == 2 and g.shape == (*w.shape, 3) and w.shape[1] >= 1, \
+        f"weights {w.shape} / grad {g.shape}: need (n, S >= 1) / (n, S, 3)"
+    gx, gy, gz = g[..., 0], g[..., 1], g[..., 2]
+    r = np.sqrt((gx * gx + gy * gy) + gz * gz)
+    d = np.fmax(r, np.float32(1e-12))[..., None]              # fmaxf: a NaN norm gives the clamp
+    n = g / d
+    N = np.zeros((w.shape[0], 3), dtype=np.float32)
+    for i in range(w.shape[1]):
+        N = N + w[:, i, None] * n[:, i]
+    out = (N + np.float32(1.0)) / np.float32(2.0)
+    assert out.dtype == np.float32
+    return torch.from_numpy(np.ascontiguousarray(out)) if as_tensor else out
+
+
 UPSAMPLE_MAX_SAMPLES, UPSAMPLE_MAX_STEPS = 256, 8
 
 
