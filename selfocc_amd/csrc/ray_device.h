@@ -1,7 +1,8 @@
 // ray_device.h — the ray geometry of the render kernels: ONE definition for render_fwd.hip (per-ray march), render_train.hip
-// (sample-parallel forward), render_bwd.hip (backward + its counting pre-pass), render_median.hip and render_upsample.hip.
+// (sample-parallel forward), render_bwd.hip (backward + its counting pre-pass), render_upsample.hip and, through
+// sdf_walk_device.h, render_median.hip and render_normal.hip.
 //
-// Ray construction, the box collider and the bin edges decide which voxel cell a sample lands in, so the three translation
+// Ray construction, the box collider and the bin edges decide which voxel cell a sample lands in, so the translation
 // units must agree on them operation for operation, and with oracle/oracle_render.c (-ffp-contract=off, every
 // rounding spelled out).  A one-ulp difference gives a gradient for another cell than the forward used.
 #pragma once
@@ -85,7 +86,55 @@ SO_DEVFN float so_edge(const so_render_args &a, int ray, int j, float tnear, flo
     return so_edge_metric(so_edge_unit(a, ray, j), tnear, tfar);
 }
 
-// 64-lane butterfly sums, every lane gets the total.  Two orders, named for the lane distances they pair: float addition is
+// ---- the canonical per-sample arithmetic ------------------------------------------------
+// so_sample_point and so_neus_alpha are the sample of so_march_exact (render_fwd.hip) and so_walk_ray (sdf_walk_device.h).
+// render_train.hip and render_bwd.hip (sample_cell) spell the same operations out in their own bodies and must agree with
+// these two, operation for operation.  They are NOT rewritten on top of them: the substitution was tried and compared with
+// scripts/kernel_isa_diff.py, and it changed the generated code of 73 of render_train.hip's 81 kernels and of 33 of
+// render_bwd.hip's 230.  The training hot path does not move for a tidier source.
+
+// position of the sample of the bin [t_start, t_end]: its start, or its middle (so_render_args::sample_pos)
+SO_DEVFN void so_sample_point(const so_render_args &a, const RayGeom &g, float t_start, float t_end, float &px, float &py, float &pz) {
+    if (a.sample_pos == SO_SAMPLE_AT_START) {
+        px = g.ox + g.dx * t_start; py = g.oy + g.dy * t_start; pz = g.oz + g.dz * t_start;
+    } else {
+        const float tt = t_start + t_end;
+        px = g.ox + (g.dx * tt) / 2.0f; py = g.oy + (g.dy * tt) / 2.0f; pz = g.oz + (g.dz * tt) / 2.0f;
+    }
+}
+
+// NeuS alpha (sdfstudio NeuS get_alpha, cos anneal ratio 1) of a sample with value `sdf`, gradient (gx, gy, gz) and bin length
+// `delta`, clamped to [0, 1]
+SO_DEVFN float so_neus_alpha(const RayGeom &g, float sdf, float gx, float gy, float gz, float delta, float inv_s) {
+    const float cosv = (g.dx * gx + g.dy * gy) + g.dz * gz;
+    const float icos = fminf(cosv, 0.0f);
+    const float half = (icos * delta) * 0.5f;
+    const float prev_cdf = so_sigmoid((sdf - half) * inv_s);
+    const float next_cdf = so_sigmoid((sdf + half) * inv_s);
+    const float alpha = ((prev_cdf - next_cdf) + 1e-5f) / (prev_cdf + 1e-5f);
+    return fminf(fmaxf(alpha, 0.0f), 1.0f);
+}
+
+// ---- host side: what every entry point that embeds an so_render_args shares ------------------
+// the checks of selfocc_render_fwd on the struct (render_fwd.hip); 0 when it is accepted, else the error is set
+int so_validate_render(const so_render_args &a);
+
+// The struct as a geometry-only entry point (render_median / render_normal / render_upsample) reads it: SDF volume, mapping,
+// rays and sampling.  The feature fields, the colour basis, the background, the flags, every output pointer and the brick are
+// ignored, whatever they hold; what is left goes through so_validate_render.
+static inline so_render_args so_geometry_only(so_render_args a) {
+    a.feat_vol = nullptr;
+    a.feat_dtype = SO_DTYPE_F32; a.feat_stride = 0; a.n_rgb = 0; a.n_sem = 0;
+    a.sh_deg = 0; a.sh_act = SO_SH_RELU;
+    a.bkgd_mode = SO_BKGD_NONE; a.bkgd_rays = nullptr;
+    a.flags = 0;
+    a.depth = a.acc = a.rgb = a.sem = a.max_depth = a.nears = a.fars = nullptr;
+    a.weights = a.ts = a.deltas = a.sdf = a.grad = nullptr;
+    a.sdf_brick = nullptr;
+    return a;
+}
+
+// 64-lane butterfly sums, every lane gets the total. Two orders, named for the lane distances they pair: float addition is
 // not associative, and render_train.hip (1, 2, .. 32) and render_bwd.hip (32, 16, .. 1) each keep the order they shipped with.
 SO_DEVFN float so_wave_sum_1to32(float v) {
 #pragma unroll

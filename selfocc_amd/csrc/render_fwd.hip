@@ -169,28 +169,14 @@ SO_DEVFN void so_march_exact(const so_render_args &a, int ray, const RayGeom &g)
         float delta = t_end - t_start;
         float t_mid = (t_start + t_end) / 2.0f;
         float px, py, pz;
-        if (a.sample_pos == SO_SAMPLE_AT_START) {
-            px = g.ox + g.dx * t_start; py = g.oy + g.dy * t_start; pz = g.oz + g.dz * t_start;
-        } else {
-            float tt = t_start + t_end;
-            px = g.ox + (g.dx * tt) / 2.0f; py = g.oy + (g.dy * tt) / 2.0f;
-            pz = g.oz + (g.dz * tt) / 2.0f;
-        }
+        so_sample_point(a, g, t_start, t_end, px, py, pz);
         so_cell c = so_locate_k<MK>(a.map, px, py, pz);
         float v[8], wk[8];
         so_gather_sdf(a.sdf_vol, H, W, D, c, v);
         float sdf = so_trilerp_sdf(c, v, wk);
         float gx, gy, gz;
         so_trilerp_grad(c, v, gx, gy, gz);
-
-        // NeuS alpha (sdfstudio NeuS get_alpha, cos anneal ratio 1)
-        float cosv = (g.dx * gx + g.dy * gy) + g.dz * gz;
-        float icos = fminf(cosv, 0.0f);
-        float half = (icos * delta) * 0.5f;
-        float prev_cdf = so_sigmoid((sdf - half) * so_inv_s(a));
-        float next_cdf = so_sigmoid((sdf + half) * so_inv_s(a));
-        float alpha = ((prev_cdf - next_cdf) + 1e-5f) / (prev_cdf + 1e-5f);
-        alpha = fminf(fmaxf(alpha, 0.0f), 1.0f);
+        float alpha = so_neus_alpha(g, sdf, gx, gy, gz, delta, so_inv_s(a));
         float w = alpha * T;
         T = T * ((1.0f - alpha) + 1e-7f);
 

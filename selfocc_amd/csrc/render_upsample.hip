@@ -31,9 +31,6 @@
 // fl(b_lo + fl(q * fl(b_hi - b_lo))) may exceed b_hi by an ulp.  No atomics: the same inputs give the same bits.
 #include "ray_device.h"
 
-// render_fwd.hip
-int so_validate_render(const so_render_args &a);
-
 namespace {
 
 constexpr int kUpMaxSamples = 256;   // S_tot limit: what render_train / render_bwd take
@@ -234,7 +231,8 @@ __global__ __launch_bounds__(64 * kUpWaves) void render_upsample_kernel(so_rende
 extern "C" int selfocc_render_upsample(const so_render_upsample_args *args, void *stream) {
     SO_REQUIRE(args != nullptr, "args is NULL");
     SO_REQUIRE(args->edges != nullptr, "render_upsample: edges is NULL");
-    so_render_args a = args->fwd;
+    so_render_args a = so_geometry_only(args->fwd);
+    a.inv_s_dev = nullptr;                               // inv_s is ignored too: the sampler has its own variance
     SO_REQUIRE(a.n_samples >= 1, "render_upsample: n_samples must be >= 1 (got %d)", (int)a.n_samples);
     SO_REQUIRE(a.n_rays >= 0, "render_upsample: n_rays must be >= 0 (got %d)", (int)a.n_rays);
     SO_REQUIRE(a.jitter_mode != SO_JITTER_EDGES, "render_upsample: the sampler starts from the uniform bins (jitter_mode 0, 1 or 2), "
@@ -249,16 +247,6 @@ extern "C" int selfocc_render_upsample(const so_render_upsample_args *args, void
                s_tot, kUpMaxSamples);
     SO_REQUIRE(args->base_variance > 0.0f && __builtin_isfinite(args->base_variance),
                "render_upsample: base_variance must be positive and finite (got %g)", (double)args->base_variance);
-    // geometry only: the feature fields, inv_s, the background and every output pointer of the embedded struct are ignored
-    a.feat_vol = nullptr;
-    a.feat_dtype = SO_DTYPE_F32; a.feat_stride = 0; a.n_rgb = 0; a.n_sem = 0;
-    a.sh_deg = 0; a.sh_act = SO_SH_RELU;
-    a.bkgd_mode = SO_BKGD_NONE; a.bkgd_rays = nullptr;
-    a.flags = 0;
-    a.depth = a.acc = a.rgb = a.sem = a.max_depth = a.nears = a.fars = nullptr;
-    a.weights = a.ts = a.deltas = a.sdf = a.grad = nullptr;
-    a.sdf_brick = nullptr;
-    a.inv_s_dev = nullptr;
     if (so_validate_render(a)) return -1;
     if (a.n_rays == 0) return 0;
     hipStream_t st = (hipStream_t)stream;

@@ -249,6 +249,22 @@ def _with_edges(cfg, edges, t_rand, n_rays):
     return dataclasses.replace(cfg, n_samples=edges.shape[1] - 1, jitter_mode=abi.JITTER_EDGES), edges.detach()
 
 
+_GEOMETRY_FIELDS = ('aabb', 'n_samples', 'inv_s', 'inv_s_dev', 'near_plane', 'sample_pos', 'jitter_mode')
+
+
+def _geometry_args(vol, rays, cfg, *, t_rand, edges=None, what, fields=_GEOMETRY_FIELDS):
+    """The ``so_render_args`` of a geometry-only entry point (csrc/ray_device.h: so_geometry_only): the SDF volume alone
+    (``vol.feat`` is not looked at), the rays, and of ``cfg`` only ``fields``, the sampling fields and inv_s; its background,
+    colour and march switches do not apply.  No output is allocated and no tensor is copied: every pointer is into the
+    storage of one of the caller's own arguments, which keep it alive.  Returns (args, n_rays, device)."""
+    if not vol.sdf.is_cuda:
+        raise RuntimeError(f"selfocc_amd.{what} needs CUDA(HIP) tensors: there is no CPU fallback")
+    cfg, t_rand = _with_edges(cfg, edges, t_rand, rays.n_rays)
+    geo = RenderConfig(**{f: getattr(cfg, f) for f in fields})
+    a, _out, _keep = marshal_render_args(SDFVolume(vol.mapping, vol.sdf), rays, geo, t_rand=t_rand, inputs_only=True)
+    return a, rays.n_rays, vol.sdf.device
+
+
 def render_rays(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, per_sample=False,
                 want_grad_samples=False, t_rand=None, bkgd_rays=None, outputs=None, edges=None):
     """Forward render on the GPU (no autograd).  Returns a dict of per-ray tensors
@@ -274,16 +290,8 @@ def render_median_depth(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, t_ra
     without materialising them: a ray stops marching at the first sample whose running weight sum reaches 0.5.
     Reads the SDF volume only (``vol.feat`` is not looked at) and marches in the canonical order whatever ``cfg.exact``.
     Returns {'median_depth': (N,) float32[, 'median_index': (N,) int32]}."""
-    if not vol.sdf.is_cuda:
-        raise RuntimeError("selfocc_amd.render_median_depth needs CUDA(HIP) tensors: there is no CPU fallback")
-    cfg, t_rand = _with_edges(cfg, edges, t_rand, rays.n_rays)
-    # geometry only: the sampling fields and inv_s of `cfg`; its background, colour and march switches do not apply
-    geo = RenderConfig(aabb=cfg.aabb, n_samples=cfg.n_samples, inv_s=cfg.inv_s, inv_s_dev=cfg.inv_s_dev, near_plane=cfg.near_plane,
-                       sample_pos=cfg.sample_pos, jitter_mode=cfg.jitter_mode)
-    a, _out, _keep = marshal_render_args(SDFVolume(vol.mapping, vol.sdf), rays, geo, t_rand=t_rand, inputs_only=True)
     ma = abi.SoRenderMedianArgs()
-    ma.fwd = a
-    N, dev = rays.n_rays, vol.sdf.device
+    ma.fwd, N, dev = _geometry_args(vol, rays, cfg, t_rand=t_rand, edges=edges, what="render_median_depth")
     out = {'median_depth': torch.empty(N, dtype=torch.float32, device=dev)}
     if want_index:
         out['median_index'] = torch.empty(N, dtype=torch.int32, device=dev)
@@ -325,16 +333,8 @@ def render_normal_vis(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, *, t_rand
     without materialising them.  Reads the SDF volume only (``vol.feat`` is not looked at), marches every sample in the
     canonical order whatever ``cfg.exact``, and never reads anything back to the host (``cfg.inv_s_dev`` is honoured).
     Returns (N, 3) float32; a ray that misses the box by more than a cell (zero gradients) gives (0.5, 0.5, 0.5)."""
-    if not vol.sdf.is_cuda:
-        raise RuntimeError("selfocc_amd.render_normal_vis needs CUDA(HIP) tensors: there is no CPU fallback")
-    cfg, t_rand = _with_edges(cfg, edges, t_rand, rays.n_rays)
-    # geometry only: the sampling fields and inv_s of `cfg`; its background, colour and march switches do not apply
-    geo = RenderConfig(aabb=cfg.aabb, n_samples=cfg.n_samples, inv_s=cfg.inv_s, inv_s_dev=cfg.inv_s_dev, near_plane=cfg.near_plane,
-                       sample_pos=cfg.sample_pos, jitter_mode=cfg.jitter_mode)
-    a, _out, _keep = marshal_render_args(SDFVolume(vol.mapping, vol.sdf), rays, geo, t_rand=t_rand, inputs_only=True)
     na = abi.SoRenderNormalArgs()
-    na.fwd = a
-    N, dev = rays.n_rays, vol.sdf.device
+    na.fwd, N, dev = _geometry_args(vol, rays, cfg, t_rand=t_rand, edges=edges, what="render_normal_vis")
     out = torch.empty(N, 3, dtype=torch.float32, device=dev)
     if N == 0:          # nothing to launch (and an empty tensor has no address to pass)
         return out
@@ -397,20 +397,17 @@ def upsample_edges(vol: SDFVolume, rays: RaySet, cfg: RenderConfig, n_importance
     fixed-variance NeuS weights (``base_variance * 2^k``).  ``u_rand`` (n_steps, N) uniform [0, 1) or None (0.5).
     Returns the (N, S_tot + 1) normalised edges for the ``edges=`` argument of the render calls; with nothing to add
     (``upsample_plan``: K = 0) they are the start edges.  Reads the SDF volume only; no gradient."""
-    if not vol.sdf.is_cuda:
-        raise RuntimeError("selfocc_amd.upsample_edges needs CUDA(HIP) tensors: there is no CPU fallback")
     m, K, s_tot = upsample_plan(cfg.n_samples, int(n_importance), int(n_steps))
     if s_tot > UPSAMPLE_MAX_SAMPLES:
         raise ValueError(f"n_samples = {s_tot} is not built for upsample_edges (built: <= {UPSAMPLE_MAX_SAMPLES})")
     assert cfg.jitter_mode != abi.JITTER_EDGES, "upsample_edges starts from the uniform bins"
-    geo = RenderConfig(aabb=cfg.aabb, n_samples=cfg.n_samples, near_plane=cfg.near_plane, jitter_mode=cfg.jitter_mode)
-    a, _out, _keep = marshal_render_args(SDFVolume(vol.mapping, vol.sdf.detach()), rays, geo, t_rand=t_rand, inputs_only=True)
-    N, dev = rays.n_rays, vol.sdf.device
+    ua = abi.SoRenderUpsampleArgs()
+    # the sampler has its own variance and always looks up the sample start: neither inv_s nor sample_pos
+    ua.fwd, N, dev = _geometry_args(vol, rays, cfg, t_rand=t_rand, what="upsample_edges",
+                                    fields=('aabb', 'n_samples', 'near_plane', 'jitter_mode'))
     edges = torch.empty(N, s_tot + 1, dtype=torch.float32, device=dev)
     if N == 0:
         return edges
-    ua = abi.SoRenderUpsampleArgs()
-    ua.fwd = a
     ua.n_importance, ua.n_steps, ua.base_variance = int(n_importance), int(n_steps), float(base_variance)
     if u_rand is not None and K > 0:
         assert tuple(u_rand.shape) == (int(n_steps), N), f"u_rand must be {(int(n_steps), N)}"
