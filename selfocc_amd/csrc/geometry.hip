@@ -97,8 +97,11 @@ extern "C" int selfocc_flatten_feats(const float *const *feats, const int32_t *h
     a.cams = cams_embeds; a.lvls = level_embeds; a.out = out;
     a.L = n_levels; a.B = B; a.N = N; a.C = C; a.S = (int)S;
     const size_t shm = (size_t)C * 65 * sizeof(float);
-    if (shm > 48 * 1024)
-        (void)hipFuncSetAttribute((const void *)flatten_feats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    if (shm > 48 * 1024) {                                           // from C = 190: more dynamic LDS than a launch gets by default
+        const hipError_t e = hipFuncSetAttribute((const void *)flatten_feats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        SO_REQUIRE(e == hipSuccess, "flatten_feats: C = %d needs %zu bytes of dynamic LDS, which the device refuses: %s", C, shm,
+                   hipGetErrorString(e));
+    }
     hipLaunchKernelGGL(flatten_feats_kernel, dim3((unsigned)tiles, (unsigned)N, (unsigned)B), dim3(256), shm, (hipStream_t)stream, a);
     return so_launch_status();
 }

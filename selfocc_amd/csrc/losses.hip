@@ -7,13 +7,17 @@
 // dimension of three (67 us), sub, pow, mean forward and pow / norm backward (a copy, div, mul, masked_fill): ~0.26 ms per
 // iteration for 88 MB of input.  Here: forward = one streaming pass writing one partial sum per block (the caller adds the
 // partials: deterministic), backward = one streaming pass
-//     d/dg = scale * 2 (||g|| - 1) g / ||g||      (0 where ||g|| = 0, as torch's norm backward),   scale read from device memory.
+//     d/dg = scale * 2 (||g|| - 1) g / ||g||      (0 where g = 0, as torch's norm backward),   scale read from device memory.
 #include "so_device.h"
 #include <algorithm>
 
 namespace {
 
 constexpr int kEikRowsPerThread = 4;
+// Below this squared norm (2^-100: 24 bits above float32's smallest normal) x^2 + y^2 + z^2 is subnormal or zero, and the
+// backward takes the row's direction from a rescaled copy: a row of magnitude 1e-25 has the gradient -2 scale g / ||g|| like
+// every other short row (float64 says so), not the 0 that sqrtf(0) would give it.  Rows above it keep the plain formula's bits.
+constexpr float kEikTinySq = 7.888609052210118e-31f;
 
 __global__ __launch_bounds__(256) void eikonal_fwd_kernel(const float *__restrict__ g, float *__restrict__ partial, long long n) {
     __shared__ float red[4];
@@ -37,9 +41,23 @@ __global__ __launch_bounds__(256) void eikonal_bwd_kernel(const float *__restric
     const long long stride = (long long)gridDim.x * 256;
     for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < n; r += stride) {
         const float x = g[3 * r], y = g[3 * r + 1], z = g[3 * r + 2];
-        const float nn = sqrtf((x * x + y * y) + z * z);
+        const float ss = (x * x + y * y) + z * z;
+        const float nn = sqrtf(ss);
         const float f = nn > 0.0f ? sc * (nn - 1.0f) / nn : 0.0f;
-        gg[3 * r] = f * x; gg[3 * r + 1] = f * y; gg[3 * r + 2] = f * z;
+        float gx = f * x, gy = f * y, gz = f * z;
+        if (ss < kEikTinySq) {                 // the squared norm lost bits or underflowed (|g| < 2^-50): the direction g / ||g|| from
+            gx = gy = gz = 0.0f;               // the row scaled by a power of two (exact); only g = 0 has no direction
+            const float m = fmaxf(fmaxf(fabsf(x), fabsf(y)), fabsf(z));
+            if (m > 0.0f) {
+                int e;
+                (void)frexpf(m, &e);
+                const float xs = ldexpf(x, -e), ys = ldexpf(y, -e), zs = ldexpf(z, -e);     // largest component in [0.5, 1)
+                const float ns = sqrtf((xs * xs + ys * ys) + zs * zs);
+                const float k = sc * (ldexpf(ns, e) - 1.0f);
+                gx = k * (xs / ns); gy = k * (ys / ns); gz = k * (zs / ns);
+            }
+        }
+        gg[3 * r] = gx; gg[3 * r + 1] = gy; gg[3 * r + 2] = gz;
     }
 }
 
