@@ -787,6 +787,10 @@ int so_field_volume_bwd_b3(const float *hw, const float *zh, const float *wz, in
                            const float *b1, const float *w2, int out_dim, const float *g_sdf, const float *g_feat,
                            int feat_stride, float *g_hw, float *g_zh, float *g_wz, float *g_w1, float *g_b1, float *g_w2,
                            float *g_b2, hipStream_t st);      // field_bwd_b3.hip
+int so_field_volume_bwd_w(const float *hw, const float *zh, const float *wz, int H, int W, int D, int C, const float *w1,
+                          const float *b1, const float *w2, int out_dim, const float *g_sdf, const float *g_feat,
+                          int feat_stride, float *g_hw, float *g_zh, float *g_wz, float *g_w1, float *g_b1, float *g_w2,
+                          float *g_b2, hipStream_t st);       // field_bwd_w.hip (C = 64 / 128)
 
 extern "C" int selfocc_field_volume_bwd(const float *hw, const float *zh, const float *wz, int32_t H, int32_t W,
                                         int32_t D, int32_t C, const float *w_hidden, const float *b_hidden,
@@ -794,7 +798,7 @@ extern "C" int selfocc_field_volume_bwd(const float *hw, const float *zh, const 
                                         int32_t feat_stride, float *g_hw, float *g_zh, float *g_wz, float *g_w_hidden,
                                         float *g_b_hidden, float *g_w_out, float *g_b_out, void *stream) {
     SO_REQUIRE(H >= 1 && W >= 1 && D >= 1, "field_volume_bwd: bad volume size (%d, %d, %d)", H, W, D);
-    SO_REQUIRE(C == 96, "field_volume_bwd: embed_dims must be 96 (got %d); use the autograd path", C);
+    SO_REQUIRE(C == 64 || C == 96 || C == 128, "field_volume_bwd: embed_dims must be 64, 96 or 128 (got %d)", C);
     SO_REQUIRE(out_dim >= 1 && out_dim <= 32, "field_volume_bwd: 1 + color_dims must be <= 32 (got %d)", out_dim);
     SO_REQUIRE(hw && zh && wz && w_hidden && b_hidden && w_out, "field_volume_bwd: NULL input pointer");
     SO_REQUIRE(g_hw && g_zh && g_wz && g_w_hidden && g_b_hidden && g_w_out && g_b_out,
@@ -805,6 +809,10 @@ extern "C" int selfocc_field_volume_bwd(const float *hw, const float *zh, const 
     SO_REQUIRE(M < (1LL << 31) * 32, "field_volume_bwd: volume too large");
     const long long PH = (H + 3) / 4, PW = (W + 3) / 4, PD = (D + 1) / 2;
     SO_REQUIRE(PH * PW * PD < (1LL << 31), "field_volume_bwd: volume too large");
+    // C = 64 / 128: the width-generic float32-MFMA kernel (every feat_stride, 64-bit indexing); C = 96 below, as ever
+    if (C != 96)
+        return so_field_volume_bwd_w(hw, zh, wz, H, W, D, C, w_hidden, b_hidden, w_out, out_dim, g_sdf, g_feat, feat_stride, g_hw,
+                                     g_zh, g_wz, g_w_hidden, g_b_hidden, g_w_out, g_b_out, (hipStream_t)stream);
     // round 5: the five GEMMs on the bf16 matrix pipe (field_bwd_b3.hip); SELFOCC_FIELD_BWD_B3=0 keeps the f32-MFMA kernel.
     // (its 16-byte loads of the upstream feature gradient need rows of a multiple of four floats)
     static const bool bwd_b3 = !(getenv("SELFOCC_FIELD_BWD_B3") && atoi(getenv("SELFOCC_FIELD_BWD_B3")) == 0);

@@ -2,8 +2,9 @@
 
 Mirror of the head's ``pre_compute_density_color`` for the tri-plane representation
 (sdfstudio-fork SDFCustomField, driven from model/head/neus_head/neus_head.py:295-306; in-repo
-analogue BEVNeRF, model/head/nerfacc_head/bev_nerf.py:74-95).  Forward only: training keeps the
-autograd path in ``SDFField.pre_compute_density_color``."""
+analogue BEVNeRF, model/head/nerfacc_head/bev_nerf.py:74-95).  ``field_volume`` is the inference form;
+``FieldVolumeFunction`` the training form (``selfocc_field_volume_bwd``) for embed_dims 64, 96 and 128 with two
+Linear layers; every other configuration keeps the autograd path in ``SDFField.pre_compute_density_color``."""
 import torch
 
 from . import abi
@@ -46,15 +47,17 @@ def field_volume(hw, zh, wz, size_hwd, linears, feat_stride=0, feat_dtype=torch.
 
 
 def field_volume_train_supported(embed_dims, n_linear, out_dim, feat_stride, feat_dtype, size_hwd=None):
-    ok = embed_dims == 96 and n_linear == 2 and 1 <= out_dim <= 32 and feat_stride <= 31 and feat_dtype == torch.float32
+    ok = embed_dims in SUPPORTED_EMBED_DIMS and n_linear == 2 and 1 <= out_dim <= 32 and feat_stride <= 31 and feat_dtype == torch.float32
     return ok          # any (H, W, D): the backward walks 4 x 4 x 2 voxel patches (ragged ones are masked)
 
 
 class FieldVolumeFunction(torch.autograd.Function):
     """Training form: (sdf, feat) = volume MLP of the tri-plane, fused in both directions
     (``selfocc_field_volume_fwd`` / ``selfocc_field_volume_bwd``).  The forward keeps only its inputs — the
-    backward kernel recomputes the activations tile by tile — so the (H*W*D, 96) intermediates of the
-    op-by-op path (634 MB each at the nuscenes_occ size) never exist."""
+    backward kernel recomputes the activations tile by tile — so the (H*W*D, C) intermediates of the
+    op-by-op path (at the nuscenes_occ size 423 / 634 / 845 MB each for C = 64 / 96 / 128) never exist.
+    C = 96 runs the bf16 x 3 kernel (or the 96-wide float32-MFMA one), C = 64 / 128 the width-generic
+    float32-MFMA kernel of csrc/field_bwd_w.hip."""
 
     @staticmethod
     def forward(ctx, hw, zh, wz, w1, b1, w2, b2, size_hwd, feat_stride):
