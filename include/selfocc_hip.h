@@ -501,6 +501,33 @@ int selfocc_field_query(const so_query_args *args, void *stream);
 int selfocc_field_query_bwd(const so_query_args *args, const float *g_sdf, const float *g_logits,
                             float *g_sdf_vol, float *g_feat_vol, void *stream);
 
+/* SDF gradient d sdf / d metre at arbitrary metre positions (csrc/field_grad.hip).
+ *   SO_GRAD_ANALYTIC   the gradient the render kernels define for a sample at that position (so_locate_k, so_gather_sdf,
+ *                      so_trilerp_grad of so_device.h: cell, corner differences and d grid / d metre slope, zero padding)
+ *   SO_GRAD_NUMERICAL  central differences (sdfstudio's use_numerical_gradients): for each axis k, p+- = x with
+ *                      x_k +- delta in float32, s+- = the value selfocc_field_query returns at p+-,
+ *                      grad_k = (0.5f * (s+ - s-)) / delta in that association
+ * q.map, q.sdf_vol, q.xyz and q.n are read; q.sdf may be NULL, and when given it is selfocc_field_query's value bit for bit;
+ * the feature / logit / arg-max fields of q are ignored.  Argument checks are host logic and run before any HIP call; n == 0
+ * succeeds without a launch.  New entry points and a new struct: SELFOCC_ABI_VERSION is unchanged. */
+#define SO_GRAD_ANALYTIC 0
+#define SO_GRAD_NUMERICAL 1
+typedef struct so_field_grad_args {
+    so_query_args q;
+    float *grad;          /* (n, 3) d sdf / d metre (x, y, z)                          */
+    int32_t mode;         /* SO_GRAD_ANALYTIC or SO_GRAD_NUMERICAL                     */
+    float delta;          /* metres, > 0; SO_GRAD_NUMERICAL only                       */
+} so_field_grad_args;
+
+int selfocc_field_grad(const so_field_grad_args *args, void *stream);
+
+/* Backward of selfocc_field_grad with respect to the SDF volume (both modes are linear in it): g_sdf (n) and / or g_grad (n, 3),
+ * either may be NULL, are scattered to the 8 corners of the point's cell (analytic) or of each of the 6 taps' cells (numerical;
+ * g_sdf to the point's own cell).  g_sdf_vol [H][W][D] is ACCUMULATED (atomic adds): zero-initialise it.  Positions carry no
+ * gradient.  The outputs of `args` (q.sdf, grad) are ignored. */
+int selfocc_field_grad_bwd(const so_field_grad_args *args, const float *g_sdf, const float *g_grad, float *g_sdf_vol,
+                           void *stream);
+
 /* ------------------------------------------------------------------------------------
  * Tri-plane -> dense volume: the head's pre_compute_density_color(representation)
  * (sdfstudio-fork SDFCustomField, driven from model/head/neus_head/neus_head.py:295-306;

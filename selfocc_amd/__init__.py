@@ -8,13 +8,14 @@ _LAZY = {'DepthMetric': 'depth_metric', 'depth_errors': 'depth_metric', 'MeanIoU
          'SSCMetrics': 'ssc_metric', 'kitti_occ_metrics': 'ssc_metric', 'cityscapes2semantickitti': 'ssc_metric',
          'openseed2nuscenes': 'ssc_metric', 'render_median_depth': 'render', 'median_depth_reference': 'render',
          'upsample_edges': 'render', 'neus_upsample_reference': 'render', 'render_normal_vis': 'render',
-         'normal_vis_reference': 'render'}
+         'normal_vis_reference': 'render', 'field_grad': 'occ', 'field_grad_autograd': 'occ'}
 
 
 def __getattr__(name):
     """``from selfocc_amd import DepthMetric`` (the depth-evaluation metric, depth_metric.py) or ``IoU, MeanIoU,
     SSCMetrics`` (the occupancy metrics, ssc_metric.py / occ.py) or ``render_median_depth, median_depth_reference, upsample_edges,
-    neus_upsample_reference, render_normal_vis, normal_vis_reference`` (render.py)
+    neus_upsample_reference, render_normal_vis, normal_vis_reference`` (render.py) or ``field_grad, field_grad_autograd`` (the SDF
+    gradient at arbitrary points, occ.py)
     without importing torch at package import."""
     if name in _LAZY:
         import importlib

@@ -23,6 +23,7 @@ LINEAR_RELU, LINEAR_BF16X1 = 1, 2
 LBL_F32, LBL_U8, LBL_I32, LBL_I64 = 0, 1, 2, 3
 MAP_LINEAR, MAP_UPSCALE = 0, 1
 SH_RELU, SH_SIGMOID = 0, 1
+GRAD_ANALYTIC, GRAD_NUMERICAL = 0, 1
 
 _f, _i, _p = C.c_float, C.c_int32, C.c_void_p
 
@@ -110,6 +111,10 @@ class SoQueryArgs(C.Structure):
         ("xyz", _p), ("n", _i),
         ("sdf", _p), ("sem_logits", _p), ("sem_argmax", _p),
     ]
+
+
+class SoFieldGradArgs(C.Structure):
+    _fields_ = [("q", SoQueryArgs), ("grad", _p), ("mode", _i), ("delta", _f)]
 
 
 class SoOccArgs(C.Structure):
@@ -225,6 +230,8 @@ SYMBOLS = {
     "selfocc_msda_plan": (C.c_int, [C.POINTER(SoMsdaArgs), C.POINTER(C.c_int32)]),
     "selfocc_field_query": (C.c_int, [C.POINTER(SoQueryArgs), _p]),
     "selfocc_field_query_bwd": (C.c_int, [C.POINTER(SoQueryArgs), _p, _p, _p, _p, _p]),
+    "selfocc_field_grad": (C.c_int, [C.POINTER(SoFieldGradArgs), _p]),
+    "selfocc_field_grad_bwd": (C.c_int, [C.POINTER(SoFieldGradArgs), _p, _p, _p, _p]),
     "selfocc_field_volume_bwd": (C.c_int, [_p] * 3 + [_i] * 4 + [_p, _p, _p, _i, _p, _p, _i] + [_p] * 7 + [_p]),
     "selfocc_field_volume_fwd": (C.c_int, [_p] * 3 + [_i] * 4 + [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p]),
     "selfocc_occ_resample": (C.c_int, [C.POINTER(SoOccArgs), _p]),

@@ -11,7 +11,8 @@ img2lidar.py:6-70) is folded into the render kernel for lattice ray modes.
 
 Restated-from-upstream semantics (the fork is unavailable; DESIGN.md §7 lists them as
 declared deviation risks): field evaluated at frustum START positions, single jitter per
-ray in training, ``inv_s = exp(10 * variance)``, eik_grad = metre gradient at every sample,
+ray in training, ``inv_s = exp(10 * variance)``, eik_grad = metre gradient at every sample
+(``use_uniform_gradient``: and / or at points drawn uniformly in ``roi_aabb``, selfocc_field_grad),
 second_grad = compact second differences of the SDF volume.
 """
 import dataclasses
@@ -26,7 +27,7 @@ import torch.nn as nn
 from ... import abi, sh
 from ..._lib import upload
 from ...mapping import GridMeterMapping
-from ...occ import field_query, field_query_autograd, uniform_lattice
+from ...occ import field_grad, field_grad_autograd, field_query, field_query_autograd, uniform_lattice
 from ...field import field_volume, field_volume_supported, field_volume_train_supported, FieldVolumeFunction
 from ...registry import HEADS
 from ...render import (SDFVolume, RaySet, RenderConfig, render_rays, render_rays_autograd, render_median_depth, render_normal_vis, upsample_edges,
@@ -320,6 +321,16 @@ class SDFField(BaseModule):
             return field_query_autograd(SDFVolume(v.mapping, v.sdf, None, 0, 0), xyz.reshape(-1, 3))['sdf']
         return field_query(SDFVolume(v.mapping, v.sdf.detach(), None, 0, 0), xyz.reshape(-1, 3))['sdf']
 
+    def gradient(self, xyz, numerical=False, delta=None):
+        """(n, 3) metres -> (n, 3) d sdf / d metre of the pre-computed volume (selfocc_field_grad): the gradient the render
+        kernels define for a sample at that position, or, ``numerical=True``, central differences over ``delta`` metres
+        (sdfstudio's numerical_gradients_delta).  Attached to the SDF volume exactly when ``forward_sdfnetwork`` is."""
+        v = self.volume
+        mode = 'numerical' if numerical else 'analytic'
+        if self._differentiable():
+            return field_grad_autograd(SDFVolume(v.mapping, v.sdf, None, 0, 0), xyz.reshape(-1, 3), mode, delta)['grad']
+        return field_grad(SDFVolume(v.mapping, v.sdf.detach(), None, 0, 0), xyz.reshape(-1, 3), mode, delta, want_sdf=False)['grad']
+
     def second_grad(self):
         """Compact second differences of the SDF volume along h, w, d (declared restatement)."""
         s = self.volume.sdf
@@ -339,6 +350,20 @@ class _NeuSModel(nn.Module):
 
 @HEADS.register_module()
 class NeuSHead(BaseModule):
+    """The eikonal points (``eik_grad`` of ``forward()``; a declared restatement, DESIGN.md section 4 — the fork that defines
+    these knobs is not on disk):
+      use_uniform_gradient   False (default): ``eik_grad`` is the metre gradient at every ray sample, whatever the three
+                             knobs below say.  True: ``forward()`` with gradients enabled also draws
+                             ``nbr_gradient_points`` points uniformly in ``roi_aabb`` (torch.rand on the device, after every
+                             other draw of the call) and takes the SDF gradient there (SDFField.gradient)
+      nbr_gradient_points    how many uniform points, > 0
+      sample_gradient        with use_uniform_gradient: True, ``eik_grad`` is the ray-sample gradients followed by the uniform
+                             ones; False, the uniform ones only, and the render is not asked for per-sample gradients
+                             (unless ``return_sample_sdf`` needs the per-sample SDF that comes with them)
+      uniform_gradient_delta None: the analytic gradient at the uniform points; a step in metres > 0: central differences
+      calculate_online       accepted without effect: the gradients are always computed in the forward pass that uses them
+    ``use_uniform_gradient=True`` together with ``ray_shard=True`` is refused: the sharded EikonalLoss takes its global
+    sample count from the ray lattice."""
 
     def __init__(self, roi_aabb, resolution=0.4, near_plane=0.0, far_plane=1e10, num_samples=64,
                  num_samples_importance=64, num_up_sample_steps=4, base_variance=64, beta_init=0.1,
@@ -357,7 +382,7 @@ class NeuSHead(BaseModule):
                  embed_dims=128, color_dims=0, density_layers=2, sh_deg=2, sh_act="relu", init_cfg=None,
                  print_freq=50, two_split=True, tpv=False, using_2d_img_feats=False,
                  sample_pos='start', single_jitter=True, feat_dtype=torch.float32, exact_render=False,
-                 ray_shard=False, render_normal=False, return_median_depth=False, **kwargs):
+                 ray_shard=False, render_normal=False, return_median_depth=False, uniform_gradient_delta=None, **kwargs):
         super().__init__(init_cfg)
         for name, on in dict(use_numerical_gradients=use_numerical_gradients, estimate_flow=estimate_flow,
                              anneal_aabb=anneal_aabb, disp_sampler=disp_sampler, using_2d_img_feats=using_2d_img_feats,
@@ -369,6 +394,18 @@ class NeuSHead(BaseModule):
             warnings.warn("NeuSHead(return_second_grad=True, use_compact_2nd_grad=False): `second_grad` is always the compact "
                           "second difference of the SDF volume here (declared restatement, DESIGN.md section 4); the "
                           "SecondGradLoss weight of configs written for the non-compact form may need re-tuning")
+        self.use_uniform_gradient, self.sample_gradient = bool(use_uniform_gradient), bool(sample_gradient)
+        self.nbr_gradient_points, self.uniform_gradient_delta = int(nbr_gradient_points), uniform_gradient_delta
+        if self.use_uniform_gradient:
+            if ray_shard:
+                raise NotImplementedError("NeuSHead(use_uniform_gradient=True) together with ray_shard=True is not built: the "
+                                          "sharded EikonalLoss counts the samples of all ranks from the ray lattice")
+            if self.nbr_gradient_points <= 0:
+                raise ValueError(f"NeuSHead(use_uniform_gradient=True) needs nbr_gradient_points > 0 (got {nbr_gradient_points})")
+            if uniform_gradient_delta is not None and not float(uniform_gradient_delta) > 0.0:
+                raise ValueError(f"NeuSHead(uniform_gradient_delta={uniform_gradient_delta!r}): a step in metres > 0, or None for "
+                                 "the analytic gradient")
+        self._aabb_dev = {}
         self.ray_sampler = RaySampler(ray_sample_mode, ray_number, ray_img_size, ray_upper_crop, ray_x_dsr_max, ray_y_dsr_max)
         self.ray_sampler_eval = RaySampler('fixed', ray_number, ray_img_size, ray_upper_crop)
         self.img2lidar = Img2LiDAR(trans_kw, trans_kw_eval, novel_view)
@@ -480,7 +517,22 @@ class NeuSHead(BaseModule):
         if self.up_steps > 0:
             raise NotImplementedError("NeuSHead: ray sharding together with up-sampling (num_samples_importance > 0, "
                                       "num_up_sample_steps > 0) is not built")
+        if self.use_uniform_gradient:
+            raise NotImplementedError("NeuSHead(use_uniform_gradient=True) together with ray sharding is not built: the sharded "
+                                      "EikonalLoss counts the samples of all ranks from the ray lattice")
         return True
+
+    def _uniform_eik_grad(self, device):
+        """(nbr_gradient_points, 3): the SDF gradient at points drawn uniformly in roi_aabb, attached to the field volume.
+        The draw is one torch.rand on the device and the box a cached device constant: no host synchronisation."""
+        key = str(device)
+        box = self._aabb_dev.get(key)
+        if box is None:
+            lo, hi = np.asarray(self.aabb[:3], np.float32), np.asarray(self.aabb[3:], np.float32)
+            box = self._aabb_dev[key] = upload(np.stack([lo, hi - lo]), device, torch.float32)
+        xyz = torch.rand(self.nbr_gradient_points, 3, device=device) * box[1] + box[0]
+        delta = self.uniform_gradient_delta
+        return self.model.field.gradient(xyz, numerical=delta is not None, delta=delta)
 
     @staticmethod
     def _frame_token(metas):
@@ -715,7 +767,11 @@ class NeuSHead(BaseModule):
         inv_s = field.inv_s()
         if full_rays is not None:
             inv_s = sdist.replicate_grad_sum(inv_s)       # d/d(variance) is a sum over all rays as well
-        out = render_rays_autograd(vol, inv_s, rays, cfg, want_grad_samples=True, t_rand=t_rand, bkgd_rays=bk, edges=edges)
+        # use_uniform_gradient (class docstring): eik_grad from uniform points, in addition to the ray samples or instead of them
+        uniform = self.use_uniform_gradient and torch.is_grad_enabled()
+        ray_grad = not uniform or self.sample_gradient
+        out = render_rays_autograd(vol, inv_s, rays, cfg, want_grad_samples=ray_grad or self.return_sample_sdf, t_rand=t_rand,
+                                   bkgd_rays=bk, edges=edges)
         self.last_inv_s = inv_s.detach()          # device tensor (the reference logs output['inv_s'], neus_head.py:631-633)
         median = None
         if self.return_median_depth:
@@ -758,12 +814,16 @@ class NeuSHead(BaseModule):
         outputs = {'ms_depths': [depth], 'ms_colors': [rgb], 'ms_accs': [acc], 'ms_fars': [fars], 'ms_rays': pix,
                    'origin': origin, 'direction': direction, 'direction_norm': direction_norm,
                    'ray_indices': ray_idx, 'weights': per_cam(weights), 'ts': per_cam(ts), 'deltas': per_cam(deltas),
-                   'eik_grad': out['grad'].reshape(-1, 3) if shard is None else sdist.tag_local(out['grad'].reshape(-1, 3), shard),
-                   'uniform_sdf': None}
+                   'eik_grad': None, 'uniform_sdf': None}
+        if ray_grad:
+            outputs['eik_grad'] = out['grad'].reshape(-1, 3) if shard is None else sdist.tag_local(out['grad'].reshape(-1, 3), shard)
         if shard is not None:
             outputs['ray_shard'] = shard       # the losses read the shard from here (dist.RayShard.local_keys)
         if self.return_uniform_sdf:
             outputs['uniform_sdf'] = self.get_uniform_sdf(self.aabb, self.resolution, device, True)[0]
+        if uniform:            # after every other draw of the call: the random streams of a knob-off forward are untouched
+            g = self._uniform_eik_grad(device)
+            outputs['eik_grad'] = torch.cat([outputs['eik_grad'], g], 0) if ray_grad else g
         if self.return_max_depth:
             outputs['ms_max_depths'] = [out['max_depth'].reshape(shp)]
         if median is not None:

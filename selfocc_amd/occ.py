@@ -108,6 +108,88 @@ def field_query_autograd(vol, xyz, want_logits=False):
     return out
 
 
+_GRAD_MODES = {'analytic': abi.GRAD_ANALYTIC, 'numerical': abi.GRAD_NUMERICAL}
+
+
+def _grad_args(mapping, sdf_vol, xyz, mode, delta):
+    """so_field_grad_args of a query; ``mode`` 'analytic' (``delta`` must be None) or 'numerical' (``delta`` metres > 0)"""
+    if mode not in _GRAD_MODES:
+        raise ValueError(f"field_grad: mode must be 'analytic' or 'numerical' (got {mode!r})")
+    if mode == 'analytic' and delta is not None:
+        raise ValueError("field_grad: delta is the step of mode='numerical'; mode='analytic' takes none")
+    if mode == 'numerical' and not (delta is not None and float(delta) > 0.0):
+        raise ValueError(f"field_grad: mode='numerical' needs delta > 0 metres (got {delta!r})")
+    a = abi.SoFieldGradArgs()
+    a.q.map = mapping.to_abi()
+    a.q.sdf_vol = ptr(sdf_vol)
+    a.q.xyz, a.q.n = ptr(xyz), xyz.shape[0]
+    a.mode, a.delta = _GRAD_MODES[mode], 0.0 if delta is None else float(delta)
+    return a
+
+
+def _grad_inputs(vol, xyz, what):
+    _need_cuda(vol.sdf, what)
+    _need_cuda(xyz, what)
+    if vol.sdf.dtype != torch.float32 or not vol.sdf.is_contiguous():
+        raise ValueError(f"{what}: the SDF volume must be contiguous float32")
+    return xyz.reshape(-1, 3).contiguous().float()
+
+
+def field_grad(vol, xyz, mode='analytic', delta=None, want_sdf=True):
+    """SDF gradient d sdf / d metre of an SDFVolume at metre positions xyz (n, 3): dict(grad (n, 3)[, sdf (n)]).
+
+    ``mode='analytic'``: the gradient the render kernels define for a sample at that position (the per-sample ``grad`` of
+    ``render_rays(per_sample=True, want_grad_samples=True)``, bit for bit).  ``mode='numerical'``: central differences over
+    ``delta`` metres, ``(0.5 * (s+ - s-)) / delta`` with ``s+-`` what ``field_query`` returns at the float32 points
+    ``x_k +- delta`` (sdfstudio's use_numerical_gradients).  ``sdf`` is ``field_query``'s value bit for bit."""
+    xyz = _grad_inputs(vol, xyz, "field_grad")
+    a = _grad_args(vol.mapping, vol.sdf, xyz, mode, delta)
+    out = {'grad': torch.empty(xyz.shape[0], 3, device=xyz.device)}
+    a.grad = ptr(out['grad'])
+    if want_sdf:
+        out['sdf'] = torch.empty(xyz.shape[0], device=xyz.device)
+        a.q.sdf = ptr(out['sdf'])
+    check(lib().selfocc_field_grad(a, current_stream(xyz.device)), "selfocc_field_grad")
+    return out
+
+
+class FieldGradFunction(torch.autograd.Function):
+    """``field_grad`` attached to the autograd graph of ``sdf_vol``: (sdf (n), grad (n, 3)).  Both modes are linear in the
+    volume, so the backward is one scatter launch (selfocc_field_grad_bwd).  Positions carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, sdf_vol, xyz, mapping, mode, delta):
+        from .render import SDFVolume
+        q = field_grad(SDFVolume(mapping, sdf_vol.detach(), None, 0, 0), xyz, mode, delta)
+        ctx.save_for_backward(sdf_vol, xyz)
+        ctx.meta = (mapping, mode, delta)
+        return q['sdf'], q['grad']
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_sdf, g_grad):
+        sdf_vol, xyz = ctx.saved_tensors
+        mapping, mode, delta = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        xyz = xyz.contiguous().float()
+        a = _grad_args(mapping, sdf_vol, xyz, mode, delta)
+        gs = None if g_sdf is None else g_sdf.contiguous().float()
+        gg = None if g_grad is None else g_grad.contiguous().float()
+        g_sdf_vol = torch.zeros_like(sdf_vol, dtype=torch.float32)
+        check(lib().selfocc_field_grad_bwd(a, ptr(gs), ptr(gg), ptr(g_sdf_vol), current_stream(xyz.device)),
+              "selfocc_field_grad_bwd")
+        return g_sdf_vol, None, None, None, None
+
+
+def field_grad_autograd(vol, xyz, mode='analytic', delta=None):
+    """``field_grad`` under autograd: dict(sdf (n), grad (n, 3)) differentiable (once) w.r.t. ``vol.sdf``."""
+    xyz = _grad_inputs(vol, xyz, "field_grad_autograd")
+    _grad_args(vol.mapping, vol.sdf, xyz, mode, delta)          # the argument errors, before autograd wraps them
+    sdf, grad = FieldGradFunction.apply(vol.sdf, xyz.detach(), vol.mapping, mode, delta)
+    return {'sdf': sdf, 'grad': grad}
+
+
 _LATTICES = {}
 _LUTS = {}
 
