@@ -548,9 +548,9 @@ int selfocc_field_volume_fwd(const float *hw, const float *zh, const float *wz, 
  * outputs zero-initialised by the caller, accumulated).  Nothing of the forward is needed: the kernel
  * recomputes the activations per 32-voxel tile (a 4 x 4 x 2 patch; any (H, W, D), ragged patches masked).
  * g_sdf / g_feat may be NULL (treated as zero); out_dim in 1..32, any feat_stride >= out_dim - 1.
- * C = 96 runs the bf16 x 3 kernel (float32-level accuracy; the 96-wide float32-MFMA kernel where feat_stride is not
- * a multiple of 4 or the volume needs 64-bit indices), C = 64 / 128 the width-generic float32-MFMA kernel.  Any other
- * width returns < 0 ("embed_dims must be 64, 96 or 128") without touching a buffer. */
+ * One width-generic float32-MFMA kernel serves C = 64 / 96 / 128; C = 96 takes the bf16 x 3 kernel instead (float32-level
+ * accuracy) unless SELFOCC_FIELD_BWD_B3=0 (read at every call), feat_stride is not a multiple of 4, or the volume needs
+ * 64-bit indices.  Any other width returns < 0 ("embed_dims must be 64, 96 or 128") without touching a buffer. */
 int selfocc_field_volume_bwd(const float *hw, const float *zh, const float *wz, int32_t H, int32_t W,
                              int32_t D, int32_t C, const float *w_hidden, const float *b_hidden,
                              const float *w_out, int32_t out_dim, const float *g_sdf, const float *g_feat,

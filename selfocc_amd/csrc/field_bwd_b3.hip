@@ -1,6 +1,6 @@
 // field_bwd_b3.hip — backward of the fused tri-plane -> volume MLP (training, C = 96, one hidden layer) with all FIVE
-// GEMMs on the bf16 matrix pipe through the exact three-way split (round 5; field.hip's field_volume_bwd_kernel keeps the
-// float32-MFMA form for A/B: SELFOCC_FIELD_BWD_B3=0).
+// GEMMs on the bf16 matrix pipe through the exact three-way split (round 5; field_bwd_w.hip keeps the float32-MFMA form, for
+// the heads this kernel does not take and for A/B: SELFOCC_FIELD_BWD_B3=0).
 //
 // Reference semantics: autograd through the field the head drives (sdfstudio-fork SDFCustomField; in-repo analogue
 // model/head/nerfacc_head/bev_nerf.py:74-95):  x = hw + zh + wz,  a = Softplus(x),  y = W1 a + b1,  z = Softplus(y),
@@ -27,54 +27,11 @@
 // GEMM contracts units — k-strided in that image — and reads it with ds_read_b64_tr_b16 (gfx950's transpose read: within
 // 16 lanes, lane s supplies the address of M[k = s >> 2][columns 4 (s & 3) .. + 3] and lane l receives M[k = 0..3][column l];
 // mapping measured with scripts/micro/tr16_map.hip).  A second [input][unit] copy (60 KB) would not fit next to the tiles.
-#include "so_device.h"
-#include <algorithm>
-#include <atomic>
-#include <cstdlib>
-#include <type_traits>
+#include "field_device.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-// torch.nn.Softplus(beta=1, threshold=20) — the same evaluation as field.hip's forward
-// (1 + e >= 1 is never denormal: the raw v_log_f32 / v_exp_f32 instructions, without the denormal-range scaling that
-// __logf emits under -fno-fast-math — 26 -> 14 vector instructions per evaluation, 192 evaluations per voxel row pair)
-SO_DEVFN float fb_softplus(float x) {
-    const float e = __builtin_amdgcn_exp2f(x * 1.44269504088896341f);
-    const float series = e * (1.0f - e * (0.5f - e * (0.33333334f - 0.25f * e)));
-    const float lg = __builtin_amdgcn_logf(1.0f + e) * 0.69314718055994531f;
-    const float r = e < 0.05f ? series : lg;
-    return x > 20.0f ? x : r;
-}
-SO_DEVFN float fb_exp_neg(float z) { return __builtin_amdgcn_exp2f(z * -1.44269504088896341f); }     // exp(-z)
-
-SO_DEVFN void fb_split3(const float (&x)[8], bf16x8 &a1, bf16x8 &a2, bf16x8 &a3) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const __bf16 b1 = (__bf16)x[j];
-        const float r1 = x[j] - (float)b1;
-        const __bf16 b2 = (__bf16)r1;
-        const float r2 = r1 - (float)b2;
-        a1[j] = b1; a2[j] = b2; a3[j] = (__bf16)r2;
-    }
-}
-
-// acc += A B with A = a1 + a2 + a3, B = b1 + b2 + b3 (all exact), the six products with i + j <= 4, small terms first
-SO_DEVFN void fb_mfma6(f32x16 &acc, const bf16x8 &a1, const bf16x8 &a2, const bf16x8 &a3, const bf16x8 &b1, const bf16x8 &b2,
-                       const bf16x8 &b3) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
-}
-
-
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -89,7 +46,7 @@ SO_DEVFN void fb_split_pair(float x0, float x1, unsigned &p1, unsigned &p2, unsi
 }
 SO_DEVFN bf16x8 fb_as8(const u32x4 &v) { return __builtin_bit_cast(bf16x8, v); }
 
-// fb_mfma6 with a work item after each of the six MFMAs, the order pinned by scheduling fences: with ONE wave per SIMD the
+// so_mfma6 with a work item after each of the six MFMAs, the order pinned by scheduling fences: with ONE wave per SIMD the
 // vector work of the next operand only hides in the shadow of the dependent MFMA chain (32 cycles each) if it sits between
 // the MFMAs in program order, and the compiler's scheduler, left alone, issues the six MFMAs first
 #define FB_SB() __builtin_amdgcn_sched_barrier(0)
@@ -108,7 +65,7 @@ SO_DEVFN void fb_mfma6_il(f32x16 &acc, const bf16x8 &a1, const bf16x8 &a2, const
     if constexpr (!IL) {          // A/B: the same work items, left to the compiler's scheduler
 #pragma unroll
         for (int k = 0; k < 6; ++k) gap(k);
-        fb_mfma6(acc, a1, a2, a3, b1, b2, b3);
+        so_mfma6(acc, a1, a2, a3, b1, b2, b3);
         return;
     }
     FB_SB();
@@ -131,23 +88,6 @@ SO_DEVFN bf16x4 fb_tr4(const __bf16 *p) {
     return __builtin_bit_cast(bf16x4, v);
 }
 
-SO_DEVFN int fb_crow(int v, int half) { return (v & 3) + 8 * (v >> 2) + 4 * half; }   // C-layout row of register v
-
-struct FieldBwdB3Args {
-    const float *hw, *zh, *wz;
-    int H, W, D;
-    const float *w1, *b1, *w2;      // (96, 96), (96), (out_dim, 96)
-    int out_dim;
-    const float *g_sdf;             // (M) or NULL
-    const float *g_feat;            // (M, feat_stride) or NULL
-    int feat_stride;
-    float *g_hw, *g_zh, *g_wz;      // zero-initialised, accumulated
-    float *g_w1, *g_b1, *g_w2, *g_b2;
-    int n_tiles;                    // PH * PW * PD patches of 4 x 4 x 2 voxels
-    int PW, PD;
-    int dbg;                        // dev switch SELFOCC_FIELD_BWD_DBG: 1 = no zh / wz plane-gradient atomics (timing only)
-};
-
 constexpr int kB3_C = 96, kB3_WAVES = 4;
 constexpr int kB3_KPB = 100;   // W1 row stride (bf16): 50 dwords — conflict-free for 8-byte reads of 32 rows AND for the transpose reads
 constexpr int kB3_OPB = 40;    // W2^T row stride (bf16): 20 dwords — conflict-free 16-byte reads
@@ -163,7 +103,7 @@ constexpr size_t kB3_LDS = kB3_W1_BYTES + kB3_W2_BYTES + kB3_WAVES * kB3_T_FLOAT
 //   o' < 31: feature channel o' (row o' + 1 of W2) when o' < out_dim - 1, else nothing;   o' = 31: the SDF (row 0 of W2)
 SO_DEVFN int fb_w2_row(int op, int out_dim) { return op == 31 ? 0 : (op < out_dim - 1 ? op + 1 : -1); }
 
-__global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(FieldBwdB3Args a) {
+__global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(FieldBwdArgs a) {
     constexpr int C = kB3_C, KPB = kB3_KPB, OPB = kB3_OPB, THREADS = kB3_WAVES * 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __bf16 *w1b = (__bf16 *)smem_raw;                               // [3 planes][96 units][KPB]   W1[unit][input]
@@ -215,9 +155,8 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
     float db1[3] = {0.0f, 0.0f, 0.0f};
     float db2 = 0.0f;              // lane (o' = i, half): sum over the voxels this lane has seen
 
-    // d-walk (field.hip, round 4): a wave takes a contiguous range of tiles, d-patches fastest, and carries the 16 hw rows of
-    // its current (h, w) column across the column's d-patches — here in 24 lane-private LDS floats (the register file is full:
-    // 192 weight-gradient accumulators + the chain's 3 x 48)
+    // d-walk (so_tile_range): the 16 hw rows of the wave's current (h, w) column are carried in 24 lane-private LDS floats
+    // (the register file is full: 192 weight-gradient accumulators + the chain's 3 x 48)
     float *hwa = tiles + (size_t)kB3_WAVES * kB3_T_FLOATS + ((size_t)wave * 64 + lane) * kB3_HWA;
 #pragma unroll
     for (int q = 0; q < kB3_HWA / 4; ++q) ((float4 *)hwa)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -239,7 +178,8 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
         }
     };
     const int n_waves = gridDim.x * kB3_WAVES, wid = blockIdx.x * kB3_WAVES + wave;
-    const int t_lo = (int)((long long)a.n_tiles * wid / n_waves), t_hi = (int)((long long)a.n_tiles * (wid + 1) / n_waves);
+    int t_lo, t_hi;
+    so_tile_range(a.n_tiles, wid, n_waves, t_lo, t_hi);
     const int nfeat = a.g_feat ? a.out_dim - 1 : 0;          // feature channels that carry a gradient
     // lane constants of the patch geometry (tile row r = voxel (r >> 3, (r >> 1) & 3, r & 1) of the 4 x 4 x 2 patch)
     // One tile.  FULL: the 4 x 4 x 2 patch lies inside the volume (89 % of the tiles at 257 x 257 x 25) — no clamps, no liveness
@@ -256,14 +196,7 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
         float *hwa = tiles + (size_t)kB3_WAVES * kB3_T_FLOATS + ((size_t)wave * 64 + lane) * kB3_HWA;
         const int hhi = i >> 3, wwi = (i >> 1) & 3, ddi = i & 1;
         auto row_voxel = [&](int hh_, int ww_, int dd_, bool &live) {      // linear voxel index of patch voxel (hh_, ww_, dd_)
-            const int hh = h_b + hh_, ww = w_b + ww_, dd = d_b + dd_;
-            if constexpr (FULL) {
-                live = true;
-                return (hh * a.W + ww) * a.D + dd;
-            } else {
-                live = (hh < a.H) & (ww < a.W) & (dd < a.D);
-                return (min(hh, a.H - 1) * a.W + min(ww, a.W - 1)) * a.D + min(dd, a.D - 1);
-            }
+            return so_patch_voxel<int, FULL>(h_b, w_b, d_b, hh_, ww_, dd_, a.H, a.W, a.D, live);
         };
         bool mlive;
         const int m = row_voxel(hhi, wwi, ddi, mlive);            // the voxel this lane owns in the lane-per-voxel steps
@@ -337,7 +270,7 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
                 const float x0 = c == 0 ? xn[q].x : c == 1 ? xn[q].y : c == 2 ? xn[q].z : xn[q].w;
                 const float x1 = c == 0 ? xn[2 + q].x : c == 1 ? xn[2 + q].y : c == 2 ? xn[2 + q].z : xn[2 + q].w;
                 const float x2 = c == 0 ? xn[4 + q].x : c == 1 ? xn[4 + q].y : c == 2 ? xn[4 + q].z : xn[4 + q].w;
-                xs[e] = fb_softplus((x0 + x1) + x2);
+                xs[e] = so_softplus_raw((x0 + x1) + x2);
                 asm volatile("" : "+v"(xs[e]));               // keeps the evaluation in ITS gap (the SLP vectoriser would pair it with
                 T[(16 * st + 8 * q + 4 * half + c) * kB3_TA + i] = xs[e];      // a later gap's element and sink both)
             };
@@ -386,7 +319,7 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
         for (int ct = 0; ct < 3; ++ct) {
             const float bias = a.b1[ct * 32 + i];
 #pragma unroll
-            for (int v = 0; v < 16; ++v) y[ct][v] = fb_softplus(y[ct][v] + bias);
+            for (int v = 0; v < 16; ++v) y[ct][v] = so_softplus_raw(y[ct][v] + bias);
         }
 
         // ---- dW2'[o'][n] += dOut^T z : A = dOut (lane o'), B = z registers, K = the tile's 32 voxels ----------------
@@ -396,15 +329,15 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
 #pragma unroll
             for (int j = 0; j < 8; ++j) gs[j] = dOC[8 * s + j];
             bf16x8 g1, g2, g3;
-            fb_split3(gs, g1, g2, g3);
+            so_split3(gs, g1, g2, g3);
 #pragma unroll
             for (int ct = 0; ct < 3; ++ct) {
                 float zs[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) zs[j] = y[ct][8 * s + j];
                 bf16x8 z1, z2, z3;
-                fb_split3(zs, z1, z2, z3);
-                fb_mfma6(dW2[ct], g1, g2, g3, z1, z2, z3);
+                so_split3(zs, z1, z2, z3);
+                so_mfma6(dW2[ct], g1, g2, g3, z1, z2, z3);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -412,7 +345,7 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
 #pragma unroll
         for (int ct = 0; ct < 3; ++ct)
 #pragma unroll
-            for (int v = 0; v < 16; ++v) y[ct][v] = 1.0f - fb_exp_neg(y[ct][v]);
+            for (int v = 0; v < 16; ++v) y[ct][v] = 1.0f - so_exp_neg_raw(y[ct][v]);
 
         // ---- S3: dZ = dOut W2 ; dY = dZ sigmoid(y) ------------------------------------------------------------------
         f32x16 dY[3];
@@ -423,13 +356,13 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             bf16x8 g1, g2, g3;
-            fb_split3(dOA[s], g1, g2, g3);
+            so_split3(dOA[s], g1, g2, g3);
 #pragma unroll
             for (int ct = 0; ct < 3; ++ct) {
                 const __bf16 *bp = w2t + (size_t)(32 * ct + i) * OPB + 16 * s + 8 * half;
                 const bf16x8 w1_ = *(const bf16x8 *)bp, w2_ = *(const bf16x8 *)(bp + (size_t)C * OPB),
                              w3_ = *(const bf16x8 *)(bp + (size_t)2 * C * OPB);
-                fb_mfma6(dY[ct], g1, g2, g3, w1_, w2_, w3_);
+                so_mfma6(dY[ct], g1, g2, g3, w1_, w2_, w3_);
             }
         }
 #pragma unroll
@@ -496,7 +429,7 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
 #pragma unroll
         for (int ct = 0; ct < 3; ++ct)
 #pragma unroll
-            for (int v = 0; v < 16; ++v) T[(size_t)fb_crow(v, half) * kB3_TY + 32 * ct + i] = dY[ct][v];
+            for (int v = 0; v < 16; ++v) T[(size_t)so_crow(v, half) * kB3_TY + 32 * ct + i] = dY[ct][v];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -557,8 +490,8 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
             float dx[16];
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const bool live = FULL ? true : ((h_b + (v >> 2) < a.H) & (w_b + 2 * half + ((v >> 1) & 1) < a.W) & (d_b + (v & 1) < a.D));
-                dx[v] = live ? dA[ct][v] * (1.0f - fb_exp_neg(aC[ct][v])) : 0.0f;
+                const bool live = FULL ? true : so_creg_live(v, half, h_b, w_b, d_b, a.H, a.W, a.D);
+                dx[v] = live ? dA[ct][v] * (1.0f - so_exp_neg_raw(aC[ct][v])) : 0.0f;
             }
             // g_hw[h][w] += sum over d: registers v, v ^ 1 (carried along the d-walk in the lane's LDS slots)
             {
@@ -594,9 +527,8 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
             if (col_prev >= 0) flush_hw(col_prev);
             col_prev = tile / a.PD;
         }
-        const int pd = tile % a.PD, tq = tile / a.PD;
-        const int pw = tq % a.PW, ph = tq / a.PW;
-        const int h_b = 4 * ph, w_b = 4 * pw, d_b = 2 * pd;
+        int h_b, w_b, d_b;
+        so_patch_origin(tile, a.PW, a.PD, h_b, w_b, d_b);
         if (h_b + 4 <= a.H && w_b + 4 <= a.W && d_b + 2 <= a.D) tile_body(std::true_type{}, h_b, w_b, d_b);     // wave-uniform
         else tile_body(std::false_type{}, h_b, w_b, d_b);
     }
@@ -605,7 +537,7 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
     // ---- the wave's weight / bias gradients -> global (once) -------------------------------------------------------
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-        const int cr = fb_crow(v, half);
+        const int cr = so_crow(v, half);
         const int w2row = fb_w2_row(cr, a.out_dim);
 #pragma unroll
         for (int ct = 0; ct < 3; ++ct) {
@@ -630,27 +562,12 @@ __global__ __launch_bounds__(kB3_WAVES * 64) void field_volume_bwd_b3_kernel(Fie
 
 }  // namespace
 
-// launched by selfocc_field_volume_bwd (field.hip)
-int so_field_volume_bwd_b3(const float *hw, const float *zh, const float *wz, int H, int W, int D, const float *w1,
-                           const float *b1, const float *w2, int out_dim, const float *g_sdf, const float *g_feat,
-                           int feat_stride, float *g_hw, float *g_zh, float *g_wz, float *g_w1, float *g_b1, float *g_w2,
-                           float *g_b2, hipStream_t st) {
-    const long long PH = (H + 3) / 4, PW = (W + 3) / 4, PD = (D + 1) / 2;
-    FieldBwdB3Args a{hw, zh, wz, H, W, D, w1, b1, w2, out_dim, g_sdf, g_feat, feat_stride,
-                     g_hw, g_zh, g_wz, g_w1, g_b1, g_w2, g_b2, (int)(PH * PW * PD), (int)PW, (int)PD,
-                     getenv("SELFOCC_FIELD_BWD_DBG") ? atoi(getenv("SELFOCC_FIELD_BWD_DBG")) : 0};
-    // the attribute is per device: set once per device, and a failure (LDS carve-out refused) is an error, not a silent launch failure
-    static std::atomic<unsigned long long> done_mask{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(done_mask.load(std::memory_order_relaxed) & bit)) {
-        const hipError_t e = hipFuncSetAttribute((const void *)field_volume_bwd_b3_kernel,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-        SO_REQUIRE(e == hipSuccess, "field_volume_bwd: cannot reserve %d bytes of LDS (%s)", 160 * 1024 - 256, hipGetErrorString(e));
-        done_mask.fetch_or(bit, std::memory_order_relaxed);
-    }
+int so_field_volume_bwd_b3(const FieldBwdArgs &a, hipStream_t st) {
     const int blocks = std::min((a.n_tiles + kB3_WAVES - 1) / kB3_WAVES, 256);
-    hipLaunchKernelGGL(field_volume_bwd_b3_kernel, dim3(blocks), dim3(kB3_WAVES * 64), kB3_LDS, st, a);
+    const int e = so_launch_lds<field_volume_bwd_b3_kernel>(dim3(blocks), dim3(kB3_WAVES * 64), kB3_LDS, 160 * 1024 - 256, st, a);
+    if (e != (int)hipSuccess) {      // the LDS carve-out was refused: a named error, not the launch failure that follows from it
+        (void)hipGetLastError();
+        SO_REQUIRE(false, "field_volume_bwd: cannot reserve %d bytes of LDS (%s)", 160 * 1024 - 256, hipGetErrorString((hipError_t)e));
+    }
     return so_launch_status();
 }

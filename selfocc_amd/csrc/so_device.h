@@ -52,20 +52,24 @@ static inline void so_with_const(T v, F &&f) {
 
 // Launch Kernel(a) with `lds` bytes of dynamic LDS.  Above the 48 KB every kernel may use, its limit is raised to `lds_limit`
 // first — once per (device, instantiation): the attribute is per device, and setting it is a driver round trip of tens of
-// microseconds, which at ~45 launches per frame would make the host the bottleneck.
+// microseconds, which at ~45 launches per frame would make the host the bottleneck.  Returns the status of raising the limit
+// (a hipError_t as a plain int, which a caller may drop; a refused reservation is tried again at the next launch).  The launch
+// is issued either way, so a caller that drops the status sees the launch failure in so_launch_status().
 template <auto Kernel, class Args>
-static inline void so_launch_lds(dim3 grid, dim3 block, size_t lds, int lds_limit, hipStream_t st, const Args &a) {
+static inline int so_launch_lds(dim3 grid, dim3 block, size_t lds, int lds_limit, hipStream_t st, const Args &a) {
     static std::atomic<unsigned long long> done_mask{0};
+    hipError_t e = hipSuccess;
     if (lds > 48 * 1024) {
         int dev = 0;
         (void)hipGetDevice(&dev);
         const unsigned long long bit = 1ull << (dev & 63);
         if (!(done_mask.load(std::memory_order_relaxed) & bit)) {
-            (void)hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
-            done_mask.fetch_or(bit, std::memory_order_relaxed);
+            e = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
+            if (e == hipSuccess) done_mask.fetch_or(bit, std::memory_order_relaxed);
         }
     }
     hipLaunchKernelGGL(Kernel, grid, block, lds, st, a);
+    return (int)e;
 }
 
 // so_row_groups (by value through the C ABI): 1 .. 8 groups, row_start[0] = 0, non-decreasing, row_start[n] = T.  Host logic only.

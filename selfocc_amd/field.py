@@ -56,8 +56,9 @@ class FieldVolumeFunction(torch.autograd.Function):
     (``selfocc_field_volume_fwd`` / ``selfocc_field_volume_bwd``).  The forward keeps only its inputs — the
     backward kernel recomputes the activations tile by tile — so the (H*W*D, C) intermediates of the
     op-by-op path (at the nuscenes_occ size 423 / 634 / 845 MB each for C = 64 / 96 / 128) never exist.
-    C = 96 runs the bf16 x 3 kernel (or the 96-wide float32-MFMA one), C = 64 / 128 the width-generic
-    float32-MFMA kernel of csrc/field_bwd_w.hip."""
+    One width-generic float32-MFMA backward (csrc/field_bwd_w.hip) serves C = 64 / 96 / 128; C = 96 takes the
+    bf16 x 3 kernel (csrc/field_bwd_b3.hip) instead where the feature stride is a multiple of 4 and 32-bit
+    indices suffice, unless SELFOCC_FIELD_BWD_B3=0 (read at every call, like SELFOCC_FIELD_B3 of the forward)."""
 
     @staticmethod
     def forward(ctx, hw, zh, wz, w1, b1, w2, b2, size_hwd, feat_stride):

@@ -1,5 +1,7 @@
 """GPU parity: selfocc_field_volume_fwd (tri-plane sum + [Softplus, Linear] x n in one MFMA-f32 kernel) vs the
-torch restatement of the same formula (float64 on CPU; neus_head.py:295-306 / bev_nerf.py:74-95)."""
+torch restatement of the same formula (float64 on CPU; neus_head.py:295-306 / bev_nerf.py:74-95).  At embed_dims 96 with a
+hidden layer the default route is the bf16 x 3 kernel; SELFOCC_FIELD_B3=0 (read at every call) selects the float32-MFMA kernel,
+and the C = 96 cases run on both."""
 import pytest
 import torch
 import torch.nn as nn
@@ -32,7 +34,19 @@ CASES = [
 
 
 @pytest.mark.parametrize("H,W,D,C,n_lin,color,F", CASES)
-def test_field_volume_vs_torch(hip, H, W, D, C, n_lin, color, F):
+def test_field_volume_vs_torch(hip, monkeypatch, H, W, D, C, n_lin, color, F):
+    monkeypatch.delenv("SELFOCC_FIELD_B3", raising=False)
+    check_field_volume(H, W, D, C, n_lin, color, F)
+
+
+@pytest.mark.parametrize("H,W,D,C,n_lin,color,F", [c for c in CASES if c[3] == 96])
+def test_field_volume_f32_kernel_vs_torch(hip, monkeypatch, H, W, D, C, n_lin, color, F):
+    """field_volume_kernel<96, *> (with a hidden layer: the route only SELFOCC_FIELD_B3=0 reaches), the same pass rule"""
+    monkeypatch.setenv("SELFOCC_FIELD_B3", "0")
+    check_field_volume(H, W, D, C, n_lin, color, F)
+
+
+def check_field_volume(H, W, D, C, n_lin, color, F):
     g = torch.Generator().manual_seed(H * 100 + W * 10 + D + C)
     hw, zh, wz = (torch.randn(n, C, generator=g) * 1.5 for n in (H * W, D * H, W * D))
     # exercise every Softplus regime: large negative (series), mid (log), > 20 (identity)

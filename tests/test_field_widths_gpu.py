@@ -1,18 +1,22 @@
-"""The fused field-volume backward (selfocc_field_volume_bwd) at embed_dims 64 and 128: the width-generic float32-MFMA kernel
-of csrc/field_bwd_w.hip against float64 torch autograd of test_field_gpu.reference (which calls no selfocc kernel).
+"""The width-generic float32-MFMA backward of csrc/field_bwd_w.hip (selfocc_field_volume_bwd at embed_dims 64 and 128, and at
+96 with SELFOCC_FIELD_BWD_B3=0, the route of the 96-wide heads the bf16 x 3 kernel does not take) against float64 torch
+autograd of test_field_gpu.reference (which calls no selfocc kernel).
 
 Shapes are the smallest at which each mechanism of the kernel can go wrong: one voxel; patches ragged in all three axes;
 whole patches with one d-patch per column; a stride that is not a multiple of four floats; the full output range; no feature
 gradient; and grids with one tile more than the launch has tile slots, so that a slot walks several tiles and the hw rows of
-a column of d-patches are flushed by several slots.  A slot is one wave at C = 64 (256 blocks x 4 = 1 024 slots, 1 025 tiles
-at 20 x 20 x 82) and a PAIR of waves at C = 128 (512 slots, 513 tiles at 12 x 36 x 38, where the last slots of a block idle
+a column of d-patches are flushed by several slots.  A slot is one wave at C = 64 and 96 (256 blocks x 4 = 1 024 slots, 1 025
+tiles at 20 x 20 x 82) and a PAIR of waves at C = 128 (512 slots, 513 tiles at 12 x 36 x 38, where the last slots of a block idle
 through the block barriers of the others).
 
 Pass rule (the project's rule for this op, tests/test_field_gpu.py): allclose(rtol=1e-3, atol=1e-4 max|g64|) per tensor, no
 element left out.  Per tensor rel-L2 and max|g - g64| / max|g64| go to parity_out/field_widths_parity.jsonl; the logs of the
 first two MI355X sessions are profiles/field_widths_parity.jsonl, and MEASURED holds their values: the second, sharp
 assertion is 10 x the measured value (the convention of tests/test_field_full_size_gpu.py: the margin is for the run-to-run
-order of the atomics)."""
+order of the atomics).
+
+At C = 96 the cases run with SELFOCC_FIELD_BWD_DBG=1 as well: only the bf16 x 3 kernel honours that switch (it drops the zh / wz
+plane-gradient atomics), so zh / wz gradients that pass name the float32 kernel as the one that ran."""
 import functools
 import json
 import os
@@ -29,7 +33,8 @@ pytestmark = pytest.mark.gpu
 D0 = torch.device("cuda:0")
 LOG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "parity_out", "field_widths_parity.jsonl")
 GRADS = ("hw", "zh", "wz", "w1", "b1", "w2", "b2")
-WIDTHS = (64, 128)
+WIDTHS = (64, 96, 128)           # 96: the float32 route, by SELFOCC_FIELD_BWD_B3=0 (run_case)
+GENERIC = (64, 128)              # the widths whose every backward is this kernel
 
 # (H, W, D, out_dim, F)
 CASES = {
@@ -40,7 +45,7 @@ CASES = {
     "5x6x31_F0": (5, 6, 31, 1, 0),              # g_feat absent
     "4x5x11_out20_F19": (4, 5, 11, 20, 19),     # a stride that is not a multiple of 4
     "6x5x4_out32_F31": (6, 5, 4, 32, 31),       # the full output range
-    "20x20x82_F24": (20, 20, 82, 25, 24),       # 1 025 tiles: the 1 024 slots of C = 64, plus one
+    "20x20x82_F24": (20, 20, 82, 25, 24),       # 1 025 tiles: the 1 024 slots of C = 64 / 96, plus one
     "12x36x38_F24": (12, 36, 38, 25, 24),       # 513 tiles: the 512 slots of C = 128, plus one
 }
 BITE = ("20x20x82_F24", "9x7x25_F24")
@@ -59,6 +64,15 @@ MEASURED = {
     (64, "6x5x4_out32_F31"): dict(hw=(2.2e-07, 2.4e-07), zh=(2.2e-07, 1.8e-07), wz=(2.1e-07, 2.8e-07), w1=(1.8e-07, 1.4e-07), b1=(1.6e-07, 1.1e-07), w2=(2.4e-07, 4.2e-07), b2=(1.2e-07, 1.5e-07), sdf=(3.7e-07, 3.9e-07), feat=(2.4e-07, 3.1e-07)),
     (64, "20x20x82_F24"): dict(hw=(2.5e-07, 2.9e-07), zh=(2.2e-07, 2.4e-07), wz=(2.3e-07, 2.2e-07), w1=(6.3e-07, 1.1e-06), b1=(7.1e-07, 1.1e-06), w2=(6.5e-07, 8.8e-07), b2=(5.7e-07, 6.6e-07), sdf=(3.3e-07, 4.9e-07), feat=(2.6e-07, 3.5e-07)),
     (64, "12x36x38_F24"): dict(hw=(2.3e-07, 2.5e-07), zh=(2.3e-07, 2.6e-07), wz=(2.2e-07, 2.1e-07), w1=(4.6e-07, 7.7e-07), b1=(4.6e-07, 5.4e-07), w2=(4.7e-07, 5.8e-07), b2=(4.3e-07, 6.2e-07), sdf=(3.4e-07, 6.5e-07), feat=(2.6e-07, 5.2e-07)),
+    (96, "1x1x1"): dict(hw=(2.7e-07, 3.5e-07), zh=(2.7e-07, 3.5e-07), wz=(2.7e-07, 3.5e-07), w1=(1.7e-07, 4.3e-07), b1=(1.6e-07, 4.5e-07), w2=(2.2e-07, 2.2e-07), b2=(0.0e+00, 0.0e+00), sdf=(2.3e-08, 2.3e-08)),
+    (96, "5x3x3_F24"): dict(hw=(2.3e-07, 2.7e-07), zh=(2.2e-07, 2.6e-07), wz=(2.4e-07, 2.3e-07), w1=(1.7e-07, 2.5e-07), b1=(1.3e-07, 1.8e-07), w2=(2.2e-07, 2.0e-07), b2=(7.8e-08, 1.2e-07), sdf=(3.0e-07, 3.3e-07), feat=(2.5e-07, 2.5e-07)),
+    (96, "8x8x2_F4"): dict(hw=(2.5e-07, 2.8e-07), zh=(2.7e-07, 2.7e-07), wz=(2.3e-07, 1.8e-07), w1=(2.3e-07, 4.0e-07), b1=(1.9e-07, 2.3e-07), w2=(3.4e-07, 3.7e-07), b2=(2.4e-07, 1.9e-07), sdf=(2.5e-07, 3.6e-07), feat=(2.6e-07, 3.2e-07)),
+    (96, "9x7x25_F24"): dict(hw=(2.5e-07, 2.3e-07), zh=(2.5e-07, 2.6e-07), wz=(2.4e-07, 2.9e-07), w1=(2.5e-07, 3.8e-07), b1=(2.3e-07, 4.3e-07), w2=(2.7e-07, 3.3e-07), b2=(1.7e-07, 1.7e-07), sdf=(2.8e-07, 5.9e-07), feat=(2.4e-07, 3.5e-07)),
+    (96, "5x6x31_F0"): dict(hw=(2.4e-07, 2.5e-07), zh=(2.0e-07, 2.6e-07), wz=(2.1e-07, 2.4e-07), w1=(2.4e-07, 3.8e-07), b1=(2.6e-07, 2.8e-07), w2=(3.6e-07, 4.7e-07), b2=(1.4e-07, 1.4e-07), sdf=(3.8e-07, 8.1e-07)),
+    (96, "4x5x11_out20_F19"): dict(hw=(2.5e-07, 2.8e-07), zh=(2.4e-07, 3.4e-07), wz=(2.4e-07, 2.5e-07), w1=(2.3e-07, 3.5e-07), b1=(2.0e-07, 2.3e-07), w2=(2.3e-07, 3.0e-07), b2=(7.6e-08, 1.2e-07), sdf=(2.1e-07, 2.2e-07), feat=(2.3e-07, 3.3e-07)),
+    (96, "6x5x4_out32_F31"): dict(hw=(2.5e-07, 3.0e-07), zh=(2.4e-07, 2.4e-07), wz=(2.6e-07, 2.2e-07), w1=(2.2e-07, 2.7e-07), b1=(2.2e-07, 2.3e-07), w2=(2.5e-07, 3.2e-07), b2=(8.7e-08, 1.1e-07), sdf=(2.8e-07, 1.7e-07), feat=(2.5e-07, 4.8e-07)),
+    (96, "20x20x82_F24"): dict(hw=(2.7e-07, 3.5e-07), zh=(2.4e-07, 2.7e-07), wz=(2.4e-07, 2.2e-07), w1=(6.0e-07, 9.9e-07), b1=(6.0e-07, 7.0e-07), w2=(6.5e-07, 9.7e-07), b2=(5.0e-07, 6.0e-07), sdf=(3.1e-07, 5.1e-07), feat=(2.3e-07, 3.9e-07)),
+    (96, "12x36x38_F24"): dict(hw=(2.5e-07, 3.0e-07), zh=(2.5e-07, 2.7e-07), wz=(2.4e-07, 2.7e-07), w1=(4.5e-07, 9.2e-07), b1=(4.3e-07, 5.3e-07), w2=(5.1e-07, 8.4e-07), b2=(4.7e-07, 5.8e-07), sdf=(3.1e-07, 4.7e-07), feat=(2.3e-07, 3.5e-07)),
     (128, "1x1x1"): dict(hw=(2.2e-07, 2.8e-07), zh=(2.2e-07, 2.8e-07), wz=(2.2e-07, 2.8e-07), w1=(1.1e-07, 1.4e-07), b1=(8.4e-08, 1.2e-07), w2=(2.7e-07, 3.7e-07), b2=(0.0e+00, 0.0e+00), sdf=(1.7e-06, 1.7e-06)),
     (128, "5x3x3_F24"): dict(hw=(2.7e-07, 2.5e-07), zh=(2.7e-07, 3.5e-07), wz=(2.5e-07, 2.8e-07), w1=(2.0e-07, 1.9e-07), b1=(1.6e-07, 1.5e-07), w2=(2.7e-07, 3.3e-07), b2=(6.0e-08, 7.2e-08), sdf=(2.7e-07, 3.8e-07), feat=(3.4e-07, 3.8e-07)),
     (128, "8x8x2_F4"): dict(hw=(2.6e-07, 3.1e-07), zh=(2.6e-07, 1.7e-07), wz=(2.6e-07, 3.0e-07), w1=(1.9e-07, 3.2e-07), b1=(1.5e-07, 1.3e-07), w2=(2.5e-07, 2.7e-07), b2=(3.2e-08, 2.6e-08), sdf=(4.0e-07, 4.8e-07), feat=(3.9e-07, 4.7e-07)),
@@ -116,15 +130,22 @@ def reference64(planes, lins, size, out_dim, gs, gf):
 
 @functools.lru_cache(maxsize=None)
 def run_case(C, name):
-    """One case, once: inputs, the float64 reference and the kernel's results (shared by the tests; nothing mutates them)."""
+    """One case, once: inputs, the float64 reference and the kernel's results (shared by the tests; nothing mutates them).
+    The switches that select the kernel are part of what is cached: they are set here, around the launch."""
     H, W, D, out_dim, F = CASES[name]
     planes, lins, gs, gf = make_inputs(C, name)
     out64, g64 = reference64(planes, lins, (H, W, D), out_dim, gs, gf)
     dev = [t.detach().clone().to(D0).requires_grad_(True)
            for t in (*planes, lins[0].weight, lins[0].bias, lins[1].weight, lins[1].bias)]
-    sdf, feat = FieldVolumeFunction.apply(*dev, (H, W, D), F)
-    torch.autograd.backward([sdf, feat] if F else [sdf], [gs.to(D0), gf.to(D0)] if F else [gs.to(D0)])
-    got = [t.grad.cpu() for t in dev]
+    with pytest.MonkeyPatch.context() as mp:
+        mp.delenv("SELFOCC_FIELD_BWD_B3", raising=False)
+        mp.delenv("SELFOCC_FIELD_BWD_DBG", raising=False)
+        if C == 96:
+            mp.setenv("SELFOCC_FIELD_BWD_B3", "0")
+            mp.setenv("SELFOCC_FIELD_BWD_DBG", "1")       # the float32 kernel ignores it; the b3 kernel would leave zh / wz zero
+        sdf, feat = FieldVolumeFunction.apply(*dev, (H, W, D), F)
+        torch.autograd.backward([sdf, feat] if F else [sdf], [gs.to(D0), gf.to(D0)] if F else [gs.to(D0)])
+        got = [t.grad.cpu() for t in dev]
     return dict(planes=planes, lins=lins, gs=gs, gf=gf, out64=out64, g64=g64, got=got, sdf=sdf.detach().cpu(),
                 feat=feat.detach().cpu() if F else None)
 
@@ -148,7 +169,7 @@ def test_backward_vs_float64_autograd(hip, C, name):
     errs["sdf"] = err(r["sdf"], r["out64"][..., 0])
     if F and out_dim > 1:
         errs["feat"] = err(r["feat"][..., :out_dim - 1], r["out64"][..., 1:])
-    slots = 256 * 4 * 64 // C
+    slots = 512 if C == 128 else 1024
     log_record(dict(C=C, case=name, size=[H, W, D], out_dim=out_dim, F=F, tiles=n_tiles(H, W, D), slots=slots, err=errs))
     print(C, name, errs)
     # forward outputs: the rule of test_field_volume_vs_torch
@@ -161,6 +182,8 @@ def test_backward_vs_float64_autograd(hip, C, name):
     for n, a, b in zip(GRADS, r["got"], r["g64"]):
         assert a.shape == b.shape
         assert passes(a, b), (C, name, n, errs[n])
+    if C == 96:                               # the float32 kernel ran: SELFOCC_FIELD_BWD_DBG=1 took no zh / wz gradient away
+        assert r["got"][1].abs().max() > 0 and r["got"][2].abs().max() > 0
     assert set(errs) == set(MEASURED[(C, name)])
     for n, e in errs.items():                 # the sharp bound: 10 x the measured value
         m = MEASURED[(C, name)][n]
@@ -198,7 +221,7 @@ def _abi_call(C, H, W, D, out_dim, fill=0.0, seed=0):
     return rc, grads
 
 
-@pytest.mark.parametrize("C", WIDTHS)
+@pytest.mark.parametrize("C", GENERIC)
 def test_c_abi_without_feature_gradient(hip, C):
     """g_feat = NULL, out_dim = 4: the output layer's feature rows receive exactly nothing, the SDF row something."""
     rc, g = _abi_call(C, 6, 7, 5, 4)
@@ -218,7 +241,7 @@ def test_c_abi_refuses_other_widths(hip, C):
         assert torch.all(t == 7.0)            # no gradient buffer was touched
 
 
-@pytest.mark.parametrize("C", WIDTHS)
+@pytest.mark.parametrize("C", GENERIC)
 def test_through_the_field(hip, C):
     """SDFField at the 32 x 32 x 12 mapping of test_sdffield_fused_equals_unfused: under grad it takes FieldVolumeFunction,
     its gradients equal the op-by-op route's, and inference is unchanged."""
