@@ -635,6 +635,8 @@ int selfocc_ssim_bwd(const float *x, const float *y, const int64_t *x_strides, c
  * mean / rstd (rows) are optional outputs of the forward (both or neither) and inputs of the backward.
  * The backward writes dx (rows, C), dgamma (C), dbeta (C) (overwritten, deterministic) and needs
  * selfocc_layernorm_bwd_workspace(rows, C) bytes of device scratch.
+ * x, y, dy, dx, gamma and beta must be 16-byte aligned (the kernels move float4s): the forward and backward entries, grouped
+ * and not, refuse any other pointer before anything is launched, and the message names it.
  * ---------------------------------------------------------------------------------- */
 int selfocc_layernorm_fwd(const float *x, const float *gamma, const float *beta, float *y, float *mean,
                           float *rstd, int64_t rows, int32_t C, float eps, void *stream);

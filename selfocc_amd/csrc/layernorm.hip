@@ -149,11 +149,16 @@ int ln_groups(const so_row_groups &in, long long rows, so_group_table *out) {
     return 0;
 }
 
+// the kernels move float4s: every (rows, C) tensor and parameter vector must sit on a 16-byte boundary (C % 4 == 0 keeps every
+// row and every group's parameters there once the base is); a contiguous view at an odd storage offset is refused, by name
+#define SO_LN_ALIGNED(who, p) SO_REQUIRE(((uintptr_t)(p) & 15) == 0, who ": " #p " must be 16-byte aligned")
+
 int ln_fwd_launch(const float *x, const float *gamma, const float *beta, float *y, float *mean, float *rstd, long long rows,
                   int C, float eps, const so_group_table &gr, hipStream_t st) {
     if (rows == 0) return 0;
     SO_REQUIRE(x && gamma && beta && y, "layernorm: NULL pointer");
     SO_REQUIRE((mean == nullptr) == (rstd == nullptr), "layernorm: mean and rstd go together");
+    SO_LN_ALIGNED("layernorm", x); SO_LN_ALIGNED("layernorm", gamma); SO_LN_ALIGNED("layernorm", beta); SO_LN_ALIGNED("layernorm", y);
     hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(gr.unit_start[gr.n]), dim3(256), 0, st, x, gamma, beta, y, mean, rstd, gr, C, eps);
     return so_launch_status();
 }
@@ -167,6 +172,8 @@ int ln_bwd_launch(const float *x, const float *gamma, const float *mean, const f
         return (int)hipMemsetAsync(dbeta, 0, (size_t)gr.n * C * sizeof(float), st);
     }
     SO_REQUIRE(x && gamma && mean && rstd && dy && dx, "layernorm_bwd: NULL pointer");
+    SO_LN_ALIGNED("layernorm_bwd", x); SO_LN_ALIGNED("layernorm_bwd", gamma); SO_LN_ALIGNED("layernorm_bwd", dy);
+    SO_LN_ALIGNED("layernorm_bwd", dx);
     const int nb = gr.unit_start[gr.n];
     SO_REQUIRE(workspace && workspace_bytes >= (size_t)nb * 2 * C * sizeof(float), "layernorm_bwd: workspace too small");
     hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nb), dim3(256), 0, st, x, gamma, mean, rstd, dy, dx, (float *)workspace, gr, C);

@@ -52,6 +52,14 @@ def constant_init(module, val, bias=0):
 GROUPED_LN_CALLS = [0]             # forward calls served by the grouped LayerNorm kernel (tests read this)
 
 
+def _aligned(t):
+    """`t` contiguous with a 16-byte-aligned data pointer (the LayerNorm kernels move float4s and their C entries refuse anything
+    else): itself where it already is, else a copy in a fresh allocation — a contiguous view keeps its storage offset
+    (``buf[1:1 + n]``, a slice of a ``cat`` / ``split`` buffer whose rows are no multiple of four floats)."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 class _LayerNormFunction(torch.autograd.Function):
     """LayerNorm over the channel dimension (csrc/layernorm.hip).  ``sizes`` None: one (weight, bias), selfocc_layernorm_fwd /
     _bwd.  ``sizes`` = host integers (no upload, no synchronisation): one (weight, bias) pair per row group — the planes of a
@@ -61,14 +69,14 @@ class _LayerNormFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, sizes, eps, *wb):
         C = x.shape[-1]
-        x2 = x.reshape(-1, C).contiguous().float()
+        x2 = _aligned(x.reshape(-1, C).float())
         rows = x2.shape[0]
         assert sizes is None or sum(sizes) == rows, (sizes, rows)
         y = torch.empty_like(x2)
         need = any(ctx.needs_input_grad)
         mean = torch.empty(rows, device=x.device) if need else None
         rstd = torch.empty(rows, device=x.device) if need else None
-        w, b = stack_rows(wb[0::2]).contiguous().float(), stack_rows(wb[1::2]).contiguous().float()      # (G * C,) = [G][C]
+        w, b = _aligned(stack_rows(wb[0::2]).float()), _aligned(stack_rows(wb[1::2]).float())      # (G * C,) = [G][C]
         args = (ptr(x2), ptr(w), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, C, float(eps))
         if sizes is None:
             check(lib().selfocc_layernorm_fwd(*args, current_stream(x.device)), "selfocc_layernorm_fwd")
@@ -88,8 +96,8 @@ class _LayerNormFunction(torch.autograd.Function):
         x2, mean, rstd, *ws = ctx.saved_tensors
         rows, C = x2.shape
         G = len(ws)
-        w = stack_rows(ws).contiguous().float()
-        dy2 = dy.reshape(rows, C).contiguous().float()
+        w = _aligned(stack_rows(ws).float())
+        dy2 = _aligned(dy.reshape(rows, C).float())
         dx = torch.empty_like(x2)
         dg, db = x2.new_empty(G, C), x2.new_empty(G, C)
         groups = () if ctx.sizes is None else (row_groups(ctx.sizes),)

@@ -1,5 +1,10 @@
 """GPU: selfocc_layernorm_fwd / _bwd (csrc/layernorm.hip, behind FastLayerNorm) against float64 torch
-LayerNorm — the op the reference's encoder layers build through mmcv's build_norm_layer(dict(type='LN'))."""
+LayerNorm — the op the reference's encoder layers build through mmcv's build_norm_layer(dict(type='LN')).
+
+These are the shipped shape and the module's routes at loose bounds.  The sharp checks — all 32 widths, the launch edges,
+ill-conditioned and constant rows, float64 at a few times the float32 port's own error and a bit-exact model of the kernels — are
+tests/test_layernorm_sharp_gpu.py on the table of tests/layernorm_cases.py (what that table is worth:
+tests/test_layernorm_cases_cpu.py)."""
 import pytest
 import torch
 

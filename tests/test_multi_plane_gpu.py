@@ -4,7 +4,9 @@
   row normalised with the (gamma, beta) of the group it lies in — against float64 at the bounds tests/test_layernorm_gpu.py
   uses for the ungrouped kernels, on row splits that put group boundaries inside, at and next to the 8-row blocks; every group
   gets its own seed, so a row served with another group's parameters is an O(1) error; empty groups give exact zeros; one
-  group is the ungrouped entry bit for bit; the backward is run-to-run bit-identical.
+  group is the ungrouped entry bit for bit; the backward is run-to-run bit-identical.  (Every group of a split against the
+  ungrouped entry bit for bit, at more widths and with a group past the 2 048-block cap by one row, and the sharp float64
+  bounds: tests/test_layernorm_sharp_gpu.py, tests/layernorm_cases.py.)
 * the module fixture and the two encoder fixtures the REAL reference classes wrote (tests/golden/make_golden_multi_plane.py).
 * launch counts, sync-freedom, torch.inference_mode().
 """
