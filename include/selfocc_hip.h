@@ -832,13 +832,14 @@ int selfocc_linear_wgrad_grouped_flags(const float *dy, const float *x, float *d
                                        so_row_groups groups, void *workspace, size_t workspace_bytes, uint32_t flags, void *stream);
 
 /* ------------------------------------------------------------------------------------
- * Fused temporal reprojection photometric term.  Replaces the per-sample part of
+ * Fused temporal reprojection photometric term: replaces the per-sample part of
  * ReprojLossMonoMultiNewCombine.reproj_loss (loss/reproj_loss_mono_multi_new_combine.py
  * :108-187 and the weighted colour composite :190-201) for one camera.
- *   weights, ts (R, S); pix (R, 2) pixel (u, v); T_prev / T_next (4,4) row-major;
- *   img_* (3, Hi, Wi) planar float32; curr_rgb (R, 3) = bilinear(curr image, pix)
- * outputs per ray: l1 (R) = sum_s w' * diff, rgb_combine (R, 3), any_valid (R) in {0,1}
- * (w' = masked, per-ray renormalised weights).
+ * so_reproj_args is the planar 3-channel form of so_reproj_c_args (below, which states the
+ * semantics): C = 3, curr_rgb / rgb_combine are its curr / combine, and
+ *   img_* (3, Hi, Wi) planar float32, of ANY base alignment (no img_stride).
+ * Both forms run one kernel and share every refusal but those of C, img_stride and the
+ * image alignment, which the planar form cannot fail.
  * ---------------------------------------------------------------------------------- */
 typedef struct so_reproj_args {
     const float *weights, *ts, *deltas; /* deltas may be NULL (:111-116)               */
@@ -859,7 +860,7 @@ int selfocc_reproj_bwd(const so_reproj_args *args, const float *g_l1,
 
 /* ------------------------------------------------------------------------------------
  * The fused temporal reprojection term on images of C channels (the `dims` knob of both reprojection losses, e.g. the
- * feature-metric loss on (C, Hi, Wi) feature maps): the semantics of selfocc_reproj_fwd / _bwd with 3 replaced by C.
+ * feature-metric loss on (C, Hi, Wi) feature maps).  This comment is the contract of selfocc_reproj_fwd / _bwd as well.
  *   weights, ts (R, S); deltas (R, S) or NULL; pix (R, 2) pixel (u, v); curr (R, C) = the current image at the ray pixels;
  *   T_prev / T_next (4,4) row-major; img_prev / img_next CHANNEL-LAST (Hi, Wi, img_stride) float32, base 16-byte aligned,
  *   img_stride % 4 == 0 and >= C.  Channels C .. img_stride-1 of a pixel are padding: no output depends on them (a NaN

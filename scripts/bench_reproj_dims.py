@@ -3,8 +3,8 @@ torch-op form of the same reference lines (tests/reproj_dims_port.py, run on the
 training shape per camera: R = 4 800 rays (48 x 100 lattice) x S = 256 samples, img_size = [768, 1600].
 
 Cases:  C = 3 through the 3-channel entry (selfocc_reproj_fwd, planar 768 x 1600 images: what dims == 3 runs),
-        C = 3 through the channel-generic entry on the same images (what the generic kernel costs beside the specialised one;
-        nothing is routed this way), C = 16 and C = 96 on 96 x 200 feature maps.
+        C = 3 through the channel-last entry on the same images (what the kernel's channel-last tap fetch costs beside its
+        planar one; nothing is routed this way), C = 16 and C = 96 on 96 x 200 feature maps.
 Per case, alternated inside every round: the kernel forward, the kernel forward + backward, the torch form forward, the torch
 form forward + backward (autograd), and for the generic entry the two channel_last copies the loss makes once per camera and
 call (the kernel figures are taken on images that are already channel-last).  A figure is the median over the warm rounds of the

@@ -1,8 +1,17 @@
-// reproj_device.h — the per-sample geometry and weight arithmetic that reproj.hip and reproj_pick.hip share: ONE definition,
-// so that the pick kernel's normalised weights are, bit for bit, the ones selfocc_reproj_fwd writes to `wnorm`.
+// reproj_device.h — what the sampling kernel (reproj.hip: both image forms, all four entries) and reproj_pick.hip share: the
+// per-sample geometry and weight arithmetic and the samples-per-lane ladder.  ONE definition, so that the pick kernel's
+// normalised weights are, bit for bit, the ones selfocc_reproj_fwd / selfocc_reproj_c_fwd write to `wnorm`.
 // Line numbers refer to the reference's loss/reproj_loss_mono_multi_new_combine.py.
 #pragma once
 #include "so_device.h"
+
+// Host: the samples-per-lane instance of S (1 <= S <= 512) as a compile-time constant, f(so_int<M>) with M the smallest of
+// 1, 2, 4, 8 that has 64 M >= S.  Lane l of a ray's wave owns samples l M .. l M + M - 1 in every kernel launched through it.
+template <class F>
+static inline void so_with_samples_per_lane(int S, F &&f) {
+    const int m = (S + 63) / 64;
+    so_with_const<int, 1, 2, 4, 8>(m <= 2 ? m : m <= 4 ? 4 : 8, f);
+}
 
 namespace {
 

@@ -109,14 +109,10 @@ extern "C" int selfocc_reproj_pick_fwd(const so_reproj_pick_args *args, void *st
     SO_REQUIRE(a.pick_index && a.pick_value, "reproj_pick: NULL output pointer");
     SO_REQUIRE(a.img_h > 0 && a.img_w > 0, "reproj_pick: bad image size");
     if (a.R == 0) return 0;
-    const int m = (a.S + 63) / 64;              // the instance selfocc_reproj_fwd takes for this S: same lane ownership
     const int blocks = (a.R + 3) / 4;
-#define SO_L(MM) hipLaunchKernelGGL((reproj_pick_kernel<MM>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a)
-    if (m <= 1) SO_L(1);
-    else if (m <= 2) SO_L(2);
-    else if (m <= 4) SO_L(4);
-    else SO_L(8);
-#undef SO_L
+    so_with_samples_per_lane(a.S, [&](auto MM) {    // the instance selfocc_reproj_fwd takes for this S: same lane ownership
+        hipLaunchKernelGGL((reproj_pick_kernel<decltype(MM)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    });
     return so_launch_status();
 }
 

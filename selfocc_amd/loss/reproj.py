@@ -7,10 +7,10 @@ is ONE fused HIP launch per camera (reproj.py -> csrc/reproj.hip); SSIM, the aut
 minimum and the means stay in torch on the (R, 3) lattice images.
 
 ``dims`` (default 3) is the channel count of the images that are warped, as in the reference.  With 3-channel images and
-``dims == 3`` the planar 3-channel kernel runs.  Any other count (``dims=K`` with ``curr_imgs / prev_imgs / next_imgs``
-mapped to K-channel feature maps in ``input_dict``: the feature-metric reprojection loss) goes through the channel-generic
-kernel (csrc/reproj_c.hip) on channel-last copies of the previous / next maps, made once per camera and call; the maps may
-have any resolution, pixels are normalised by ``img_size``.
+``dims == 3`` the kernel reads the planar images as they are.  Any other count (``dims=K`` with ``curr_imgs / prev_imgs /
+next_imgs`` mapped to K-channel feature maps in ``input_dict``: the feature-metric reprojection loss) goes through the same
+kernel's channel-last tap fetch on channel-last copies of the previous / next maps, made once per camera and call; the maps
+may have any resolution, pixels are normalised by ``img_size``.
 """
 import numpy as np
 import torch
@@ -111,8 +111,8 @@ class _ReprojBase(BaseLoss):
 
     def _sampler(self, curr_imgs, prev_imgs, next_imgs, shard):
         """-> (the per-sample Function, what turns one camera's previous / next image into its image argument).
-        3-channel images with dims == 3: the planar kernel on the images as they are.  Otherwise the images must all have
-        ``dims`` channels, and the channel-generic kernel runs on channel-last copies."""
+        3-channel images with dims == 3: the planar form, on the images as they are.  Otherwise the images must all have
+        ``dims`` channels, and the kernel runs on channel-last copies."""
         chans = tuple(int(x.shape[2]) for x in (curr_imgs, prev_imgs, next_imgs))
         if self.dims == 3 and chans == (3, 3, 3):
             return ReprojSampleFunction, lambda img: img.float()

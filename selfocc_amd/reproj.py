@@ -1,71 +1,14 @@
-"""Host side of the fused reprojection sampling (selfocc_reproj_fwd / _bwd): the
-per-sample part of ReprojLossMonoMultiNewCombine.reproj_loss
+"""Host side of the fused reprojection sampling: the per-sample part of ReprojLossMonoMultiNewCombine.reproj_loss
 (loss/reproj_loss_mono_multi_new_combine.py:108-201) for one camera, and of the arg-max pick of the mono loss's
-``sdf_loss`` term (selfocc_reproj_pick_fwd / _bwd; loss/reproj_loss_mono_multi_new.py:265-270).  Images of a channel
-count other than 3 (the losses' ``dims`` knob) go through selfocc_reproj_c_fwd / _bwd on channel-last images."""
+``sdf_loss`` term (selfocc_reproj_pick_fwd / _bwd; loss/reproj_loss_mono_multi_new.py:265-270).  The sampling is one kernel
+and, here, one Function body with two image forms: planar 3-channel images through selfocc_reproj_fwd / _bwd, channel-last
+images of any channel count (the losses' ``dims`` knob) through selfocc_reproj_c_fwd / _bwd."""
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import abi
 from ._lib import lib, check, ptr, current_stream
-
-
-def _args(weights, ts, deltas, pix, curr_rgb, T_prev, T_next, img_prev, img_next, img_h, img_w):
-    R, S = weights.shape
-    a = abi.SoReprojArgs()
-    a.weights, a.ts = ptr(weights), ptr(ts)
-    a.deltas = ptr(deltas)
-    a.pix, a.curr_rgb = ptr(pix), ptr(curr_rgb)
-    a.T_prev, a.T_next = ptr(T_prev), ptr(T_next)
-    a.img_prev, a.img_next = ptr(img_prev), ptr(img_next)
-    a.R, a.S = R, S
-    a.Hi, a.Wi = img_prev.shape[-2], img_prev.shape[-1]
-    a.img_h, a.img_w = float(img_h), float(img_w)
-    return a
-
-
-class ReprojSampleFunction(Function):
-    """(weights (R,S), ts (R,S), deltas (R,S)|None, pix (R,2), curr_rgb (R,3), T_prev (4,4),
-    T_next (4,4), img_prev (3,Hi,Wi), img_next (3,Hi,Wi), img_h, img_w)
-       -> l1 (R), rgb_combine (R,3), any_valid (R).   Differentiable wrt ``weights`` only
-    (ts / pixels / matrices / images are constants of the loss in the reference too)."""
-
-    @staticmethod
-    def forward(ctx, weights, ts, deltas, pix, curr_rgb, T_prev, T_next, img_prev, img_next, img_h, img_w):
-        if not weights.is_cuda:
-            raise RuntimeError("ReprojSampleFunction needs CUDA(HIP) tensors: selfocc_amd has no CPU fallback")
-        f = lambda t: None if t is None else t.detach().contiguous().float()
-        tens = [f(t) for t in (weights, ts, deltas, pix, curr_rgb, T_prev, T_next, img_prev, img_next)]
-        a = _args(*tens, img_h, img_w)
-        R = tens[0].shape[0]
-        dev = weights.device
-        l1 = torch.empty(R, device=dev)
-        comb = torch.empty(R, 3, device=dev)
-        anyv = torch.empty(R, device=dev)
-        a.l1, a.rgb_combine, a.any_valid = ptr(l1), ptr(comb), ptr(anyv)
-        check(lib().selfocc_reproj_fwd(a, current_stream(dev)), "selfocc_reproj_fwd")
-        # saved through autograd (version-counter checks, saved-tensor hooks): an in-place change of `weights`
-        # between forward and backward is an error, not a silent mismatch
-        ctx.has_deltas = tens[2] is not None
-        ctx.save_for_backward(*[t for t in tens if t is not None])
-        ctx.hw = (img_h, img_w)
-        ctx.mark_non_differentiable(anyv)
-        return l1, comb, anyv
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_l1, g_comb, _g_any):
-        tens = list(ctx.saved_tensors)
-        if not ctx.has_deltas:
-            tens.insert(2, None)
-        a = _args(*tens, *ctx.hw)
-        g_l1 = g_l1.contiguous().float()
-        g_comb = g_comb.contiguous().float()
-        g_w = torch.zeros_like(tens[0])
-        check(lib().selfocc_reproj_bwd(a, ptr(g_l1), ptr(g_comb), ptr(g_w), current_stream(g_w.device)),
-              "selfocc_reproj_bwd")
-        return (g_w,) + (None,) * 10
 
 
 class ChannelLastImage:
@@ -91,71 +34,107 @@ def channel_last(img):
     return ChannelLastImage(data, C)
 
 
-def _args_c(weights, ts, deltas, pix, curr, T_prev, T_next, img_prev, img_next, C, img_h, img_w):
-    a = abi.SoReprojCArgs()
-    a.weights, a.ts, a.deltas = ptr(weights), ptr(ts), ptr(deltas)
-    a.pix, a.curr = ptr(pix), ptr(curr)
+def _args(tens, C, img_h, img_w):
+    """tens = [weights, ts, deltas | None, pix, curr, T_prev, T_next, img_prev, img_next] -> the struct of the image form:
+    so_reproj_args for planar (3, Hi, Wi) images (C is None), so_reproj_c_args for channel-last (Hi, Wi, stride) ones"""
+    weights, ts, deltas, pix, curr, T_prev, T_next, img_prev, img_next = tens
+    a = abi.SoReprojArgs() if C is None else abi.SoReprojCArgs()
+    a.weights, a.ts, a.deltas, a.pix = ptr(weights), ptr(ts), ptr(deltas), ptr(pix)
     a.T_prev, a.T_next = ptr(T_prev), ptr(T_next)
     a.img_prev, a.img_next = ptr(img_prev), ptr(img_next)
     a.R, a.S = weights.shape
-    a.Hi, a.Wi, a.img_stride = img_prev.shape
-    a.C = C
+    if C is None:
+        a.curr_rgb = ptr(curr)
+        a.Hi, a.Wi = img_prev.shape[1:]
+    else:
+        a.curr, a.C = ptr(curr), C
+        a.Hi, a.Wi, a.img_stride = img_prev.shape
     a.img_h, a.img_w = float(img_h), float(img_w)
     return a
 
 
-class ReprojSampleCFunction(Function):
+class _ReprojSample(Function):
+    """The one body of ReprojSampleFunction / ReprojSampleCFunction.  A subclass names its entries (``who``), says whether
+    its images are planar and turns an image argument into the float32 tensor whose address the entry gets, and C."""
+
+    @classmethod
+    def forward(cls, ctx, weights, ts, deltas, pix, curr, T_prev, T_next, img_prev, img_next, img_h, img_w):
+        if not weights.is_cuda:
+            raise RuntimeError(f"{cls.__name__} needs CUDA(HIP) tensors: selfocc_amd has no CPU fallback")
+        f = lambda t: None if t is None else t.detach().contiguous().float()
+        weights, ts, deltas, pix, curr, T_prev, T_next = (f(t) for t in (weights, ts, deltas, pix, curr, T_prev, T_next))
+        (img_prev, C), (img_next, C_next) = cls._image(img_prev), cls._image(img_next)
+        R, S = weights.shape
+        who = cls.who
+        if C_next != C or img_next.shape != img_prev.shape:
+            raise ValueError(f"{who}: img_prev {tuple(img_prev.shape)} (C = {C}) and img_next {tuple(img_next.shape)} "
+                             f"(C = {C_next}) differ")
+        if curr.shape != (R, C) or pix.shape != (R, 2) or ts.shape != (R, S) or (deltas is not None and deltas.shape != (R, S)):
+            raise ValueError(f"{who}: need curr (R, C) = {(R, C)}, pix (R, 2) and ts / deltas of the shape of weights "
+                             f"{(R, S)}; got curr {tuple(curr.shape)}, pix {tuple(pix.shape)}, ts {tuple(ts.shape)}")
+        if T_prev.numel() != 16 or T_next.numel() != 16:
+            raise ValueError(f"{who}: the transforms must be (4, 4)")
+        tens = [weights, ts, deltas, pix, curr, T_prev, T_next, img_prev, img_next]
+        ctx.form = (None if cls.planar else C, img_h, img_w)
+        a = _args(tens, *ctx.form)
+        dev = weights.device
+        l1 = torch.empty(R, device=dev)
+        comb = torch.empty(R, C, device=dev)
+        anyv = torch.empty(R, device=dev)
+        a.l1, a.any_valid = ptr(l1), ptr(anyv)
+        if cls.planar:
+            a.rgb_combine = ptr(comb)
+        else:
+            a.combine = ptr(comb)
+        check(getattr(lib(), f"selfocc_{who}_fwd")(a, current_stream(dev)), f"selfocc_{who}_fwd")
+        # saved through autograd (version-counter checks, saved-tensor hooks): an in-place change of `weights`
+        # between forward and backward is an error, not a silent mismatch
+        ctx.has_deltas = deltas is not None
+        ctx.save_for_backward(*[t for t in tens if t is not None])
+        ctx.mark_non_differentiable(anyv)
+        return l1, comb, anyv
+
+    @classmethod
+    @once_differentiable
+    def backward(cls, ctx, g_l1, g_comb, _g_any):
+        tens = list(ctx.saved_tensors)
+        if not ctx.has_deltas:
+            tens.insert(2, None)
+        a = _args(tens, *ctx.form)
+        g_l1 = g_l1.contiguous().float()
+        g_comb = g_comb.contiguous().float()
+        g_w = torch.zeros_like(tens[0])
+        check(getattr(lib(), f"selfocc_{cls.who}_bwd")(a, ptr(g_l1), ptr(g_comb), ptr(g_w), current_stream(g_w.device)),
+              f"selfocc_{cls.who}_bwd")
+        return (g_w,) + (None,) * 10
+
+
+class ReprojSampleFunction(_ReprojSample):
+    """(weights (R,S), ts (R,S), deltas (R,S)|None, pix (R,2), curr_rgb (R,3), T_prev (4,4),
+    T_next (4,4), img_prev (3,Hi,Wi), img_next (3,Hi,Wi), img_h, img_w)
+       -> l1 (R), rgb_combine (R,3), any_valid (R), through selfocc_reproj_fwd / _bwd on the planar images as they are.
+    Differentiable wrt ``weights`` only (ts / pixels / matrices / images are constants of the loss in the reference too)."""
+    who, planar = "reproj", True
+
+    @staticmethod
+    def _image(img):
+        if img.dim() != 3 or img.shape[0] != 3:
+            raise ValueError(f"reproj: need planar (3, Hi, Wi) images, got {tuple(img.shape)}")
+        return img.detach().contiguous().float(), 3
+
+
+class ReprojSampleCFunction(_ReprojSample):
     """ReprojSampleFunction on images of C channels (selfocc_reproj_c_fwd / _bwd):
     (weights (R,S), ts (R,S), deltas (R,S)|None, pix (R,2), curr (R,C), T_prev (4,4), T_next (4,4), img_prev, img_next,
     img_h, img_w) -> l1 (R), combine (R,C), any_valid (R).  ``img_prev`` / ``img_next`` are ChannelLastImage (convert an
     image once with ``channel_last`` where it is sampled more than once) or tensors with (C, Hi, Wi) semantics of any layout,
     converted here.  Differentiable wrt ``weights`` only."""
+    who, planar = "reproj_c", False
 
     @staticmethod
-    def forward(ctx, weights, ts, deltas, pix, curr, T_prev, T_next, img_prev, img_next, img_h, img_w):
-        if not weights.is_cuda:
-            raise RuntimeError("ReprojSampleCFunction needs CUDA(HIP) tensors: selfocc_amd has no CPU fallback")
-        f = lambda t: None if t is None else t.detach().contiguous().float()
-        weights, ts, deltas, pix, curr, T_prev, T_next = (f(t) for t in (weights, ts, deltas, pix, curr, T_prev, T_next))
-        img_prev, img_next = channel_last(img_prev), channel_last(img_next)
-        R, S = weights.shape
-        C = img_prev.C
-        if img_next.C != C or img_next.data.shape != img_prev.data.shape:
-            raise ValueError(f"reproj_c: img_prev {tuple(img_prev.data.shape)} (C = {C}) and img_next "
-                             f"{tuple(img_next.data.shape)} (C = {img_next.C}) differ")
-        if curr.shape != (R, C) or pix.shape != (R, 2) or ts.shape != (R, S) or (deltas is not None and deltas.shape != (R, S)):
-            raise ValueError(f"reproj_c: need curr (R, C) = {(R, C)}, pix (R, 2) and ts / deltas of the shape of weights "
-                             f"{(R, S)}; got curr {tuple(curr.shape)}, pix {tuple(pix.shape)}, ts {tuple(ts.shape)}")
-        if T_prev.numel() != 16 or T_next.numel() != 16:
-            raise ValueError("reproj_c: the transforms must be (4, 4)")
-        tens = [weights, ts, deltas, pix, curr, T_prev, T_next, img_prev.data, img_next.data]
-        a = _args_c(*tens, C, img_h, img_w)
-        dev = weights.device
-        l1 = torch.empty(R, device=dev)
-        comb = torch.empty(R, C, device=dev)
-        anyv = torch.empty(R, device=dev)
-        a.l1, a.combine, a.any_valid = ptr(l1), ptr(comb), ptr(anyv)
-        check(lib().selfocc_reproj_c_fwd(a, current_stream(dev)), "selfocc_reproj_c_fwd")
-        # saved through autograd, like ReprojSampleFunction: an in-place change of `weights` before backward is an error
-        ctx.has_deltas = deltas is not None
-        ctx.save_for_backward(*[t for t in tens if t is not None])
-        ctx.chw = (C, img_h, img_w)
-        ctx.mark_non_differentiable(anyv)
-        return l1, comb, anyv
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_l1, g_comb, _g_any):
-        tens = list(ctx.saved_tensors)
-        if not ctx.has_deltas:
-            tens.insert(2, None)
-        a = _args_c(*tens, *ctx.chw)
-        g_l1 = g_l1.contiguous().float()
-        g_comb = g_comb.contiguous().float()
-        g_w = torch.zeros_like(tens[0])
-        check(lib().selfocc_reproj_c_bwd(a, ptr(g_l1), ptr(g_comb), ptr(g_w), current_stream(g_w.device)),
-              "selfocc_reproj_c_bwd")
-        return (g_w,) + (None,) * 10
+    def _image(img):
+        img = channel_last(img)
+        return img.data, img.C
 
 
 class ReprojPickFunction(Function):

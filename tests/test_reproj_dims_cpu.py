@@ -1,4 +1,4 @@
-"""CPU: the host side of the channel-generic reprojection entry (selfocc_reproj_c_fwd / _bwd) and of the losses' ``dims``
+"""CPU: the host side of the channel-last reprojection entries (selfocc_reproj_c_fwd / _bwd, csrc/reproj.hip) and of the losses' ``dims``
 knob: struct layout, every refusal before any device is touched, the loss classes' argument errors."""
 import ctypes as C
 import os

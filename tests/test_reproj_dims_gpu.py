@@ -1,5 +1,5 @@
-"""GPU: the channel-generic reprojection sampling (selfocc_reproj_c_fwd / _bwd, csrc/reproj_c.hip) and the ``dims`` knob of
-the two reprojection losses.
+"""GPU: the reprojection sampling on channel-last images of any channel count (selfocc_reproj_c_fwd / _bwd: csrc/reproj.hip's one
+kernel with its channel-last tap fetch) and the ``dims`` knob of the two reprojection losses.
 
 1. The kernel against float64, by the rule of tests/test_reproj_gpu.py (its module docstring states it in full): the
    reference is the torch-op port of the reference lines in float64 on the float32-rounded inputs (tests/reproj_dims_port.py:
@@ -9,18 +9,21 @@ the two reprojection losses.
    The geometry is that file's ``make_case``; only the images and the current values are drawn anew with C channels.
    Measured pairs (kernel, float32 port) go to parity_out/reproj_dims_parity.jsonl.
 2. ``wnorm`` / ``any_valid`` bit for bit those of selfocc_reproj_fwd on the same geometry.
-3. C = 3 through the new entry against the old entry, within the same yardstick.
+3. C = 3 through the channel-last entries against the planar entries: one kernel body with two tap fetches, so l1, combine
+   and any_valid agree in every bit and the gradient in every value, at every samples-per-lane instance.
 4. Pad channels filled with NaN change no bit of any output.
 5. Two runs of one launch are bit-identical (inside every case of 1).
-6. The loss classes against tests/golden/reproj_dims.npz (the reference's own classes with dims = 1, 5, 16), with the bounds of
+6. The one Python body of ReprojSampleFunction / ReprojSampleCFunction: a planar call equals the raw C entry, and a wrong
+   shape is a ValueError before any launch.
+7. The loss classes against tests/golden/reproj_dims.npz (the reference's own classes with dims = 1, 5, 16), with the bounds of
    test_golden_gpu.py::test_reproj_losses_vs_reference_class.
-7. One dims = 16 forward + backward of each class under torch.cuda.set_sync_debug_mode("error").
+8. One dims = 16 forward + backward of each class under torch.cuda.set_sync_debug_mode("error").
 
 Measured on MI355X (worst case over the nine cases of 1 and the two of 3; float32 port in brackets; profiles/
 reproj_dims_parity.jsonl): l1 1.21e-5 (1.20e-5), combine 1.56e-5 (1.56e-5); e_r 2.63e-4 (2.64e-4), l1 term alone 1.35e-4
 (1.37e-4), combine term alone 2.68e-4 (2.69e-4), the kernel never above 1.21 x the port on a figure above its floor;
-ill-conditioned rays 3.2e-6 of T'_r (port, all rays: 1.4e-5); rays left out as undecided: 0 - 11 of 301.  On the two 3-channel
-cases of 3 the new entry equals the old one in every bit.
+ill-conditioned rays 3.2e-6 of T'_r (port, all rays: 1.4e-5); rays left out as undecided: 0 - 11 of 301.  On the four 3-channel
+cases of 3 the channel-last entry equals the planar one in every bit.
 """
 import json
 import os
@@ -200,8 +203,8 @@ def test_reproj_c_vs_float64(hip, name, kw):
         assert (r["mp"] ^ r["mn"]).double().mean().item() >= 0.10     # samples with exactly one valid frame
 
 
-def _raw_fwd(hip, case, generic):
-    """one forward through the C entry itself, with `wnorm`: -> wnorm (R, S), any_valid (R)"""
+def _raw_fwd(hip, case, generic, full=False):
+    """one forward through the C entry itself, with `wnorm`: -> wnorm (R, S), any_valid (R); full: l1 (R), combine (R, C) too"""
     w, ts, deltas, pix, curr, T_prev, T_next, img_prev, img_next, img_h, img_w = to_dev(case)
     R, S = w.shape
     C = curr.shape[1]
@@ -227,7 +230,7 @@ def _raw_fwd(hip, case, generic):
     else:
         a.rgb_combine = ptr(comb)
         check(hip.selfocc_reproj_fwd(a, current_stream(D0)), "selfocc_reproj_fwd")
-    return wnorm.cpu(), anyv.cpu()
+    return (wnorm.cpu(), anyv.cpu()) + ((l1.cpu(), comb.cpu()) if full else ())
 
 
 @pytest.mark.parametrize("C", [1, 5, 99])
@@ -246,9 +249,13 @@ def test_wnorm_and_any_valid_are_the_three_channel_entry_s_bits(hip, C):
 
 
 def test_three_channels_new_entry_against_old_entry(hip):
-    """the same 3-channel case through both entries: their distance is within the yardstick either is held to against float64
-    (4 x the float32 port's error).  Bit equality is not required: the order of the channel sum is the implementer's."""
-    for name, kw in (("S100_d", dict(R=301, S=100, with_deltas=True)), ("S256_img", dict(R=301, S=256, img_hw=(50, 77)))):
+    """the same 3-channel case through both pairs of entries: within the yardstick either is held to against float64 (4 x the
+    float32 port's error), and, both being one kernel body that differs in the tap fetch alone, equal: l1, combine and any_valid
+    in every bit, the gradient in every value (the sign of an exact zero is free).  S: M = 2 and 4 on whole images, M = 1 and 8
+    on a small image with masked rays and samples."""
+    small = dict(R=61, img_hw=(24, 50), with_deltas=True, outside=0.2, edge=0.2)
+    for name, kw in (("S100_d", dict(R=301, S=100, with_deltas=True)), ("S256_img", dict(R=301, S=256, img_hw=(50, 77))),
+                     ("S12_d_small", dict(S=12, **small)), ("S512_d_small", dict(S=512, **small))):
         case = list(make_case(seed=4000 + kw["S"], **kw))
         r = check_case("C3_both_" + name, case)
         n_l1, n_comb, n_any, n_g = r["out"]
@@ -262,6 +269,24 @@ def test_three_channels_new_entry_against_old_entry(hip):
               f"bit-equal {torch.equal(n_l1, o_l1) and torch.equal(n_comb, o_comb) and torch.equal(n_g, o_g)}")
         assert d_l1 <= max(4 * m["l1"][1], 1e-6) and d_comb <= max(4 * m["combine"][1], 1e-6), (d_l1, d_comb, m)
         assert e <= max(4 * m["grad"][1], 1e-5) and e_ill <= max(4 * m["grad_ill"][1], 1e-5), (e, e_ill, m)
+        assert torch.equal(n_l1, o_l1) and torch.equal(n_comb, o_comb) and torch.equal(n_g, o_g), name
+
+
+def test_planar_call_is_the_raw_entry_and_checks_its_shapes(hip):
+    """ReprojSampleFunction shares its body, the shape checks included, with ReprojSampleCFunction: a valid planar call
+    returns what selfocc_reproj_fwd itself returns, a wrong ``curr`` or transform is refused before any launch (either
+    would be read out of bounds)"""
+    case = list(make_case(R=61, S=65, seed=6065, img_hw=(24, 50)))
+    dev = to_dev(case)
+    l1, comb, anyv = ReprojSampleFunction.apply(*dev)
+    _, r_any, r_l1, r_comb = _raw_fwd(hip, case, generic=False, full=True)
+    assert torch.equal(l1.cpu(), r_l1) and torch.equal(comb.cpu(), r_comb) and torch.equal(anyv.cpu(), r_any)
+    assert r_any.sum() > 0 and r_l1.abs().max() > 0
+    for i, bad in ((4, dev[4][:, :2]), (4, dev[4][:-1]), (5, dev[5][:3]), (6, dev[6][:, :3])):
+        args = list(dev)
+        args[i] = bad
+        with pytest.raises(ValueError):
+            ReprojSampleFunction.apply(*args)
 
 
 @pytest.mark.parametrize("C", [1, 5, 99])
